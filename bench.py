@@ -61,7 +61,12 @@ def main():
     ap.add_argument("--require-library-merge", action="store_true",
                     help="N > 1: exit non-zero when the library's own RCCL communicator cannot be created on every rank, instead of "
                          "falling back to the torch collective + host reduce")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned (group keys, aggregation results, execution statistics) as "
+                         "DIR/<name>.npy, float64, at most 64 MB in all; the inputs are a pure function of the arguments")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # not launched by torchrun: spawn the N ranks ourselves (one process per GPU, rendezvous on 127.0.0.1)
@@ -209,6 +214,8 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(dense, args.dump_outputs)
 
     total_rows = float(args.docs) * world * args.steps
     value = total_rows / elapsed
@@ -345,6 +352,48 @@ def main():
         seg.destroy()
     if world > 1:
         dist.destroy_process_group()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(result, out_dir, limit_bytes=DUMP_LIMIT_BYTES):
+    """--dump-outputs: the arrays the timed step handed its caller, as float64 .npy files, so that two builds can be compared output for
+    output.  A ResultsBlock is written in group-key order (the kernels may emit groups in any order): `group_keys` [groups, group-by
+    columns] (decoded values), one `agg<i>_<function>_<column>[_<component>]` per aggregation component (HLL registers as [groups, 2^log2m]),
+    and `stats` (numDocsScanned, numEntriesScannedInFilter, numEntriesScannedPostFilter, numTotalDocs, numGroupsLimitReached).  Above
+    `limit_bytes` a fixed, seeded sample of the groups is written.  The fallback merge of N > 1 ranks hands back a DenseGroupTable:
+    its SUM / MAX / MIN rows in dense-key order."""
+    from pinot_amd import capi
+    from pinot_amd.distributed import DenseGroupTable
+    os.makedirs(out_dir, exist_ok=True)
+    if isinstance(result, DenseGroupTable):
+        for name in ("sum_rows", "max_rows", "min_rows"):
+            np.save(os.path.join(out_dir, name + ".npy"), getattr(result, name).astype(np.float64))
+        return
+    ng = result.num_groups
+    per_group = {}
+    if result.query.group_by:
+        per_group["group_keys"] = np.array([[np.nan if v is None else v for v in k] for k in result.group_keys],
+                                           dtype=np.float64).reshape(ng, len(result.query.group_by))
+    for i, (spec, arr) in enumerate(zip(result.query.aggregations, result.arrays)):
+        if arr[0] not in (capi.RESULT_LONG, capi.RESULT_DOUBLE, capi.RESULT_AVG_PAIR, capi.RESULT_MINMAX_PAIR, capi.RESULT_HLL):
+            raise SystemExit(f"--dump-outputs: no fixed-shape array form for the result of {spec.function}")
+        name = f"agg{i}_{spec.function.lower()}_{spec.column or 'star'}"
+        for c, comp in enumerate(arr[1:]):
+            per_group[name + (f"_{c}" if len(arr) > 2 else "")] = comp.astype(np.float64)
+    keys = per_group.get("group_keys")
+    order = np.lexsort(keys.T[::-1]) if keys is not None and ng > 1 else np.arange(ng)
+    total = sum(a.nbytes for a in per_group.values())
+    budget = limit_bytes - 4096 * (len(per_group) + 1)   # (room for the .npy headers and `stats`)
+    if total > budget:
+        keep = int(ng * budget // total)
+        order = order[np.sort(np.random.default_rng(0).choice(ng, size=keep, replace=False))]
+    for name, a in per_group.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a[order])
+    s = result.stats
+    np.save(os.path.join(out_dir, "stats.npy"), np.array([s.num_docs_scanned, s.num_entries_scanned_in_filter, s.num_entries_scanned_post_filter,
+                                                          s.num_total_docs, s.num_groups_limit_reached], dtype=np.float64))
 
 
 def validate_multi_gpu(api, args, seg, qc, sql, columns, comm, merged, rank, world, local_rank):

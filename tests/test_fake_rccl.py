@@ -23,8 +23,10 @@ class UniqueId(C.Structure):
 @pytest.fixture(scope="module")
 def fake():
     subprocess.check_call(["make", "-s", "-C", os.path.join(HERE, "fake_rccl")])
-    os.environ["FAKE_RCCL_HOST_BUFFERS"] = "1"
-    os.environ["FAKE_RCCL_TIMEOUT_MS"] = "400"
+    # undone after the module: a worker of tests/test_gpu_fake_rccl.py started later in the same session must not inherit host buffers
+    mp = pytest.MonkeyPatch()
+    mp.setenv("FAKE_RCCL_HOST_BUFFERS", "1")
+    mp.setenv("FAKE_RCCL_TIMEOUT_MS", "400")
     lib = C.CDLL(LIB)
     lib.ncclCommInitAll.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_int)]
     lib.ncclCommInitRank.argtypes = [C.POINTER(C.c_void_p), C.c_int, UniqueId, C.c_int]
@@ -34,7 +36,8 @@ def fake():
     lib.ncclCommDestroy.argtypes = [C.c_void_p]
     for f in ("fake_rccl_lonely_ranks", "fake_rccl_mismatched_collectives", "fake_rccl_collectives"):
         getattr(lib, f).restype = C.c_int64
-    return lib
+    yield lib
+    mp.undo()
 
 
 def _init_all(lib, n):

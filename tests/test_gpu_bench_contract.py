@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -19,9 +20,10 @@ def last_json_line(out):
     return json.loads(lines[-1])
 
 
-def test_bench_line_on_a_small_segment():
+def test_bench_line_on_a_small_segment(tmp_path, oracle_api):
+    dump = str(tmp_path / "outputs")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--docs", "3000000", "--steps", "3", "--warmup", "1", "--no-traffic",
-                          "--cpu-sample-docs", "1000000"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                          "--cpu-sample-docs", "1000000", "--dump-outputs", dump], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     d = last_json_line(out)
     for k in REQUIRED:
@@ -44,6 +46,18 @@ def test_bench_line_on_a_small_segment():
     # the library merge with nothing to exchange (communicator of one rank): its latency is on record, its result the unmerged one
     m = d["merge_world_of_one"]
     assert m.get("error") is None and m["p50_ms"] > 0 and m["equals_unmerged_result"] is True
+    # --dump-outputs: the timed step's result, array for array the oracle's on the same segment
+    import bench
+    from pinot_amd import synth
+    from pinot_amd.executor import NativeSegment
+    seg = NativeSegment(oracle_api, synth.generate_segment(3000000, columns=list(synth.CFG3_COLUMNS)))
+    bench.dump_outputs(seg.execute(synth.QUERY_CFG3), str(tmp_path / "oracle"))
+    seg.destroy()
+    names = sorted(os.listdir(dump))
+    assert names == sorted(os.listdir(tmp_path / "oracle")) and "group_keys.npy" in names
+    for f in names:
+        a, b = np.load(os.path.join(dump, f)), np.load(tmp_path / "oracle" / f)
+        assert a.dtype == np.float64 and np.array_equal(a, b), f
 
 
 def test_bench_under_torchrun_with_one_rank():

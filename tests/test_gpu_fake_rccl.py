@@ -22,6 +22,7 @@ def test_all_reduce_ranks_on_one_device(world):
     if not os.path.exists(FAKE):
         subprocess.check_call(["make", "-s", "-C", os.path.join(HERE, "fake_rccl")])
     env = dict(os.environ, PG_RCCL_LIBRARY=FAKE, FAKE_RCCL_TIMEOUT_MS="30000")
+    env.pop("FAKE_RCCL_HOST_BUFFERS", None)   # the tables are in HBM: the double must not treat them as host memory
     p = subprocess.run([sys.executable, os.path.join(HERE, "fake_rccl_worker.py"), str(world)], cwd=ROOT, env=env, capture_output=True,
                        text=True, timeout=900)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
