@@ -243,6 +243,25 @@ typedef struct pg_query {
                                               FastFilteredCountOperator, which knows no nulls (AggregationPlanNode.java:104-108).  Refused
                                               (PG_ERR_UNSUPPORTED: the Java plan answers): nulls in a multi-value column, more than 3 nullable
                                               group-by columns, more groups than numGroupsLimit across their null partitions, PG_QUERY_FLAG_KEEP_DEVICE_TABLE next to nulls */
+/* SELECT DISTINCT (DistinctOperator, pinot-core/.../operator/query/DistinctOperator.java).  group_by_columns / n_group_by are the DISTINCT
+   expressions (plain columns), n_aggregations must be 0, order_by entries are PG_ORDER_BY_GROUP_KEY and `limit` is always read (INT32_MAX:
+   unbounded); num_groups_limit and min_segment_group_trim_size are ignored.  The tuples come back through pg_result_num_groups /
+   _group_dict_ids / _group_key_type / _group_values_* / _group_values_bytes* like group keys, one row per tuple: sorted under ORDER BY (the
+   remaining columns ascending after the ORDER BY ones); without ORDER BY and a bounded limit in the order of their first matching docId —
+   the first `limit` tuples in docId order, as the reference's executors keep them; with limit INT32_MAX (every tuple, an unordered set in
+   the reference) in key order.  With ORDER BY over fewer columns than the DISTINCT list, which tuples tied at the
+   cut survive is unspecified (a heap in the reference).  pg_result_data_table_v4 writes DistinctTable#toDataTable (typed columns, one row per
+   tuple).  ExecutionStatistics: no filter, one column with a dictionary: answered from the dictionary (DictionaryBasedDistinctOperator:
+   numDocsScanned = numEntriesScannedPostFilter = the values kept, an upsert snapshot does not matter); otherwise numDocsScanned = the matching
+   docs of the 10 000-doc blocks read until the limit was reached (all of them under ORDER BY or when fewer tuples exist),
+   numEntriesScannedPostFilter = numDocsScanned x columns.  numEntriesScannedInFilter is exact when the whole filter is consumed and, under an
+   early stop, for no filter, index-only filters and a filter that is one scan predicate (the scan's whole 256-doc batches up to the last
+   consumed match); other early-stopped filters report the whole filter's count with stats_exact = 0.  Refused (PG_ERR_UNSUPPORTED: the Java
+   plan answers): more than 8 columns, multi-value columns, a column holding nulls under PG_QUERY_FLAG_NULL_HANDLING, ORDER BY over a raw
+   STRING / BYTES column, key spaces (the product of the columns' cardinalities) over 2^32, a column without values (an empty segment's:
+   cardinality 0), limit <= 0, expressions.  Only the filter's plan is cached (the DISTINCT shape is re-derived per call: no kernel plan).  pg_result_merge / pg_result_all_reduce refuse
+   distinct results (DistinctCombineOperator merges them by value). */
+#define PG_QUERY_FLAG_DISTINCT 0x80
 #define PG_QUERY_FLAG_KEEP_DEVICE_TABLE 0x4 /* keep the dense accumulator table in HBM with the result (pg_result_merge / _all_reduce) */
 
 /* ExecutionStatistics (pinot-core/.../operator/ExecutionStatistics.java) + device timings. */

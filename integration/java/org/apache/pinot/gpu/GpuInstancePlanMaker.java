@@ -94,6 +94,21 @@ public class GpuInstancePlanMaker extends InstancePlanMakerImplV2 {
     IndexSegment segment = segmentContext.getIndexSegment();
     // (enableNullHandling travels in the query record: three-valued filters, null-skipping aggregations and null group keys are answered by
     // the library — results and keys come back with NULL flags, GpuGroupByOperator#blockOf; it refuses nulls in multi-value columns)
+    // SELECT DISTINCT (and the broker's rewrite of a GROUP BY without aggregations into it): GpuDistinctOperator over PG_QUERY_FLAG_DISTINCT
+    if (segment instanceof ImmutableSegment && QueryContextUtils.isDistinctQuery(queryContext)) {
+      long handle = _registry.handleFor((ImmutableSegment) segment, segmentContext);
+      if (handle != 0) {
+        NativeQuery nativeQuery = NativeQuery.fromDistinct(queryContext);
+        if (nativeQuery != null) {
+          if (PinotGpu.querySupported(handle, nativeQuery.address()) == PinotGpu.PG_OK) {
+            return () -> new GpuDistinctOperator(segment, queryContext, handle, nativeQuery,
+                () -> super.makeSegmentPlanNode(segmentContext, queryContext).run());
+          }
+          nativeQuery.close();
+        }
+      }
+      return super.makeSegmentPlanNode(segmentContext, queryContext);
+    }
     if (segment instanceof ImmutableSegment && QueryContextUtils.isAggregationQuery(queryContext)) {
       long handle = _registry.handleFor((ImmutableSegment) segment, segmentContext);   // pins the columns in HBM on first use; 0: Java plan only
       if (handle != 0) {

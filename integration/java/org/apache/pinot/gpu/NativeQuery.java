@@ -37,6 +37,7 @@ public final class NativeQuery implements AutoCloseable {
   private static final int FLAG_NULL_HANDLING = 0x40;
 
   private static final int FLAG_KEEP_DEVICE_TABLE = 0x4;   // PG_QUERY_FLAG_KEEP_DEVICE_TABLE
+  private static final int FLAG_DISTINCT = 0x80;          // PG_QUERY_FLAG_DISTINCT
 
   private final long _address;
   private final int _flags;
@@ -106,6 +107,39 @@ public final class NativeQuery implements AutoCloseable {
       return null;
     }
     return new NativeQuery(PinotGpu.queryParse(b, b.position()), extraFlags);
+  }
+
+  /**
+   * SELECT DISTINCT (PG_QUERY_FLAG_DISTINCT): the DISTINCT expressions in the group-by slots, no aggregation, every ORDER BY expression a
+   * group-key entry, LIMIT always read (Integer.MAX_VALUE: every tuple).  null when an expression is not a plain column (the Java plan answers).
+   */
+  public static NativeQuery fromDistinct(QueryContext q) {
+    List<ExpressionContext> columns = q.getSelectExpressions();
+    List<OrderByExpressionContext> orderBy = q.getOrderByExpressions();
+    int numOrderBy = orderBy == null ? 0 : orderBy.size();
+    ByteBuffer b = ByteBuffer.allocateDirect(estimate(q)).order(ByteOrder.LITTLE_ENDIAN);
+    b.putInt(MAGIC).putInt(FLAG_DISTINCT | (q.isNullHandlingEnabled() ? FLAG_NULL_HANDLING : 0)).putInt(q.getNumGroupsLimit())
+        .putInt(q.getMaxInitialResultHolderCapacity()).putInt(columns.size()).putInt(0)
+        .putInt(q.getFilter() == null ? 0 : 1).putInt(numOrderBy);
+    b.putInt(q.getLimit()).putInt(-1);
+    for (ExpressionContext e : columns) {
+      if (e.getType() != ExpressionContext.Type.IDENTIFIER) {
+        return null;
+      }
+      putString(b, e.getIdentifier());
+    }
+    for (int i = 0; i < numOrderBy; i++) {
+      OrderByExpressionContext o = orderBy.get(i);
+      int index = columns.indexOf(o.getExpression());
+      if (index < 0) {
+        return null;
+      }
+      b.putInt(0).putInt(index).putInt(o.isAsc() ? 1 : 0).putInt(o.isNullsLast() ? 1 : 0);   // PG_ORDER_BY_GROUP_KEY
+    }
+    if (q.getFilter() != null && !putFilter(b, q.getFilter())) {
+      return null;
+    }
+    return new NativeQuery(PinotGpu.queryParse(b, b.position()), FLAG_DISTINCT);
   }
 
   /** {kind, index, ascending, nullsLast} per ORDER BY expression (pg_order_by), or null when the query has none or one the record cannot carry. */

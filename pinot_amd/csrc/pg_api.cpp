@@ -253,6 +253,11 @@ int32_t pg_query_supported(pg_segment_t segment, const pg_query* query) {
     use_device(segment->seg.device);
     // compiled under the segment's lock and cached: the pg_query_exec that follows finds the plan (PlanMaker calls supported()
     // then exec() from many worker threads); throws PG_ERR_UNSUPPORTED for shapes off the GPU path
+    if (query->flags & PG_QUERY_FLAG_DISTINCT) {   // the checks of the DISTINCT path; its filter plan is compiled and cached
+      (void)distinct_shape(segment->seg, *query);
+      (void)get_plan(segment->seg, query->filter, nullptr, query->flags & PG_QUERY_FLAG_NULL_HANDLING);
+      return;
+    }
     check_null_handling(segment->seg, *query);
     (void)get_plan(segment->seg, query->filter, query);
   });
@@ -293,12 +298,14 @@ int32_t pg_query_exec_cancellable(pg_segment_t segment, const pg_query* query, p
 int32_t pg_result_merge(pg_result_t dst, pg_result_t src) {
   return guarded([&] {
     REQUIRE(dst && src && dst != src, "null or identical results");
+    if (dst->r->distinct || src->r->distinct) fail(PG_ERR_UNSUPPORTED, "distinct results are merged by value (DistinctCombineOperator)");
     result_merge(*dst->r, *src->r);
   });
 }
 int32_t pg_result_all_reduce(pg_result_t result, pg_comm_t comm) {
   return guarded([&] {
     REQUIRE(result && comm && comm->c, "null argument");
+    if (result->r->distinct) fail(PG_ERR_UNSUPPORTED, "distinct results are merged by value (DistinctCombineOperator)");
     result_all_reduce(*result->r, *comm->c);
   });
 }

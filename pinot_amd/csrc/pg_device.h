@@ -439,6 +439,32 @@ PG_HD static inline int64_t pg_acc_identity(int32_t fn, int32_t is_float) {
 #define PG_TRIM_CTRL_HIST 64
 #define PG_TRIM_CTRL_WORDS (PG_TRIM_CTRL_HIST + 8 * 256)
 
+// SELECT DISTINCT (pg_kernels_distinct.hip): a presence bitmap over the mixed-radix key space of the DISTINCT columns' dictIds (or virtual
+// dictionary ids), then a select of its first set bits.  A select chunk is PG_DISTINCT_CHUNK_WORDS 32-bit words (2^18 keys or docs).
+#define PG_DISTINCT_CHUNK_WORDS 8192
+#define PG_DISTINCT_LDS_MAX_KEYS (1 << 20)   // key spaces up to this many keys keep one bitmap per workgroup in LDS (128 KiB)
+#define PG_DISTINCT_GROUP_WORDS 8            // rank granule of the first-doc pass: one prefix per 8 words (256 keys)
+struct PgDistinctCol {
+  const uint8_t* data;   // fixed-bit ids (dictIds, or ids of the column's virtual dictionary), MSB-first big-endian bit stream
+  uint64_t mult;         // weight of the column's digit in the key
+  int32_t bits;
+  int32_t card;
+  int32_t desc;          // the digit is card - 1 - id (ORDER BY ... DESC)
+  int32_t pad;
+};
+struct PgDistinctArgs {
+  const uint64_t* match;       // the filter's match words: bit b of word w is doc 64 w + b
+  int64_t w_begin, w_end;      // the match words this pass reads
+  int32_t n_cols;
+  int32_t pad;
+  PgDistinctCol cols[PG_MAX_GROUP_COLS];
+  uint32_t* keys;              // presence pass: the bitmap the keys are set in (HBM); first-doc pass: the new keys of the window (read)
+  const uint32_t* seen;        // nullable: keys of earlier windows, skipped by the presence pass
+  int64_t key_words;           // 32-bit words of a key bitmap
+  const uint32_t* group_rank;  // first-doc pass: rank of the first key of every PG_DISTINCT_GROUP_WORDS-word group among the new keys
+  uint32_t* first_doc;         // first-doc pass: per new key (by rank) its smallest matching docId
+};
+
 struct PgTrimArgs {
   const int64_t* table;     // [n_ops][G]
   int64_t G;

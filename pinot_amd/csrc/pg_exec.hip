@@ -47,6 +47,7 @@ extern "C" const int pg_specw_waves_per_block;   // pg_kernels_specw.hip: pg_fas
 extern "C" int pg_specw_stage_bytes(int scan_bits, int value_bits, int bits0, int bits1, int n_bitmaps);
 extern "C" int pg_specw_list_bytes();
 PG_DECL_FAST(pg_fast_multi_wd) PG_DECL_FAST(pg_fast_none_wd) PG_DECL_FAST(pg_generic_query_ld) PG_DECL_FAST(pg_generic_query_gd)
+extern "C" __global__ void pg_distinct_keys_lds(const PgDistinctArgs a);   // pg_kernels_distinct.hip: up to 128 KiB of dynamic LDS
 extern "C" __global__ void pg_reduce_partials_kernel(const int64_t* partials, int64_t* out, int n_wg, int n_ops,
                                                      int n_groups, const PgAccOp* ops, unsigned long long* stats, int reduce);
 extern "C" __global__ void pg_reduce_parts_kernel(const int64_t* partials, int64_t* out, int n_wg, int n_ops, int n_groups,
@@ -342,6 +343,7 @@ void use_device(int ordinal) {
       for (QueryKernel k : {pg_mv_query_f, pg_mv_query_l, pg_mv_query_g})   // 10.5 KB of static LDS (per-wavefront entry bitmaps): the planner's 144 KB still fit
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 12288);
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pg_radix_scatter_packed_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 8192);
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pg_distinct_keys_lds), hipFuncAttributeMaxDynamicSharedMemorySize, PG_DISTINCT_LDS_MAX_KEYS / 8);
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pg_radix_aggregate_packed_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 8192);
       (void)hipGetLastError();   // a refused attribute must not surface as the "last error" of a later launch
       di.ready.store(1, std::memory_order_release);
@@ -480,6 +482,13 @@ static int pinned_spec_shape(const CompiledPlan& P, int agg_mode) {
 static bool uses_spec_kernel(const CompiledPlan& P, int agg_mode) { return pinned_spec_shape(P, agg_mode) != 0; }
 
 extern "C" void pg_trim_launch(const PgTrimArgs* args, int grid, hipStream_t stream);
+extern "C" void pg_distinct_launch_keys(const PgDistinctArgs* args, int mode, int grid, hipStream_t stream);   // pg_kernels_distinct.hip
+extern "C" void pg_distinct_launch_count(const uint32_t* bm, int64_t n_chunks, uint32_t* counts, hipStream_t stream);
+extern "C" void pg_distinct_launch_rank(const uint32_t* bm, int64_t n_chunks, const uint64_t* chunk_off, uint32_t* group_rank, hipStream_t stream);
+extern "C" void pg_distinct_launch_expand(const uint32_t* bm, int64_t n_chunks, const uint64_t* chunk_off, uint64_t n_out, uint32_t* out, hipStream_t stream);
+extern "C" void pg_distinct_launch_mark(const uint32_t* first_doc, int64_t n, uint32_t* doc_bits, int grid, hipStream_t stream);
+extern "C" void pg_distinct_launch_fold(uint32_t* seen, uint32_t* fresh, const uint32_t* counts, int64_t n_chunks, hipStream_t stream);
+extern "C" void pg_distinct_launch_decode(const PgDistinctArgs* args, const uint32_t* pos, int64_t n, int from_docs, int32_t* out, int grid, hipStream_t stream);
 extern "C" void pg_trim_launch_keys(const PgTrimArgs* args, int grid, hipStream_t stream);
 extern "C" void pg_trim_launch_select(const PgTrimArgs* args, int grid, hipStream_t stream);
 typedef void (*QueryKernel)(const PgQueryPlan);
@@ -604,6 +613,7 @@ struct ThreadCtx {
   DeviceBuffer aux_summary;   // PG_QUERY_FLAG_FINAL_DISTINCT: [n_aux][G] final values
   DeviceBuffer fs_leaves, fs_arena;   // exact numEntriesScannedInFilter on the device: the leaves' match bitmaps, scratch (pg_filter_stats.cpp)
   DeviceBuffer trim_keys, trim_ctrl, trim_out;   // segment-level group trim on the device: [G] keys, counters, the compact block
+  DeviceBuffer dist_seen, dist_fresh, dist_docs, dist_counts, dist_off, dist_rank, dist_first, dist_pos, dist_ids;   // SELECT DISTINCT (execute_distinct)
   size_t aux_clean_bytes = 0;    // the first bytes of `aux` are zero (pg_finish_fused_kernel re-zeroes the states it folds): the next query's fill is skipped
   const void* aux_clean_ptr = nullptr;
   DeviceBuffer hll_small[17];  // per log2m: round(m * ln(m / zeros)), zeros = 0 .. m
@@ -1278,6 +1288,308 @@ struct AdmissionGuard {
   }
 };
 }  // namespace
+
+// ---- SELECT DISTINCT (PG_QUERY_FLAG_DISTINCT) --------------------------------------------------------------------------------------------------
+// DictionaryBasedDistinctOperator (core/operator/query/DictionaryBasedDistinctOperator.java:104-142): the first min(limit, cardinality)
+// dictionary values (the last ones under ORDER BY ... DESC), numDocsScanned = numEntriesScannedPostFilter = the values kept.
+// DistinctOperator (:58-67): 10 000-doc blocks of the filter's docs until the executor's limit is reached — without ORDER BY the first `limit`
+// tuples in docId order (DictionaryBased{Single,Multi}ColumnDistinctExecutor stop after the block that completes them), with ORDER BY the top
+// `limit` tuples of the whole filter result.  The stages are those of pg_kernels_distinct.hip.
+namespace {
+constexpr int64_t kDistinctBlockDocs = 10000;   // DocIdSetPlanNode.MAX_DOC_PER_CALL
+constexpr int64_t kScanBatchDocs = 256;         // SVScanDocIdIterator batches (BlockDocIdIterator.OPTIMAL_ITERATOR_BATCH_SIZE)
+
+int64_t chunks_of_bits(uint64_t bits) {
+  const uint64_t words = (bits + 31) / 32;
+  return (int64_t)((words + PG_DISTINCT_CHUNK_WORDS - 1) / PG_DISTINCT_CHUNK_WORDS);
+}
+
+// the match words of the 16 384-doc tile `tile` on the host
+void tile_words(const DocIdSet& s, int64_t tile, ThreadCtx& ctx, uint64_t* w) {
+  PG_HIP(hipMemcpyAsync(w, s.words.as<uint64_t>() + tile * PG_TILE_WORDS, PG_TILE_WORDS * 8, hipMemcpyDeviceToHost, ctx.stream));
+  PG_HIP(hipStreamSynchronize(ctx.stream));
+}
+// docId of the k-th matching doc (1-based, k <= cardinality)
+int64_t kth_match(const DocIdSet& s, int64_t k, ThreadCtx& ctx) {
+  int64_t acc = 0, tile = 0;
+  while (tile < (int64_t)s.tile_counts.size() && acc + s.tile_counts[(size_t)tile] < k) acc += s.tile_counts[(size_t)tile++];
+  uint64_t w[PG_TILE_WORDS];
+  tile_words(s, tile, ctx, w);
+  for (int i = 0; i < PG_TILE_WORDS; i++) {
+    uint64_t v = w[i];
+    const int pc = __builtin_popcountll(v);
+    if (acc + pc < k) { acc += pc; continue; }
+    for (; acc + 1 < k; acc++) v &= v - 1;
+    return tile * PG_TILE_DOCS + (int64_t)i * 64 + __builtin_ctzll(v);
+  }
+  fail(PG_ERR_INTERNAL, "match %lld not found", (long long)k);
+}
+// matching docs with docId <= doc
+int64_t matches_through(const DocIdSet& s, int64_t doc, ThreadCtx& ctx) {
+  const int64_t tile = doc / PG_TILE_DOCS;
+  int64_t acc = 0;
+  for (int64_t t = 0; t < tile; t++) acc += s.tile_counts[(size_t)t];
+  uint64_t w[PG_TILE_WORDS];
+  tile_words(s, tile, ctx, w);
+  const int64_t in_tile = doc - tile * PG_TILE_DOCS;
+  for (int64_t i = 0; i <= in_tile / 64; i++) {
+    const uint64_t v = i < in_tile / 64 ? w[i] : w[i] & (~0ULL >> (63 - (in_tile & 63)));
+    acc += __builtin_popcountll(v);
+  }
+  return acc;
+}
+}  // namespace
+
+// the set bits of a chunked bitmap: per-chunk counts on the host, their exclusive prefix on the device (ctx.dist_off); returns the total
+static uint64_t distinct_chunk_prefix(const uint32_t* bm, int64_t n_chunks, ThreadCtx& ctx, const CancelToken* cancel, std::vector<uint32_t>& counts,
+                                      std::vector<uint64_t>& off) {
+  if (n_chunks == 0) {
+    counts.clear();
+    off.assign(1, 0);
+    return 0;
+  }
+  ThreadCtx::grow(ctx.dist_counts, (size_t)n_chunks * 4);
+  pg_distinct_launch_count(bm, n_chunks, ctx.dist_counts.as<uint32_t>(), ctx.stream);
+  PG_HIP(hipGetLastError());
+  counts.resize((size_t)n_chunks);
+  PG_HIP(hipMemcpyAsync(counts.data(), ctx.dist_counts.ptr, (size_t)n_chunks * 4, hipMemcpyDeviceToHost, ctx.stream));
+  stream_wait(ctx, cancel);
+  off.assign((size_t)n_chunks + 1, 0);
+  for (int64_t c = 0; c < n_chunks; c++) off[(size_t)c + 1] = off[(size_t)c] + counts[(size_t)c];
+  ThreadCtx::grow(ctx.dist_off, off.size() * 8);
+  PG_HIP(hipMemcpyAsync(ctx.dist_off.ptr, off.data(), off.size() * 8, hipMemcpyHostToDevice, ctx.stream));
+  return off.back();
+}
+
+// the first n_out set bits of a chunked bitmap into ctx.dist_pos (after distinct_chunk_prefix)
+static void distinct_expand(const uint32_t* bm, const std::vector<uint64_t>& off, uint64_t n_out, ThreadCtx& ctx) {
+  int64_t last = 0;
+  while (off[(size_t)last + 1] < n_out) last++;   // the chunk that holds the n_out-th bit
+  ThreadCtx::grow(ctx.dist_pos, (size_t)n_out * 4);
+  pg_distinct_launch_expand(bm, last + 1, ctx.dist_off.as<uint64_t>(), n_out, ctx.dist_pos.as<uint32_t>(), ctx.stream);
+  PG_HIP(hipGetLastError());
+}
+
+// the rows of a distinct result: per column the ids -> dictIds, or values of a raw column's virtual dictionary
+static void distinct_assemble(Result& res, const DistinctShape& S, std::vector<std::vector<int32_t>>& ids, int32_t n_rows) {
+  const size_t n = S.cols.size();
+  res.num_groups = n_rows;
+  res.group_key_type.assign(n, PG_GROUP_KEY_DICT_IDS);
+  res.group_values.assign(n, {});
+  res.group_bytes.assign(n, {});
+  res.group_bytes_off.assign(n, {});
+  res.group_dict_ids.assign(n, {});
+  for (size_t j = 0; j < n; j++) {
+    const Column* vd = S.vdicts[j];
+    const std::vector<int32_t>& v = ids[j];
+    if (!vd) { res.group_dict_ids[j] = std::move(ids[j]); continue; }
+    if (vd->vdict_kind == 4) {
+      res.group_key_type[j] = PG_GROUP_KEY_BYTES_VALUES;
+      auto& off = res.group_bytes_off[j];
+      auto& bytes = res.group_bytes[j];
+      off.resize((size_t)n_rows + 1);
+      off[0] = 0;
+      for (int32_t i = 0; i < n_rows; i++) off[(size_t)i + 1] = off[(size_t)i] + vd->vdict_bytes_off[(size_t)v[(size_t)i] + 1] - vd->vdict_bytes_off[(size_t)v[(size_t)i]];
+      bytes.resize((size_t)off[(size_t)n_rows]);
+      for (int32_t i = 0; i < n_rows; i++)
+        if (off[(size_t)i + 1] > off[(size_t)i]) memcpy(bytes.data() + off[(size_t)i], vd->vdict_bytes.data() + vd->vdict_bytes_off[(size_t)v[(size_t)i]], (size_t)(off[(size_t)i + 1] - off[(size_t)i]));
+      continue;
+    }
+    res.group_key_type[j] = vd->vdict_kind <= 1 ? PG_GROUP_KEY_LONG_VALUES : PG_GROUP_KEY_DOUBLE_VALUES;
+    auto& out = res.group_values[j];
+    out.resize((size_t)n_rows);
+    for (int32_t i = 0; i < n_rows; i++) out[(size_t)i] = vdict_value_of_key(vd->vdict_keys[(size_t)v[(size_t)i]], vd->vdict_kind, nullptr);
+  }
+}
+
+std::unique_ptr<Result> execute_distinct(Segment& seg, const pg_query& q, const CancelToken* cancel) {
+  AdmissionGuard admitted(seg.device, knobs().max_inflight);
+  const double t0 = now_ms();
+  check_cancel(cancel, nullptr);
+  ThreadCtx& ctx = ctx_on(seg.device);
+  const DistinctShape S = distinct_shape(seg, q);
+  const double t_plan = now_ms();
+  const int n_cols = q.n_group_by;
+  const int64_t limit = q.limit;
+  auto res = std::make_unique<Result>();
+  res->distinct = true;
+  pg_exec_stats& st = res->stats;
+  st.num_total_docs = seg.total_docs;
+  st.star_tree_index = -1;
+  st.stats_exact = 1;
+  std::vector<std::vector<int32_t>> ids((size_t)n_cols);
+  int32_t n_rows = 0;
+  if (S.dict_only) {
+    const int32_t card = S.cols[0]->cardinality;
+    const bool desc = S.desc[0] != 0;
+    n_rows = (int32_t)std::min<int64_t>(limit, card);
+    ids[0].resize((size_t)n_rows);
+    for (int32_t i = 0; i < n_rows; i++) ids[0][(size_t)i] = desc ? card - 1 - i : i;
+    st.num_docs_scanned = n_rows;
+    st.num_entries_scanned_post_filter = n_rows;
+    snprintf(st.kernel, sizeof(st.kernel), "pg_distinct_dictionary");
+  } else {
+    // stage 1: the filter over the segment (its match words and per-tile counts)
+    auto ds = execute_filter(seg, q.filter, q.flags & PG_QUERY_FLAG_NULL_HANDLING);
+    check_cancel(cancel, &ctx);
+    const int64_t M = ds->cardinality;
+    const int64_t n_words = (seg.total_docs + 63) / 64;
+    PgDistinctArgs A;
+    memset(&A, 0, sizeof(A));
+    A.match = ds->words.as<uint64_t>();
+    A.n_cols = n_cols;
+    for (int j = 0; j < n_cols; j++) {
+      A.cols[j].data = S.cols[(size_t)j]->fwd_dev.as<uint8_t>();
+      A.cols[j].bits = S.cols[(size_t)j]->bits;
+      A.cols[j].card = S.cols[(size_t)j]->cardinality;
+      A.cols[j].mult = S.mult[(size_t)j];
+      A.cols[j].desc = S.desc[(size_t)j];
+    }
+    const uint64_t K = S.key_space;
+    const int64_t key_chunks = chunks_of_bits(K);
+    A.key_words = (int64_t)((K + 31) / 32);
+    const bool lds = K <= PG_DISTINCT_LDS_MAX_KEYS;
+    const int mode = lds ? 0 : 1;
+    // 256-thread workgroups taking 4 match words per wavefront; in the LDS tier as many per CU as their bitmaps let fit (a small bitmap: 8)
+    const int64_t lds_wgs_per_cu = std::max<int64_t>(1, std::min<int64_t>(8, (int64_t)lds_per_cu() / (A.key_words * 4 + 2048)));
+    const int grid_max = (int)(lds ? num_cus() * lds_wgs_per_cu : num_cus() * 8);
+    auto grid_for = [&](int64_t words) { return (int)std::max<int64_t>(1, std::min<int64_t>(grid_max, (words + 15) / 16)); };
+    const size_t key_bytes = (size_t)key_chunks * PG_DISTINCT_CHUNK_WORDS * 4;
+    ThreadCtx::grow(ctx.dist_seen, key_bytes);
+    PG_HIP(hipMemsetAsync(ctx.dist_seen.ptr, 0, key_bytes, ctx.stream));
+    std::vector<uint32_t> counts;
+    std::vector<uint64_t> off;
+    PG_HIP(hipEventRecord(ctx.ev[0], ctx.stream));
+    int64_t docs_scanned = M;
+    int64_t words_read = n_words;   // match words the presence passes read
+    bool early = false;
+    // ORDER BY, and an unbounded limit (every tuple: the reference's set has no order, addUnbounded): one presence pass, the key-space select
+    const bool key_order = S.ordered || limit >= INT32_MAX;
+    if (key_order) {
+      // stage 2 over every matching doc in order space, stage 3: the first `limit` keys
+      A.keys = ctx.dist_seen.as<uint32_t>();
+      A.w_begin = 0;
+      A.w_end = n_words;
+      if (M > 0) {
+        pg_distinct_launch_keys(&A, mode, grid_for(n_words), ctx.stream);
+        PG_HIP(hipGetLastError());
+      }
+      const uint64_t total = distinct_chunk_prefix(ctx.dist_seen.as<uint32_t>(), key_chunks, ctx, cancel, counts, off);
+      n_rows = (int32_t)std::min<uint64_t>((uint64_t)limit, total);
+      if (n_rows > 0) distinct_expand(ctx.dist_seen.as<uint32_t>(), off, (uint64_t)n_rows, ctx);
+    } else {
+      // windows of docs, grown 8 x: the keys no earlier window held ("fresh"), each one's first matching docId marked in a doc bitmap
+      ThreadCtx::grow(ctx.dist_fresh, key_bytes);
+      PG_HIP(hipMemsetAsync(ctx.dist_fresh.ptr, 0, key_bytes, ctx.stream));
+      // the doc bitmap is zeroed, counted and selected only over the chunks of the windows read
+      const int64_t doc_chunks = chunks_of_bits((uint64_t)std::max(seg.total_docs, 1));
+      ThreadCtx::grow(ctx.dist_docs, (size_t)doc_chunks * PG_DISTINCT_CHUNK_WORDS * 4);
+      int64_t doc_chunks_zeroed = 0;
+      ThreadCtx::grow(ctx.dist_rank, (size_t)key_chunks * (PG_DISTINCT_CHUNK_WORDS / PG_DISTINCT_GROUP_WORDS) * 4);
+      uint64_t total = 0;
+      int64_t window = std::max<int64_t>(1024, (16 * limit + 63) / 64);   // in match words
+      for (int64_t w_lo = 0; w_lo < n_words && total < (uint64_t)limit; window *= 8) {
+        const int64_t w_hi = std::min(n_words, w_lo + window);
+        const int64_t chunks_needed = chunks_of_bits((uint64_t)w_hi * 64);
+        if (chunks_needed > doc_chunks_zeroed) {
+          PG_HIP(hipMemsetAsync(ctx.dist_docs.as<uint32_t>() + doc_chunks_zeroed * PG_DISTINCT_CHUNK_WORDS, 0,
+                                (size_t)(chunks_needed - doc_chunks_zeroed) * PG_DISTINCT_CHUNK_WORDS * 4, ctx.stream));
+          doc_chunks_zeroed = chunks_needed;
+        }
+        A.keys = ctx.dist_fresh.as<uint32_t>();
+        A.seen = ctx.dist_seen.as<uint32_t>();
+        A.w_begin = w_lo;
+        A.w_end = w_hi;
+        pg_distinct_launch_keys(&A, mode, grid_for(w_hi - w_lo), ctx.stream);
+        PG_HIP(hipGetLastError());
+        const uint64_t fresh = distinct_chunk_prefix(ctx.dist_fresh.as<uint32_t>(), key_chunks, ctx, cancel, counts, off);
+        if (fresh > 0) {
+          pg_distinct_launch_rank(ctx.dist_fresh.as<uint32_t>(), key_chunks, ctx.dist_off.as<uint64_t>(), ctx.dist_rank.as<uint32_t>(), ctx.stream);
+          ThreadCtx::grow(ctx.dist_first, (size_t)fresh * 4);
+          PG_HIP(hipMemsetAsync(ctx.dist_first.ptr, 0xFF, (size_t)fresh * 4, ctx.stream));
+          PgDistinctArgs F = A;
+          F.seen = nullptr;
+          F.group_rank = ctx.dist_rank.as<uint32_t>();
+          F.first_doc = ctx.dist_first.as<uint32_t>();
+          pg_distinct_launch_keys(&F, 2, (int)std::max<int64_t>(1, std::min<int64_t>(num_cus() * 8, (w_hi - w_lo + 15) / 16)), ctx.stream);
+          pg_distinct_launch_mark(ctx.dist_first.as<uint32_t>(), (int64_t)fresh, ctx.dist_docs.as<uint32_t>(),
+                                  (int)std::min<uint64_t>((fresh + 255) / 256, (uint64_t)num_cus() * 8), ctx.stream);
+          pg_distinct_launch_fold(ctx.dist_seen.as<uint32_t>(), ctx.dist_fresh.as<uint32_t>(), ctx.dist_counts.as<uint32_t>(), key_chunks, ctx.stream);
+          PG_HIP(hipGetLastError());
+        }
+        total += fresh;
+        w_lo = w_hi;
+        words_read = w_hi;
+        check_cancel(cancel, &ctx);
+      }
+      // stage 3 over the doc bitmap: the first `limit` first-occurrence docs, in docId order
+      const uint64_t marked = distinct_chunk_prefix(ctx.dist_docs.as<uint32_t>(), doc_chunks_zeroed, ctx, cancel, counts, off);
+      if (marked != total) fail(PG_ERR_INTERNAL, "DISTINCT: %llu first docs for %llu tuples", (unsigned long long)marked, (unsigned long long)total);
+      n_rows = (int32_t)std::min<uint64_t>((uint64_t)limit, total);
+      if (n_rows > 0) distinct_expand(ctx.dist_docs.as<uint32_t>(), off, (uint64_t)n_rows, ctx);
+      if (total >= (uint64_t)limit && n_rows > 0) {
+        // the doc that adds the limit-th tuple, its rank r among the matching docs: the operator stopped after r's 10 000-doc block
+        uint32_t t = 0;
+        PG_HIP(hipMemcpyAsync(&t, ctx.dist_pos.as<uint32_t>() + (n_rows - 1), 4, hipMemcpyDeviceToHost, ctx.stream));
+        stream_wait(ctx, cancel);
+        const int64_t r = matches_through(*ds, (int64_t)t, ctx);
+        docs_scanned = std::min(M, (r + kDistinctBlockDocs - 1) / kDistinctBlockDocs * kDistinctBlockDocs);
+        early = docs_scanned < M || M % kDistinctBlockDocs == 0;   // a full last block: the iterator never reached its end
+      }
+    }
+    if (n_rows > 0) {
+      ThreadCtx::grow(ctx.dist_ids, (size_t)n_rows * (size_t)n_cols * 4);
+      pg_distinct_launch_decode(&A, ctx.dist_pos.as<uint32_t>(), n_rows, key_order ? 0 : 1, ctx.dist_ids.as<int32_t>(),
+                                (int)std::min<int64_t>((n_rows + 255) / 256, (int64_t)num_cus() * 4), ctx.stream);
+      PG_HIP(hipGetLastError());
+      std::vector<int32_t> flat((size_t)n_rows * (size_t)n_cols);
+      PG_HIP(hipMemcpyAsync(flat.data(), ctx.dist_ids.ptr, flat.size() * 4, hipMemcpyDeviceToHost, ctx.stream));
+      PG_HIP(hipEventRecord(ctx.ev[1], ctx.stream));
+      stream_wait(ctx, cancel);
+      for (int j = 0; j < n_cols; j++) ids[(size_t)j].assign(flat.begin() + (int64_t)j * n_rows, flat.begin() + (int64_t)(j + 1) * n_rows);
+    } else {
+      PG_HIP(hipEventRecord(ctx.ev[1], ctx.stream));
+      stream_wait(ctx, cancel);
+    }
+    float ms = 0;
+    PG_HIP(hipEventElapsedTime(&ms, ctx.ev[0], ctx.ev[1]));
+    st.device_ms_filter = ds->stats.device_ms_filter;
+    st.device_ms_aggregate = ms;
+    st.device_ms_total = ds->stats.device_ms_filter + ms;
+    st.num_docs_scanned = docs_scanned;
+    st.num_entries_scanned_post_filter = docs_scanned * n_cols;
+    // numEntriesScannedInFilter: the whole filter's count unless the operator stopped early; then exact for filters that scan nothing and for
+    // one scan predicate (its iterator read whole 256-doc batches up to the last doc consumed), approximate (stats_exact = 0) otherwise
+    st.num_entries_scanned_in_filter = ds->stats.num_entries_scanned_in_filter;
+    st.stats_exact = ds->stats.stats_exact;
+    st.filter_stats_path = ds->stats.filter_stats_path;
+    if (early) {
+      const bool lone_predicate = q.filter && q.filter->type == PG_FILTER_PREDICATE && !seg.queryable_doc_ids;
+      if (ds->stats.stats_exact && ds->stats.num_entries_scanned_in_filter == 0) {
+        st.num_entries_scanned_in_filter = 0;
+      } else if (lone_predicate && ds->stats.stats_exact && ds->stats.num_entries_scanned_in_filter == seg.total_docs) {
+        const int64_t last = kth_match(*ds, docs_scanned, ctx);
+        st.num_entries_scanned_in_filter = std::min<int64_t>(seg.total_docs, (last / kScanBatchDocs + 1) * kScanBatchDocs);
+      } else {
+        st.stats_exact = 0;
+      }
+    }
+    // the filter's bytes + the bit-packed ids the presence passes read (of the docs of the windows read; a raw column's virtual dictionary ids)
+    auto plan = get_plan(seg, q.filter, nullptr, q.flags & PG_QUERY_FLAG_NULL_HANDLING);
+    int64_t id_bits = 0;
+    for (const Column* c : S.cols) id_bits += c->bits;
+    st.algorithmic_bytes = plan->algorithmic_bytes + (std::min<int64_t>(words_read * 64, seg.total_docs) * id_bits + 7) / 8;
+    snprintf(st.kernel, sizeof(st.kernel), "%s", lds ? "pg_distinct_keys_lds" : "pg_distinct_keys_hbm");
+    // work areas beyond 64 MiB (the HBM tier's bitmaps, first docIds of many keys) are not kept by the calling thread
+    for (DeviceBuffer* b : {&ctx.dist_seen, &ctx.dist_fresh, &ctx.dist_docs, &ctx.dist_rank, &ctx.dist_first, &ctx.dist_pos, &ctx.dist_ids})
+      if (b->size > ((size_t)64 << 20)) b->release();
+  }
+  distinct_assemble(*res, S, ids, n_rows);
+  fill_result_schema(seg, q, *res);
+  st.host_ms_plan = (float)(t_plan - t0);
+  st.host_ms_total = (float)(now_ms() - t0);
+  return res;
+}
 
 static std::unique_ptr<Result> execute_query_impl(Segment& seg, const pg_query& q, const CancelToken* cancel, const ExecOptions& opt) {
   AdmissionGuard admitted(seg.device, knobs().max_inflight);

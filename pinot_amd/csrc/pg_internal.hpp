@@ -332,6 +332,17 @@ struct CompiledPlan {
 void hll_registers_of_dictionary(Column& c, int log2m, uint8_t* regs);
 double dictionary_value_as_double(const Column& c, int32_t dict_id);
 std::shared_ptr<CompiledPlan> compile_plan(Segment& seg, const pg_filter_node* filter, const pg_query* query, int32_t flags = 0);   // flags: of a filter-only plan (query == nullptr)
+// SELECT DISTINCT (PG_QUERY_FLAG_DISTINCT): the checked query and its key space (pg_plan.cpp); execute_distinct runs it (pg_exec.hip)
+struct DistinctShape {
+  std::vector<Column*> cols;       // per DISTINCT column: the column of fixed-bit ids (its own dictIds, or its virtual dictionary's ids)
+  std::vector<Column*> vdicts;     // per DISTINCT column: the virtual dictionary of a raw column, or null
+  std::vector<uint64_t> mult;      // weight of the column's digit in the key (order-by columns most significant, in ORDER BY order)
+  std::vector<int32_t> desc;       // the digit is cardinality - 1 - id
+  uint64_t key_space = 1;          // product of the cardinalities (<= 2^32)
+  bool dict_only = false;          // DictionaryBasedDistinctOperator: no filter, one dictionary-encoded column
+  bool ordered = false;            // ORDER BY present
+};
+DistinctShape distinct_shape(Segment& seg, const pg_query& q);
 std::string query_signature(const pg_filter_node* filter, const pg_query* query, int32_t flags = 0);
 
 // ---- results --------------------------------------------------------------------------------------------------------------------
@@ -412,6 +423,7 @@ struct Result {
   // PG_QUERY_FLAG_NULL_HANDLING: per aggregation / per group-by column, 1 where the group's result / key is NULL (empty vector: none is)
   std::vector<std::vector<uint8_t>> agg_nulls, key_nulls;
   bool null_handling = false;   // the query ran with PG_QUERY_FLAG_NULL_HANDLING (its data table carries the columns' null bitmaps)
+  bool distinct = false;        // PG_QUERY_FLAG_DISTINCT: the groups are the distinct tuples, no aggregation (never merged in the library)
   pg_exec_stats stats{};
 };
 struct DocIdSet {
@@ -434,6 +446,7 @@ std::unique_ptr<Result> execute_query(Segment& seg, const pg_query& q, const Can
 // internal query flag (never set by callers: pg_query_exec masks it): the query is a part of a null-partitioned one — its filter is evaluated in
 // three-valued logic even where the reference's FastFilteredCountOperator would not (a lone COUNT(*) over an index-only filter)
 constexpr int32_t kQueryFlagNullPartition = 0x40000000;
+std::unique_ptr<Result> execute_distinct(Segment& seg, const pg_query& q, const CancelToken* cancel);   // PG_QUERY_FLAG_DISTINCT (pg_exec.hip)
 std::unique_ptr<Result> execute_query_plain(Segment& seg, const pg_query& q, const CancelToken* cancel);   // ... the executor proper (pg_exec.hip)
 void fill_result_schema(Segment& seg, const pg_query& q, Result& r);
 int64_t hll_cardinality(const uint8_t* regs, int log2m);   // HyperLogLog#cardinality of one register row (pg_exec.hip)

@@ -9,6 +9,7 @@
 //                                                                surviving candidates (this is what PG_F_AND_SCAN does)
 //   query/aggregation/groupby/DictionaryBasedGroupKeyGenerator.java:106-185,312-354   raw key = Σ dictId_j · Π card_<j
 #include <algorithm>
+#include <cctype>
 #include <functional>
 #include <cerrno>
 #include <cmath>
@@ -2525,6 +2526,74 @@ static std::shared_ptr<CompiledPlan> compile_in_space(Segment& seg, OpPtr root_o
     }
   }
   return plan;
+}
+
+// ---- SELECT DISTINCT --------------------------------------------------------------------------------------------------------------------------
+// DistinctPlanNode (core/plan/DistinctPlanNode.java:50-77): no filter and one column with a dictionary -> DictionaryBasedDistinctOperator; every
+// other shape -> DistinctOperator over the filter's docs.  Here: the checks of the GPU path and the key space of the presence bitmap.
+DistinctShape distinct_shape(Segment& seg, const pg_query& q) {
+  if (q.n_aggregations != 0) fail(PG_ERR_INVALID_ARGUMENT, "PG_QUERY_FLAG_DISTINCT with %d aggregations (must be 0)", q.n_aggregations);
+  if (q.n_group_by < 1 || !q.group_by_columns) fail(PG_ERR_INVALID_ARGUMENT, "DISTINCT needs at least one column");
+  if (q.n_group_by > PG_MAX_GROUP_COLS) fail(PG_ERR_UNSUPPORTED, "DISTINCT over more than %d columns", PG_MAX_GROUP_COLS);
+  if (q.limit <= 0) fail(PG_ERR_UNSUPPORTED, "DISTINCT with LIMIT %d", q.limit);
+  if (q.n_order_by < 0 || (q.n_order_by > 0 && !q.order_by)) fail(PG_ERR_INVALID_ARGUMENT, "order_by is null");
+  DistinctShape S;
+  const int n = q.n_group_by;
+  std::lock_guard<std::mutex> lock(seg.mu);   // virtual dictionaries are built under the segment's lock
+  for (int j = 0; j < n; j++) {
+    const char* name = q.group_by_columns[j];
+    Column* c = name ? seg.find(name) : nullptr;
+    if (!c) {
+      bool identifier = name && *name;
+      for (const char* p = name; identifier && *p; p++) identifier = isalnum((unsigned char)*p) || *p == '_' || *p == '.' || *p == '$';
+      if (!identifier) fail(PG_ERR_UNSUPPORTED, "DISTINCT over the expression %s", name ? name : "(null)");
+      fail(PG_ERR_NOT_FOUND, "column not found: %s", name);
+    }
+    if (c->is_mv || c->raw_mv) fail(PG_ERR_UNSUPPORTED, "DISTINCT over the multi-value column %s", c->name.c_str());
+    if (q.flags & PG_QUERY_FLAG_NULL_HANDLING) {
+      auto it = seg.null_vectors.find(c->name);
+      if (it != seg.null_vectors.end() && it->second && !it->second->posting_card.empty() && it->second->posting_card[0] > 0)
+        fail(PG_ERR_UNSUPPORTED, "enableNullHandling: DISTINCT over %s, which holds nulls", c->name.c_str());
+    }
+    Column* id = c;
+    Column* vd = nullptr;
+    if (!c->has_dictionary) {
+      if (c->col_kind != PG_COL_RAW32 && c->col_kind != PG_COL_RAW64 && c->col_kind != PG_COL_VAR_BYTES)
+        fail(PG_ERR_UNSUPPORTED, "DISTINCT over the column %s (layout %d)", c->name.c_str(), c->col_kind);
+      ensure_virtual_dictionary(seg, *c);   // the typed executors' value identity: all NaNs one value, -0.0 != 0.0
+      id = vd = c->vdict.get();
+    }
+    if (id->cardinality < 1 || id->bits < 1 || id->bits > 31)
+      fail(PG_ERR_UNSUPPORTED, "DISTINCT over %s: %d values in %d bits", c->name.c_str(), id->cardinality, id->bits);
+    S.cols.push_back(id);
+    S.vdicts.push_back(vd);
+  }
+  // digit order: the ORDER BY columns first (most significant, in ORDER BY order), then the others in DISTINCT order
+  std::vector<int> order;
+  S.desc.assign((size_t)n, 0);
+  for (int32_t i = 0; i < q.n_order_by; i++) {
+    const pg_order_by& ob = q.order_by[i];
+    if (ob.kind != PG_ORDER_BY_GROUP_KEY) fail(PG_ERR_INVALID_ARGUMENT, "DISTINCT ordered by an expression of kind %d", ob.kind);
+    if (ob.index < 0 || ob.index >= n) fail(PG_ERR_INVALID_ARGUMENT, "ORDER BY DISTINCT column %d of %d", ob.index, n);
+    const Column* vd = S.vdicts[(size_t)ob.index];
+    if (vd && vd->vdict_kind == 4) fail(PG_ERR_UNSUPPORTED, "DISTINCT ordered by the raw STRING / BYTES column %s", q.group_by_columns[ob.index]);
+    if (std::find(order.begin(), order.end(), ob.index) != order.end()) continue;   // a repeated expression decides nothing more
+    order.push_back(ob.index);
+    S.desc[(size_t)ob.index] = ob.ascending ? 0 : 1;
+  }
+  S.ordered = !order.empty();
+  for (int j = 0; j < n; j++) if (std::find(order.begin(), order.end(), j) == order.end()) order.push_back(j);
+  S.mult.assign((size_t)n, 0);
+  uint64_t K = 1;
+  for (int k = n - 1; k >= 0; k--) {
+    const int j = order[(size_t)k];
+    S.mult[(size_t)j] = K;
+    K *= (uint64_t)S.cols[(size_t)j]->cardinality;
+    if (K > ((uint64_t)1 << 32)) fail(PG_ERR_UNSUPPORTED, "DISTINCT key space over 2^32 (the product of the columns' cardinalities)");
+  }
+  S.key_space = K;
+  S.dict_only = q.filter == nullptr && n == 1 && S.vdicts[0] == nullptr;
+  return S;
 }
 
 }  // namespace pg

@@ -345,7 +345,8 @@ class ResultsBlock:
         n = C.c_int32()
         api.call("result_num_groups", h, C.byref(n))
         ng = n.value
-        ngb = len(qc.group_by)
+        keys = qc.distinct or qc.group_by   # SELECT DISTINCT: the tuples come back as group keys
+        ngb = len(keys)
         ids = np.zeros((ngb, ng), dtype=np.int32)
         rb.group_values = None
         rb.group_value_columns = {}      # group-by column index -> the groups' values (no-dictionary columns)
@@ -368,7 +369,7 @@ class ResultsBlock:
                 api.call("result_group_values_bytes", h, j, offs.ctypes.data, ng + 1, blob.ctypes.data, int(total.value))
                 raw = blob.tobytes()
                 vals = np.empty(ng, dtype=object)
-                is_string = host.columns[qc.group_by[j]].data_type == "STRING"
+                is_string = host.columns[keys[j]].data_type == "STRING"
                 for i in range(ng):
                     v = raw[offs[i]:offs[i + 1]]
                     vals[i] = v.decode("utf-8") if is_string else v
@@ -444,7 +445,14 @@ class ResultsBlock:
 
     @property
     def num_groups(self) -> int:
-        return self.group_dict_ids.shape[1] if self.query.group_by else 1
+        return self.group_dict_ids.shape[1] if (self.query.distinct or self.query.group_by) else 1
+
+    @property
+    def distinct_rows(self) -> List[tuple]:
+        """SELECT DISTINCT: the tuples in result order (sorted under ORDER BY, else by first matching docId), decoded — dictionary values,
+        raw values, strings; a NaN is "NaN" and -0.0 is "-0.0" so that tuples compare as the reference's typed executors do."""
+        assert self.query.distinct, "not a DISTINCT query"
+        return self.group_keys
 
     @property
     def group_keys(self) -> List[tuple]:
@@ -456,7 +464,7 @@ class ResultsBlock:
             vcols = getattr(self, "group_value_columns", {})
             ng = self.num_groups
             per_col = []
-            for j, g in enumerate(self.query.group_by):
+            for j, g in enumerate(self.query.distinct or self.query.group_by):
                 if j in vcols:   # raw values; a NaN key is one group: give it a key that compares equal to itself
                     v = vcols[j]
                     per_col.append(list(v) if v.dtype == object else ([int(x) for x in v] if v.dtype == np.int64 else [float(x) for x in v]))

@@ -100,6 +100,7 @@ class QueryContext:
     flags: int = 0
     has_group_by: bool = False
     min_segment_group_trim_size: int = -1   # InstancePlanMakerImplV2.DEFAULT_MIN_SEGMENT_GROUP_TRIM_SIZE: the segment's groups are not trimmed
+    distinct: List[str] = field(default_factory=list)   # SELECT DISTINCT a, b: the DISTINCT columns (empty: not a DISTINCT query)
 
     def resolved_order_by(self) -> "Optional[List[Tuple[int, int, bool]]]":
         """(kind, index, ascending) per ORDER BY expression as TableResizer resolves them (TableResizer.java:129-161): a group-by expression
@@ -307,6 +308,9 @@ class _Parser:
     def parse(self) -> QueryContext:
         q = QueryContext()
         self.expect_kw("SELECT")
+        is_distinct = self.kw("DISTINCT")
+        if is_distinct:
+            self.i += 1
         self.select_item(q)
         while self.peek() == ("op", ","):
             self.i += 1
@@ -368,6 +372,15 @@ class _Parser:
             q.limit = int(self.literal())
         if self.peek()[0] != "eof":
             raise SqlError(f"trailing tokens: {self.toks[self.i:]}")
+        if is_distinct:
+            # DistinctPlanNode: the select list is the DISTINCT expressions; an ORDER BY expression must be one of them (the broker
+            # rejects anything else) and DISTINCT does not mix with aggregations or GROUP BY
+            if q.aggregations or q.has_group_by:
+                raise SqlError("DISTINCT with aggregations or GROUP BY is not supported")
+            if any(text not in q.select_columns for text, _ in q.order_by):
+                raise SqlError("ORDER BY of a DISTINCT query must name DISTINCT columns")
+            q.distinct = list(q.select_columns)
+            q.flags |= capi.QUERY_FLAG_DISTINCT
         return q
 
 
@@ -396,10 +409,11 @@ class CQuery:
             self.query.filter = C.pointer(root)
         else:
             self.query.filter = None
-        ng = len(q.group_by)
+        keys = q.distinct or q.group_by
+        ng = len(keys)
         self.query.n_group_by = ng
         if ng:
-            arr = (C.c_char_p * ng)(*[g.encode() for g in q.group_by])
+            arr = (C.c_char_p * ng)(*[g.encode() for g in keys])
             self._keep.append(arr)
             self.query.group_by_columns = arr
         na = len(q.aggregations)
@@ -414,9 +428,12 @@ class CQuery:
             self.query.aggregations = aggs
         self.query.num_groups_limit = q.num_groups_limit
         self.query.max_initial_result_holder_capacity = q.max_initial_result_holder_capacity
-        self.query.flags = q.flags
+        self.query.flags = q.flags | (capi.QUERY_FLAG_DISTINCT if q.distinct else 0)
         # segment-level group trim (GroupByOperator.java:120-133): ORDER BY + LIMIT + minSegmentGroupTrimSize travel with group-by queries
-        ob = q.resolved_order_by() if (ng and q.order_by) else None
+        if q.distinct:   # ORDER BY over DISTINCT columns: group-key entries
+            ob = [(capi.ORDER_BY_GROUP_KEY, q.distinct.index(text), asc) for text, asc in q.order_by] or None
+        else:
+            ob = q.resolved_order_by() if (ng and q.order_by) else None
         self.query.limit = q.limit
         self.query.min_segment_group_trim_size = q.min_segment_group_trim_size
         if ob:
