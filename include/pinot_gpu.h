@@ -262,6 +262,32 @@ typedef struct pg_query {
    cardinality 0), limit <= 0, expressions.  Only the filter's plan is cached (the DISTINCT shape is re-derived per call: no kernel plan).  pg_result_merge / pg_result_all_reduce refuse
    distinct results (DistinctCombineOperator merges them by value). */
 #define PG_QUERY_FLAG_DISTINCT 0x80
+/* Selection queries: SELECT cols | * ... [ORDER BY ...] LIMIT n (SelectionPlanNode, pinot-core/.../plan/SelectionPlanNode.java:58-125).
+   group_by_columns / n_group_by are the output expressions in SelectionOperatorUtils#extractExpressions order (the distinct ORDER BY
+   expressions first, then the select list without them; SELECT * is every column not starting with '$', sorted by name), up to 64 plain
+   columns; n_aggregations must be 0; order_by entries are PG_ORDER_BY_GROUP_KEY indexes into that list, at most 8.  `limit` is the
+   operator's _numRowsToKeep: offset + limit under ORDER BY, limit without it (INT32_MAX: unbounded); 0 is EmptySelectionOperator (no rows,
+   statistics (0, 0, 0, totalDocs)).  The rows come back through pg_result_num_groups / _group_key_type / _group_dict_ids /
+   _group_values_* / _group_values_bytes* like group keys: DICT_IDS for dictionary columns (sorted ones included), LONG_VALUES /
+   DOUBLE_VALUES for raw numeric columns (the values at the docId), BYTES_VALUES for raw STRING / BYTES.  Row order: without ORDER BY the
+   first `limit` matching docs in docId order (SelectionOnlyOperator); with ORDER BY the rows sorted by OrderByComparatorFactory's
+   comparator (compareTo on the values: dictionary columns by dictId, FLOAT / DOUBLE by Float.compare / Double.compare, -0.0 < 0.0, every
+   NaN the greatest) — which rows tied at the cut survive is unspecified (a heap in SelectionOrderByOperator), and tied rows come in any order.
+   pg_result_data_table_v4 writes SelectionResultsBlock#getDataTable (typed columns, one row per result row, in result order).
+   ExecutionStatistics — without ORDER BY: numDocsScanned = min(limit, matches), numEntriesScannedPostFilter = numDocsScanned x the distinct
+   output columns, numEntriesScannedInFilter is the filter iterators' count where the operator stopped (after ceil(limit / B) x B next()
+   calls, B = min(limit, 10 000): DocIdSetOperator blocks; the whole filter's count when fewer docs match): exact for no filter, index-only
+   filters and one scan predicate (its whole 256-doc batches), from the reference's iterator automaton run to that point up to
+   PG_EXACT_STATS_MAX_DOCS docs, beyond that the whole filter's count with stats_exact = 0.  With ORDER BY: numDocsScanned = matches,
+   numEntriesScannedPostFilter = matches x the ORDER BY columns + rows x the other distinct output columns, numEntriesScannedInFilter the
+   whole filter's.  Refused (PG_ERR_UNSUPPORTED: the Java plan answers): multi-value columns, expressions, under PG_QUERY_FLAG_NULL_HANDLING
+   an output column holding nulls, ORDER BY whose first column is sorted (SelectionPartiallyOrdered{ByAsc,ByDesc}), ORDER BY over a raw
+   STRING / BYTES column, an ORDER BY key wider than 64 bits (a dictionary column takes its bits per value, raw INT / FLOAT 32, LONG /
+   DOUBLE 64), more than 64 output columns or 8 ORDER BY expressions, and a limit above 1024 (PG_SELECT_LDS_MAX_K) whose sort of every
+   matching doc would exceed PG_SELECT_SORT_MAX_BYTES (default 8 GiB; refused by pg_query_exec, which alone knows the matches).  Only the
+   filter's plan is cached.  pg_result_merge / pg_result_all_reduce refuse selection results (SelectionCombineOperator and the broker merge
+   them by value). */
+#define PG_QUERY_FLAG_SELECTION 0x100
 #define PG_QUERY_FLAG_KEEP_DEVICE_TABLE 0x4 /* keep the dense accumulator table in HBM with the result (pg_result_merge / _all_reduce) */
 
 /* ExecutionStatistics (pinot-core/.../operator/ExecutionStatistics.java) + device timings. */

@@ -17,10 +17,13 @@
  */
 package org.apache.pinot.gpu;
 
+import java.util.List;
+import org.apache.pinot.common.request.context.ExpressionContext;
 import org.apache.pinot.core.plan.PlanNode;
 import org.apache.pinot.core.plan.maker.InstancePlanMakerImplV2;
 import org.apache.pinot.core.query.request.context.QueryContext;
 import org.apache.pinot.core.query.request.context.utils.QueryContextUtils;
+import org.apache.pinot.core.query.selection.SelectionOperatorUtils;
 import org.apache.pinot.segment.spi.ImmutableSegment;
 import org.apache.pinot.segment.spi.IndexSegment;
 import org.apache.pinot.segment.spi.SegmentContext;
@@ -94,6 +97,23 @@ public class GpuInstancePlanMaker extends InstancePlanMakerImplV2 {
     IndexSegment segment = segmentContext.getIndexSegment();
     // (enableNullHandling travels in the query record: three-valued filters, null-skipping aggregations and null group keys are answered by
     // the library — results and keys come back with NULL flags, GpuGroupByOperator#blockOf; it refuses nulls in multi-value columns)
+    // selection queries over plain columns: GpuSelectionOperator over PG_QUERY_FLAG_SELECTION (ORDER BY whose first column is sorted, and
+    // every other refusal, keeps SelectionPlanNode's operators)
+    if (segment instanceof ImmutableSegment && QueryContextUtils.isSelectionQuery(queryContext)) {
+      long handle = _registry.handleFor((ImmutableSegment) segment, segmentContext);
+      if (handle != 0) {
+        List<ExpressionContext> expressions = SelectionOperatorUtils.extractExpressions(queryContext, segment);
+        NativeQuery nativeQuery = NativeQuery.fromSelection(queryContext, expressions);
+        if (nativeQuery != null) {
+          if (PinotGpu.querySupported(handle, nativeQuery.address()) == PinotGpu.PG_OK) {
+            return () -> new GpuSelectionOperator(segment, queryContext, expressions, handle, nativeQuery,
+                () -> super.makeSegmentPlanNode(segmentContext, queryContext).run());
+          }
+          nativeQuery.close();
+        }
+      }
+      return super.makeSegmentPlanNode(segmentContext, queryContext);
+    }
     // SELECT DISTINCT (and the broker's rewrite of a GROUP BY without aggregations into it): GpuDistinctOperator over PG_QUERY_FLAG_DISTINCT
     if (segment instanceof ImmutableSegment && QueryContextUtils.isDistinctQuery(queryContext)) {
       long handle = _registry.handleFor((ImmutableSegment) segment, segmentContext);

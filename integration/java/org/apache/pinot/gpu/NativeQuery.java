@@ -38,6 +38,7 @@ public final class NativeQuery implements AutoCloseable {
 
   private static final int FLAG_KEEP_DEVICE_TABLE = 0x4;   // PG_QUERY_FLAG_KEEP_DEVICE_TABLE
   private static final int FLAG_DISTINCT = 0x80;          // PG_QUERY_FLAG_DISTINCT
+  private static final int FLAG_SELECTION = 0x100;        // PG_QUERY_FLAG_SELECTION
 
   private final long _address;
   private final int _flags;
@@ -140,6 +141,43 @@ public final class NativeQuery implements AutoCloseable {
       return null;
     }
     return new NativeQuery(PinotGpu.queryParse(b, b.position()), FLAG_DISTINCT);
+  }
+
+  /**
+   * Selection (PG_QUERY_FLAG_SELECTION): `expressions` (SelectionOperatorUtils#extractExpressions over the segment) in the group-by slots, no
+   * aggregation, every ORDER BY expression a group-key entry (none under LIMIT 0), LIMIT the operator's _numRowsToKeep (offset + limit under
+   * ORDER BY).  null when an expression is not a plain column (the Java plan answers).
+   */
+  public static NativeQuery fromSelection(QueryContext q, List<ExpressionContext> expressions) {
+    List<OrderByExpressionContext> orderBy = q.getLimit() > 0 ? q.getOrderByExpressions() : null;
+    int numOrderBy = orderBy == null ? 0 : orderBy.size();
+    int size = estimate(q);
+    for (ExpressionContext e : expressions) {
+      size += 8 + 4 * e.toString().length();
+    }
+    ByteBuffer b = ByteBuffer.allocateDirect(size).order(ByteOrder.LITTLE_ENDIAN);
+    b.putInt(MAGIC).putInt(FLAG_SELECTION | (q.isNullHandlingEnabled() ? FLAG_NULL_HANDLING : 0)).putInt(q.getNumGroupsLimit())
+        .putInt(q.getMaxInitialResultHolderCapacity()).putInt(expressions.size()).putInt(0)
+        .putInt(q.getFilter() == null ? 0 : 1).putInt(numOrderBy);
+    b.putInt(orderBy == null ? q.getLimit() : q.getOffset() + q.getLimit()).putInt(-1);   // SelectionOrderByOperator._numRowsToKeep
+    for (ExpressionContext e : expressions) {
+      if (e.getType() != ExpressionContext.Type.IDENTIFIER) {
+        return null;
+      }
+      putString(b, e.getIdentifier());
+    }
+    for (int i = 0; i < numOrderBy; i++) {
+      OrderByExpressionContext o = orderBy.get(i);
+      int index = expressions.indexOf(o.getExpression());
+      if (index < 0) {
+        return null;
+      }
+      b.putInt(0).putInt(index).putInt(o.isAsc() ? 1 : 0).putInt(o.isNullsLast() ? 1 : 0);   // PG_ORDER_BY_GROUP_KEY
+    }
+    if (q.getFilter() != null && !putFilter(b, q.getFilter())) {
+      return null;
+    }
+    return new NativeQuery(PinotGpu.queryParse(b, b.position()), FLAG_SELECTION);
   }
 
   /** {kind, index, ascending, nullsLast} per ORDER BY expression (pg_order_by), or null when the query has none or one the record cannot carry. */

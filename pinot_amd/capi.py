@@ -50,6 +50,7 @@ QUERY_FLAG_EXACT_FILTER_STATS = 0x10
 QUERY_FLAG_FINAL_DISTINCT = 0x20
 QUERY_FLAG_NULL_HANDLING = 0x40
 QUERY_FLAG_DISTINCT = 0x80   # SELECT DISTINCT: group_by_columns are the DISTINCT columns, no aggregation
+QUERY_FLAG_SELECTION = 0x100   # SELECT cols | * ... [ORDER BY] LIMIT n: group_by_columns are the output columns (extractExpressions order)
 LIMIT_UNBOUNDED = 2**31 - 1   # DISTINCT ... LIMIT Integer.MAX_VALUE: every tuple
 COMM_UNIQUE_ID_BYTES = 128
 GROUP_KEY_DICT_IDS, GROUP_KEY_LONG_VALUES, GROUP_KEY_DOUBLE_VALUES, GROUP_KEY_BYTES_VALUES = 0, 1, 2, 3

@@ -39,6 +39,7 @@ static void knobs_read(Knobs& k) {
   k.wave_specialised_min_permille = (int)num("PG_WAVE_SPECIALISED_MIN_PERMILLE", 150);
   k.exact_stats_max_docs = num("PG_EXACT_STATS_MAX_DOCS", (int64_t)1 << 22);
   k.filter_stats_host = flag("PG_FILTER_STATS_HOST"); k.exact_stats_device_max_docs = num("PG_EXACT_STATS_DEVICE_MAX_DOCS", (int64_t)1 << 27);
+  k.select_sort_max_bytes = num("PG_SELECT_SORT_MAX_BYTES", (int64_t)8 << 30);
   k.limit_prefix_min_docs = std::max<int64_t>(PG_WAVE_DOCS, num("PG_LIMIT_PREFIX_MIN_DOCS", (int64_t)1 << 20));
   k.oct_passes = str("PG_OCT_PASSES"); k.rccl_library = str("PG_RCCL_LIBRARY");
 }
@@ -253,6 +254,11 @@ int32_t pg_query_supported(pg_segment_t segment, const pg_query* query) {
     use_device(segment->seg.device);
     // compiled under the segment's lock and cached: the pg_query_exec that follows finds the plan (PlanMaker calls supported()
     // then exec() from many worker threads); throws PG_ERR_UNSUPPORTED for shapes off the GPU path
+    if (query->flags & PG_QUERY_FLAG_SELECTION) {   // the checks of the selection path; its filter plan is compiled and cached
+      (void)selection_shape(segment->seg, *query);
+      (void)get_plan(segment->seg, query->filter, nullptr, query->flags & PG_QUERY_FLAG_NULL_HANDLING);
+      return;
+    }
     if (query->flags & PG_QUERY_FLAG_DISTINCT) {   // the checks of the DISTINCT path; its filter plan is compiled and cached
       (void)distinct_shape(segment->seg, *query);
       (void)get_plan(segment->seg, query->filter, nullptr, query->flags & PG_QUERY_FLAG_NULL_HANDLING);
@@ -299,6 +305,7 @@ int32_t pg_result_merge(pg_result_t dst, pg_result_t src) {
   return guarded([&] {
     REQUIRE(dst && src && dst != src, "null or identical results");
     if (dst->r->distinct || src->r->distinct) fail(PG_ERR_UNSUPPORTED, "distinct results are merged by value (DistinctCombineOperator)");
+    if (dst->r->selection || src->r->selection) fail(PG_ERR_UNSUPPORTED, "selection results are merged by value (SelectionCombineOperator)");
     result_merge(*dst->r, *src->r);
   });
 }
@@ -306,6 +313,7 @@ int32_t pg_result_all_reduce(pg_result_t result, pg_comm_t comm) {
   return guarded([&] {
     REQUIRE(result && comm && comm->c, "null argument");
     if (result->r->distinct) fail(PG_ERR_UNSUPPORTED, "distinct results are merged by value (DistinctCombineOperator)");
+    if (result->r->selection) fail(PG_ERR_UNSUPPORTED, "selection results are merged by value (SelectionCombineOperator)");
     result_all_reduce(*result->r, *comm->c);
   });
 }

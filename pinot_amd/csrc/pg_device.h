@@ -465,6 +465,40 @@ struct PgDistinctArgs {
   uint32_t* first_doc;         // first-doc pass: per new key (by rank) its smallest matching docId
 };
 
+// Selection queries (pg_kernels_select.hip): the ORDER BY columns of a doc folded into one 64-bit order-space key (the K smallest keys are
+// the top K rows), then the output columns gathered at the rows' docIds.
+#define PG_SELECT_LDS_MAX_K 1024   // the streaming top-K keeps up to this many rows per wavefront in LDS; beyond it the matches are sorted
+#define PG_SELECT_MAX_KEY_COLS 8       // ORDER BY expressions of a selection
+#define PG_SELECT_MAX_OUT_COLS 64      // output columns of a selection (SELECT * over a wide table)
+enum PgSelectKeyKind : int32_t { PG_SK_DICT = 0, PG_SK_I32 = 1, PG_SK_I64 = 2, PG_SK_F32 = 3, PG_SK_F64 = 4 };
+struct PgSelectKeyCol {
+  const uint8_t* data;   // fixed-bit dictIds (MSB-first big-endian bit stream), or big-endian raw values (4 / 8 bytes per doc)
+  int32_t kind;          // PgSelectKeyKind
+  int32_t bits;          // width of the field in the key (dictIds: bits per value; raw: 32 / 64)
+  int32_t shift;         // position of the field's lowest bit in the key
+  int32_t desc;          // DESC: dictIds card - 1 - id, raw fields complemented
+  int32_t card;          // dictIds: the cardinality
+  int32_t pad;
+};
+struct PgSelectKeyArgs {
+  const uint64_t* match;        // the filter's match words (null: every doc 0 .. n_docs-1 is a candidate)
+  int64_t n_docs;
+  int32_t n_cols;
+  int32_t k;                    // rows to keep (top-K tier)
+  PgSelectKeyCol cols[PG_SELECT_MAX_KEY_COLS];
+  unsigned long long* threshold;   // top-K tier: the published K-th key (starts at ~0)
+  unsigned long long* out_keys;    // (key, docId) pairs of the survivors (top-K tier) or of every matching doc (sort tier)
+  uint32_t* out_docs;
+  uint32_t* out_count;          // pairs written
+};
+enum PgSelectOutKind : int32_t { PG_SO_DICT = 0, PG_SO_I32 = 1, PG_SO_I64 = 2, PG_SO_F32 = 3, PG_SO_F64 = 4, PG_SO_BYTES = 5 };
+struct PgSelectOutCol {
+  const uint8_t* data;          // fixed-bit dictIds, big-endian raw values, or var-byte values back to back
+  const int64_t* vb_offsets;    // PG_SO_BYTES: numDocs + 1 offsets
+  int32_t kind;                 // PgSelectOutKind
+  int32_t bits;                 // PG_SO_DICT
+};
+
 struct PgTrimArgs {
   const int64_t* table;     // [n_ops][G]
   int64_t G;

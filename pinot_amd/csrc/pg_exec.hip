@@ -48,6 +48,7 @@ extern "C" int pg_specw_stage_bytes(int scan_bits, int value_bits, int bits0, in
 extern "C" int pg_specw_list_bytes();
 PG_DECL_FAST(pg_fast_multi_wd) PG_DECL_FAST(pg_fast_none_wd) PG_DECL_FAST(pg_generic_query_ld) PG_DECL_FAST(pg_generic_query_gd)
 extern "C" __global__ void pg_distinct_keys_lds(const PgDistinctArgs a);   // pg_kernels_distinct.hip: up to 128 KiB of dynamic LDS
+extern "C" void pg_select_lds_opt_in();   // pg_kernels_select.hip: its top-K kernels take up to 96 KiB of dynamic LDS
 extern "C" __global__ void pg_reduce_partials_kernel(const int64_t* partials, int64_t* out, int n_wg, int n_ops,
                                                      int n_groups, const PgAccOp* ops, unsigned long long* stats, int reduce);
 extern "C" __global__ void pg_reduce_parts_kernel(const int64_t* partials, int64_t* out, int n_wg, int n_ops, int n_groups,
@@ -344,6 +345,7 @@ void use_device(int ordinal) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 12288);
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pg_radix_scatter_packed_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 8192);
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pg_distinct_keys_lds), hipFuncAttributeMaxDynamicSharedMemorySize, PG_DISTINCT_LDS_MAX_KEYS / 8);
+      pg_select_lds_opt_in();
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pg_radix_aggregate_packed_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 8192);
       (void)hipGetLastError();   // a refused attribute must not surface as the "last error" of a later launch
       di.ready.store(1, std::memory_order_release);
@@ -489,6 +491,14 @@ extern "C" void pg_distinct_launch_expand(const uint32_t* bm, int64_t n_chunks, 
 extern "C" void pg_distinct_launch_mark(const uint32_t* first_doc, int64_t n, uint32_t* doc_bits, int grid, hipStream_t stream);
 extern "C" void pg_distinct_launch_fold(uint32_t* seen, uint32_t* fresh, const uint32_t* counts, int64_t n_chunks, hipStream_t stream);
 extern "C" void pg_distinct_launch_decode(const PgDistinctArgs* args, const uint32_t* pos, int64_t n, int from_docs, int32_t* out, int grid, hipStream_t stream);
+extern "C" size_t pg_select_topk_lds_bytes(int n_slots);   // pg_kernels_select.hip
+extern "C" void pg_select_launch_topk(const PgSelectKeyArgs* args, int n_slots, int grid, hipStream_t stream);
+extern "C" void pg_select_launch_keys(const PgSelectKeyArgs* args, const int64_t* tile_offsets, int n_tiles, int grid, hipStream_t stream);
+extern "C" void pg_select_launch_gather(const PgSelectOutCol* cols_dev, int n_cols, const uint32_t* docs, int64_t n, int64_t* out, int grid, hipStream_t stream);
+extern "C" void pg_select_launch_gather_bytes(const PgSelectOutCol* col, const uint32_t* docs, int64_t n, const int64_t* off, uint8_t* out, int grid,
+                                              hipStream_t stream);
+extern "C" hipError_t pg_select_sort_pairs(void* tmp, size_t* tmp_bytes, const unsigned long long* keys_in, unsigned long long* keys_out,
+                                           const uint32_t* docs_in, uint32_t* docs_out, size_t n, int end_bit, hipStream_t stream);
 extern "C" void pg_trim_launch_keys(const PgTrimArgs* args, int grid, hipStream_t stream);
 extern "C" void pg_trim_launch_select(const PgTrimArgs* args, int grid, hipStream_t stream);
 typedef void (*QueryKernel)(const PgQueryPlan);
@@ -614,6 +624,7 @@ struct ThreadCtx {
   DeviceBuffer fs_leaves, fs_arena;   // exact numEntriesScannedInFilter on the device: the leaves' match bitmaps, scratch (pg_filter_stats.cpp)
   DeviceBuffer trim_keys, trim_ctrl, trim_out;   // segment-level group trim on the device: [G] keys, counters, the compact block
   DeviceBuffer dist_seen, dist_fresh, dist_docs, dist_counts, dist_off, dist_rank, dist_first, dist_pos, dist_ids;   // SELECT DISTINCT (execute_distinct)
+  DeviceBuffer sel_ctrl, sel_keys, sel_docs, sel_keys2, sel_docs2, sel_tmp, sel_cols, sel_vals, sel_off, sel_bytes;   // selections (execute_selection)
   size_t aux_clean_bytes = 0;    // the first bytes of `aux` are zero (pg_finish_fused_kernel re-zeroes the states it folds): the next query's fill is skipped
   const void* aux_clean_ptr = nullptr;
   DeviceBuffer hll_small[17];  // per log2m: round(m * ln(m / zeros)), zeros = 0 .. m
@@ -796,18 +807,23 @@ static bool exact_stats_by_default(const CompiledPlan& P) {
   return (int64_t)P.space_docs <= knobs().exact_stats_max_docs || ((int64_t)P.space_docs <= knobs().exact_stats_device_max_docs && stats_counted_on_device(P));
 }
 
-static int64_t exact_entries_scanned(CompiledPlan& P, ThreadCtx& ctx, const CancelToken* cancel, int32_t* path_out = nullptr) {
+// `leaves`: the leaf plans to run (default: the plan's own); max_next >= 0: the count where a consumer stopped after that many next() calls
+// (a selection's early stop: counted by the host walk)
+using StatLeafPlans = std::vector<std::pair<const FilterOp*, std::shared_ptr<CompiledPlan>>>;
+static int64_t exact_entries_scanned(CompiledPlan& P, ThreadCtx& ctx, const CancelToken* cancel, int32_t* path_out = nullptr,
+                                     const StatLeafPlans* leaves = nullptr, int64_t max_next = -1) {
   StatLeafBits bits;
   const int32_t n_docs = P.space_docs;
-  const bool on_device = stats_counted_on_device(P);
+  const StatLeafPlans& stat_leaves = leaves ? *leaves : P.stat_leaves;
+  const bool on_device = max_next < 0 && stats_counted_on_device(P);
   StatLeafWords dev_bits;
   size_t slot_words = 0;
   if (on_device) {
-    for (auto& lf : P.stat_leaves) slot_words = std::max(slot_words, (size_t)std::max(lf.second->dev.n_tiles, 1) * PG_TILE_WORDS);
-    ThreadCtx::grow(ctx.fs_leaves, std::max<size_t>(P.stat_leaves.size(), 1) * slot_words * 8);
+    for (auto& lf : stat_leaves) slot_words = std::max(slot_words, (size_t)std::max(lf.second->dev.n_tiles, 1) * PG_TILE_WORDS);
+    ThreadCtx::grow(ctx.fs_leaves, std::max<size_t>(stat_leaves.size(), 1) * slot_words * 8);
   }
   size_t slot = 0;
-  for (auto& lf : P.stat_leaves) {
+  for (auto& lf : stat_leaves) {
     if (cancel && cancel->requested.load(std::memory_order_acquire)) fail(PG_ERR_CANCELLED, "query cancelled (EarlyTerminationException)");
     CompiledPlan& L = *lf.second;
     PgQueryPlan D = L.dev;
@@ -837,7 +853,7 @@ static int64_t exact_entries_scanned(CompiledPlan& P, ThreadCtx& ctx, const Canc
     return n;
   }
   if (path_out) *path_out = 1;
-  return emulate_entries_scanned_in_filter(*P.root_op, bits, n_docs);
+  return emulate_entries_scanned_in_filter(*P.root_op, bits, n_docs, max_next);
 }
 
 // ---- result assembly: dense accumulator table (+ statistics, + DISTINCTCOUNT / HLL regions) -> groups and intermediates --------
@@ -1585,6 +1601,297 @@ std::unique_ptr<Result> execute_distinct(Segment& seg, const pg_query& q, const 
       if (b->size > ((size_t)64 << 20)) b->release();
   }
   distinct_assemble(*res, S, ids, n_rows);
+  fill_result_schema(seg, q, *res);
+  st.host_ms_plan = (float)(t_plan - t0);
+  st.host_ms_total = (float)(now_ms() - t0);
+  return res;
+}
+
+// ---- selection queries (PG_QUERY_FLAG_SELECTION) -----------------------------------------------------------------------------------------------
+// EmptySelectionOperator (LIMIT 0); SelectionOnlyOperator (core/operator/query/SelectionOnlyOperator.java:115-171): the first `limit` matching
+// docs in docId order, pulled in DocIdSetOperator blocks of min(limit, 10 000) docs (DocIdSetOperator.java:59-86), the filter iterator not
+// drained; SelectionOrderByOperator (:111,146-368): the `limit` best rows of every matching doc under OrderByComparatorFactory's comparator
+// (query/utils/OrderByComparatorFactory.java:87-99), the ORDER BY columns read for every match, the others for the kept rows only.  The
+// kernels are those of pg_kernels_select.hip.
+namespace {
+// numEntriesScannedInFilter of a filter whose iterator the operator stopped after `n_next` next() calls (n_next < the matches)
+void selection_early_filter_stats(Segment& seg, const pg_query& q, DocIdSet& ds, int64_t n_next, ThreadCtx& ctx, const CancelToken* cancel,
+                                  pg_exec_stats& st) {
+  const bool lone_predicate = q.filter && q.filter->type == PG_FILTER_PREDICATE && !seg.queryable_doc_ids;
+  if (ds.stats.stats_exact && ds.stats.num_entries_scanned_in_filter == 0) {   // no filter, index-only filters: nothing is scanned
+    st.num_entries_scanned_in_filter = 0;
+  } else if (lone_predicate && ds.stats.stats_exact && ds.stats.num_entries_scanned_in_filter == seg.total_docs) {
+    // one single-value scan: whole 256-doc batches (SVScanDocIdIterator.java:76-98) up to the batch of the last doc consumed
+    const int64_t last = kth_match(ds, n_next, ctx);
+    st.num_entries_scanned_in_filter = std::min<int64_t>(seg.total_docs, (last / kScanBatchDocs + 1) * kScanBatchDocs);
+  } else if ((int64_t)seg.total_docs <= knobs().exact_stats_max_docs) {
+    // the reference's iterator automaton over the leaves' match bitmaps, stopped after the n_next-th doc (pg_filter_stats.cpp)
+    auto plan = get_plan(seg, q.filter, nullptr, q.flags & PG_QUERY_FLAG_NULL_HANDLING);
+    const StatLeafPlans leaves = stat_leaf_plans(seg, *plan);
+    st.num_entries_scanned_in_filter = exact_entries_scanned(*plan, ctx, cancel, &st.filter_stats_path, &leaves, n_next);
+    st.stats_exact = 1;
+  } else {
+    st.stats_exact = 0;   // the whole filter's count stands in
+  }
+}
+
+int64_t pow2_at_least(int64_t v) {
+  int64_t p = 1;
+  while (p < v) p <<= 1;
+  return p;
+}
+}  // namespace
+
+std::unique_ptr<Result> execute_selection(Segment& seg, const pg_query& q, const CancelToken* cancel) {
+  AdmissionGuard admitted(seg.device, knobs().max_inflight);
+  const double t0 = now_ms();
+  check_cancel(cancel, nullptr);
+  ThreadCtx& ctx = ctx_on(seg.device);
+  const SelectionShape S = selection_shape(seg, q);
+  const double t_plan = now_ms();
+  const int n_cols = q.n_group_by;
+  const int64_t limit = q.limit;
+  auto res = std::make_unique<Result>();
+  res->selection = true;
+  pg_exec_stats& st = res->stats;
+  st.num_total_docs = seg.total_docs;
+  st.star_tree_index = -1;
+  st.stats_exact = 1;
+  const bool ordered = !S.order.empty();
+  const bool filtered = q.filter || seg.queryable_doc_ids;   // an upsert snapshot is a filter of its own (FilterPlanNode.java:88-106)
+  int64_t n_rows = 0;
+  int64_t algorithmic = 0;
+  const char* kernel = "pg_select_empty";
+  PG_HIP(hipEventRecord(ctx.ev[0], ctx.stream));
+  std::unique_ptr<DocIdSet> ds;
+  if (limit > 0 && filtered) {   // (no filter: every doc is a candidate, no filter pass)
+    ds = execute_filter(seg, q.filter, q.flags & PG_QUERY_FLAG_NULL_HANDLING);
+    check_cancel(cancel, &ctx);
+    algorithmic += get_plan(seg, q.filter, nullptr, q.flags & PG_QUERY_FLAG_NULL_HANDLING)->algorithmic_bytes;
+    st.num_entries_scanned_in_filter = ds->stats.num_entries_scanned_in_filter;
+    st.stats_exact = ds->stats.stats_exact;
+    st.filter_stats_path = ds->stats.filter_stats_path;
+    st.device_ms_filter = ds->stats.device_ms_filter;
+    PG_HIP(hipEventRecord(ctx.ev[0], ctx.stream));
+  }
+  const int64_t M = ds ? ds->cardinality : seg.total_docs;   // matching docs
+  const uint32_t* rows_dev = nullptr;                         // the result rows' docIds on the device, in result order
+  if (limit > 0 && !ordered) {
+    n_rows = std::min(limit, M);
+    kernel = "pg_select_gather";
+    if (n_rows > 0 && !ds) {   // no filter: docs 0 .. n_rows - 1, no kernel over the segment
+      std::vector<uint32_t> iota((size_t)n_rows);
+      for (int64_t i = 0; i < n_rows; i++) iota[(size_t)i] = (uint32_t)i;
+      ThreadCtx::grow(ctx.sel_docs, (size_t)n_rows * 4);
+      PG_HIP(hipMemcpyAsync(ctx.sel_docs.ptr, iota.data(), (size_t)n_rows * 4, hipMemcpyHostToDevice, ctx.stream));
+      PG_HIP(hipStreamSynchronize(ctx.stream));   // (the pageable source goes out of scope)
+      rows_dev = ctx.sel_docs.as<uint32_t>();
+    } else if (n_rows > 0) {   // the first n_rows matches: the tiles that hold them, expanded
+      int64_t last = 0, acc = 0;
+      std::vector<int64_t> offs(1, 0);
+      while (acc + ds->tile_counts[(size_t)last] < n_rows) { acc += ds->tile_counts[(size_t)last++]; offs.push_back(acc); }
+      offs.push_back(acc + ds->tile_counts[(size_t)last]);
+      ThreadCtx::grow(ctx.sel_off, offs.size() * 8);
+      PG_HIP(hipMemcpyAsync(ctx.sel_off.ptr, offs.data(), offs.size() * 8, hipMemcpyHostToDevice, ctx.stream));
+      ThreadCtx::grow(ctx.sel_docs, (size_t)offs.back() * 4);
+      hipLaunchKernelGGL(pg_expand_docids_kernel, dim3((unsigned)std::min<int64_t>(last + 1, num_cus() * 8)), dim3(PG_TILE_WORDS), 0, ctx.stream,
+                         ds->words.as<uint64_t>(), ctx.sel_off.as<int64_t>(), ctx.sel_docs.as<int32_t>(), (int)(last + 1));
+      PG_HIP(hipGetLastError());
+      PG_HIP(hipStreamSynchronize(ctx.stream));   // (the pageable offsets go out of scope)
+      rows_dev = ctx.sel_docs.as<uint32_t>();
+    }
+    st.num_docs_scanned = n_rows;
+    st.num_entries_scanned_post_filter = n_rows * S.n_distinct;
+    // the operator pulls blocks of min(limit, 10 000) docs until it holds `limit` rows: its iterator stopped after the last block's docs
+    const int64_t block = std::min<int64_t>(limit, kDistinctBlockDocs);
+    const int64_t n_next = (limit + block - 1) / block * block;
+    if (ds && M >= n_next) selection_early_filter_stats(seg, q, *ds, n_next, ctx, cancel, st);
+  } else if (limit > 0) {
+    // the order-space key: the ORDER BY columns' fields, most significant first, in the key's low key_bits bits
+    PgSelectKeyArgs A;
+    memset(&A, 0, sizeof(A));
+    A.match = ds ? ds->words.as<uint64_t>() : nullptr;
+    A.n_docs = seg.total_docs;
+    A.n_cols = (int32_t)S.order.size();
+    int shift = S.key_bits;
+    int64_t key_bytes_per_doc_x8 = 0;
+    for (size_t i = 0; i < S.order.size(); i++) {
+      const Column* c = S.cols[(size_t)S.order[i].first];
+      PgSelectKeyCol& k = A.cols[i];
+      k.data = c->fwd_dev.as<uint8_t>();
+      k.desc = S.order[i].second ? 0 : 1;
+      if (c->has_dictionary) {
+        k.kind = PG_SK_DICT;
+        k.bits = c->bits;
+        k.card = c->cardinality;
+      } else {
+        const bool wide = c->col_kind == PG_COL_RAW64;
+        const bool fp = c->data_type == PG_TYPE_FLOAT || c->data_type == PG_TYPE_DOUBLE;
+        k.kind = fp ? (wide ? PG_SK_F64 : PG_SK_F32) : (wide ? PG_SK_I64 : PG_SK_I32);
+        k.bits = wide ? 64 : 32;
+      }
+      shift -= k.bits;
+      k.shift = shift;
+      key_bytes_per_doc_x8 += k.bits;
+    }
+    const int64_t K = std::min(limit, M);
+    n_rows = K;
+    ThreadCtx::grow(ctx.sel_ctrl, 16);
+    PG_HIP(hipMemsetAsync(ctx.sel_ctrl.ptr, 0xFF, 8, ctx.stream));   // threshold: ~0
+    PG_HIP(hipMemsetAsync(ctx.sel_ctrl.as<uint8_t>() + 8, 0, 8, ctx.stream));
+    A.threshold = ctx.sel_ctrl.as<unsigned long long>();
+    A.out_count = reinterpret_cast<uint32_t*>(ctx.sel_ctrl.as<uint8_t>() + 8);
+    A.k = (int32_t)std::max<int64_t>(K, 1);
+    const int64_t n_words = ((int64_t)seg.total_docs + 63) / 64;
+    uint64_t n_pairs = 0;
+    if (K > 0 && K <= PG_SELECT_LDS_MAX_K) {
+      kernel = "pg_select_topk_lds";
+      const int n_slots = (int)(2 * std::max<int64_t>(64, pow2_at_least(K)));
+      const size_t lds = pg_select_topk_lds_bytes(n_slots);
+      const int wgs_per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, lds_per_cu() / (lds + 1024)));
+      const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)num_cus() * wgs_per_cu, (n_words + 15) / 16));
+      const size_t cap = (size_t)grid * 4 * (size_t)K;   // each wavefront writes at most K survivors
+      ThreadCtx::grow(ctx.sel_keys, cap * 8);
+      ThreadCtx::grow(ctx.sel_docs, cap * 4);
+      A.out_keys = ctx.sel_keys.as<unsigned long long>();
+      A.out_docs = ctx.sel_docs.as<uint32_t>();
+      pg_select_launch_topk(&A, n_slots, grid, ctx.stream);
+      PG_HIP(hipGetLastError());
+      uint32_t cnt = 0;
+      PG_HIP(hipMemcpyAsync(&cnt, A.out_count, 4, hipMemcpyDeviceToHost, ctx.stream));
+      stream_wait(ctx, cancel);
+      if ((int64_t)cnt < K || cnt > cap) fail(PG_ERR_INTERNAL, "selection top-K: %u survivors for %lld rows", cnt, (long long)K);
+      n_pairs = cnt;
+    } else if (K > 0) {
+      kernel = "pg_select_sort";
+      size_t tmp_bytes = 0;
+      PG_HIP(pg_select_sort_pairs(nullptr, &tmp_bytes, nullptr, nullptr, nullptr, nullptr, (size_t)M, std::max(S.key_bits, 1), ctx.stream));
+      const uint64_t need = (uint64_t)M * 24 + tmp_bytes;
+      if ((int64_t)need > knobs().select_sort_max_bytes)
+        fail(PG_ERR_UNSUPPORTED, "selection of %lld rows sorts %lld matches: %llu bytes of work area over PG_SELECT_SORT_MAX_BYTES (%lld)", (long long)K,
+             (long long)M, (unsigned long long)need, (long long)knobs().select_sort_max_bytes);
+      ThreadCtx::grow(ctx.sel_keys, (size_t)M * 8);
+      ThreadCtx::grow(ctx.sel_docs, (size_t)M * 4);
+      A.out_keys = ctx.sel_keys.as<unsigned long long>();
+      A.out_docs = ctx.sel_docs.as<uint32_t>();
+      // the pairs' offsets: the exclusive prefix of the tiles' match counts (every doc of a tile without a filter)
+      const int n_tiles = (int)((seg.total_docs + PG_TILE_DOCS - 1) / PG_TILE_DOCS);
+      std::vector<int64_t> offs((size_t)n_tiles + 1, 0);
+      for (int t = 0; t < n_tiles; t++)
+        offs[(size_t)t + 1] = offs[(size_t)t] + (ds ? (int64_t)ds->tile_counts[(size_t)t] : std::min<int64_t>(PG_TILE_DOCS, (int64_t)seg.total_docs - (int64_t)t * PG_TILE_DOCS));
+      if (offs.back() != M) fail(PG_ERR_INTERNAL, "selection sort tier: %lld matches in the tiles for %lld", (long long)offs.back(), (long long)M);
+      ThreadCtx::grow(ctx.sel_off, offs.size() * 8);
+      PG_HIP(hipMemcpyAsync(ctx.sel_off.ptr, offs.data(), offs.size() * 8, hipMemcpyHostToDevice, ctx.stream));
+      pg_select_launch_keys(&A, ctx.sel_off.as<int64_t>(), n_tiles, (int)std::min<int64_t>(n_tiles, (int64_t)num_cus() * 8), ctx.stream);
+      PG_HIP(hipStreamSynchronize(ctx.stream));   // (the pageable offsets go out of scope)
+      PG_HIP(hipGetLastError());
+      n_pairs = (uint64_t)M;
+    }
+    if (n_pairs > 0) {   // the pairs in key order: the first K are the rows
+      ThreadCtx::grow(ctx.sel_keys2, (size_t)n_pairs * 8);
+      ThreadCtx::grow(ctx.sel_docs2, (size_t)n_pairs * 4);
+      size_t tmp_bytes = 0;
+      PG_HIP(pg_select_sort_pairs(nullptr, &tmp_bytes, ctx.sel_keys.as<unsigned long long>(), ctx.sel_keys2.as<unsigned long long>(), ctx.sel_docs.as<uint32_t>(),
+                                  ctx.sel_docs2.as<uint32_t>(), (size_t)n_pairs, std::max(S.key_bits, 1), ctx.stream));
+      ThreadCtx::grow(ctx.sel_tmp, std::max<size_t>(tmp_bytes, 16));
+      PG_HIP(pg_select_sort_pairs(ctx.sel_tmp.ptr, &tmp_bytes, ctx.sel_keys.as<unsigned long long>(), ctx.sel_keys2.as<unsigned long long>(),
+                                  ctx.sel_docs.as<uint32_t>(), ctx.sel_docs2.as<uint32_t>(), (size_t)n_pairs, std::max(S.key_bits, 1), ctx.stream));
+      rows_dev = ctx.sel_docs2.as<uint32_t>();
+    }
+    check_cancel(cancel, &ctx);
+    // numEntriesScannedPostFilter: the ORDER BY columns of every match, the other (distinct) output columns of the kept rows, fetched by docId
+    int n_other = 0;
+    for (int j = 0; j < n_cols; j++) {
+      bool skip = false;
+      for (int i = 0; i < j; i++) skip = skip || S.cols[(size_t)i] == S.cols[(size_t)j];
+      for (const auto& o : S.order) skip = skip || S.cols[(size_t)o.first] == S.cols[(size_t)j];
+      n_other += skip ? 0 : 1;
+    }
+    st.num_docs_scanned = M;
+    st.num_entries_scanned_post_filter = M * (int64_t)S.order.size() + n_rows * n_other;
+    algorithmic += (M * key_bytes_per_doc_x8 + 7) / 8;
+  }
+  // the output columns at the rows' docIds
+  std::vector<std::vector<int64_t>> vals((size_t)n_cols);
+  std::vector<std::vector<int64_t>> boffs((size_t)n_cols);
+  std::vector<std::vector<uint8_t>> bytes((size_t)n_cols);
+  if (n_rows > 0) {
+    std::vector<PgSelectOutCol> oc((size_t)n_cols);
+    for (int j = 0; j < n_cols; j++) {
+      const Column* c = S.cols[(size_t)j];
+      PgSelectOutCol& o = oc[(size_t)j];
+      memset(&o, 0, sizeof(o));
+      o.data = c->fwd_dev.as<uint8_t>();
+      if (c->has_dictionary) { o.kind = PG_SO_DICT; o.bits = c->bits; algorithmic += (n_rows * c->bits + 7) / 8; }
+      else if (c->col_kind == PG_COL_VAR_BYTES) { o.kind = PG_SO_BYTES; o.vb_offsets = c->vb_offsets_dev.as<int64_t>(); }
+      else {
+        const bool wide = c->col_kind == PG_COL_RAW64;
+        const bool fp = c->data_type == PG_TYPE_FLOAT || c->data_type == PG_TYPE_DOUBLE;
+        o.kind = fp ? (wide ? PG_SO_F64 : PG_SO_F32) : (wide ? PG_SO_I64 : PG_SO_I32);
+        algorithmic += n_rows * (wide ? 8 : 4);
+      }
+    }
+    ThreadCtx::grow(ctx.sel_cols, oc.size() * sizeof(PgSelectOutCol));
+    PG_HIP(hipMemcpyAsync(ctx.sel_cols.ptr, oc.data(), oc.size() * sizeof(PgSelectOutCol), hipMemcpyHostToDevice, ctx.stream));
+    ThreadCtx::grow(ctx.sel_vals, (size_t)n_rows * (size_t)n_cols * 8);
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((n_rows + 255) / 256, (int64_t)num_cus() * 4));
+    pg_select_launch_gather(ctx.sel_cols.as<PgSelectOutCol>(), n_cols, rows_dev, n_rows, ctx.sel_vals.as<int64_t>(), grid, ctx.stream);
+    PG_HIP(hipGetLastError());
+    std::vector<int64_t> flat((size_t)n_rows * (size_t)n_cols);
+    PG_HIP(hipMemcpyAsync(flat.data(), ctx.sel_vals.ptr, flat.size() * 8, hipMemcpyDeviceToHost, ctx.stream));
+    stream_wait(ctx, cancel);
+    for (int j = 0; j < n_cols; j++) vals[(size_t)j].assign(flat.begin() + (int64_t)j * n_rows, flat.begin() + (int64_t)(j + 1) * n_rows);
+    // var-byte columns: lengths -> offsets on the host, then the values copied on the device
+    for (int j = 0; j < n_cols; j++) {
+      if (oc[(size_t)j].kind != PG_SO_BYTES) continue;
+      std::vector<int64_t>& off = boffs[(size_t)j];
+      off.assign((size_t)n_rows + 1, 0);
+      for (int64_t i = 0; i < n_rows; i++) off[(size_t)i + 1] = off[(size_t)i] + vals[(size_t)j][(size_t)i];
+      const int64_t total = off.back();
+      algorithmic += total + n_rows * 16;
+      bytes[(size_t)j].resize((size_t)total);
+      if (total == 0) continue;
+      ThreadCtx::grow(ctx.sel_off, off.size() * 8);
+      ThreadCtx::grow(ctx.sel_bytes, (size_t)total);
+      PG_HIP(hipMemcpyAsync(ctx.sel_off.ptr, off.data(), off.size() * 8, hipMemcpyHostToDevice, ctx.stream));
+      pg_select_launch_gather_bytes(&oc[(size_t)j], rows_dev, n_rows, ctx.sel_off.as<int64_t>(), ctx.sel_bytes.as<uint8_t>(), grid, ctx.stream);
+      PG_HIP(hipGetLastError());
+      PG_HIP(hipMemcpyAsync(bytes[(size_t)j].data(), ctx.sel_bytes.ptr, (size_t)total, hipMemcpyDeviceToHost, ctx.stream));
+      stream_wait(ctx, cancel);
+    }
+  }
+  PG_HIP(hipEventRecord(ctx.ev[1], ctx.stream));
+  stream_wait(ctx, cancel);
+  float ms = 0;
+  PG_HIP(hipEventElapsedTime(&ms, ctx.ev[0], ctx.ev[1]));
+  st.device_ms_aggregate = ms;
+  st.device_ms_total = st.device_ms_filter + ms;
+  st.algorithmic_bytes = algorithmic;
+  snprintf(st.kernel, sizeof(st.kernel), "%s", kernel);
+  // the rows as group keys: dictIds, values, or bytes
+  res->num_groups = (int32_t)n_rows;
+  res->group_key_type.assign((size_t)n_cols, PG_GROUP_KEY_DICT_IDS);
+  res->group_values.assign((size_t)n_cols, {});
+  res->group_bytes.assign((size_t)n_cols, {});
+  res->group_bytes_off.assign((size_t)n_cols, {});
+  res->group_dict_ids.assign((size_t)n_cols, {});
+  for (int j = 0; j < n_cols; j++) {
+    const Column* c = S.cols[(size_t)j];
+    if (c->has_dictionary) {
+      res->group_dict_ids[(size_t)j].assign(vals[(size_t)j].begin(), vals[(size_t)j].end());
+    } else if (c->col_kind == PG_COL_VAR_BYTES) {
+      res->group_key_type[(size_t)j] = PG_GROUP_KEY_BYTES_VALUES;
+      res->group_bytes[(size_t)j] = std::move(bytes[(size_t)j]);
+      res->group_bytes_off[(size_t)j] = n_rows > 0 ? std::move(boffs[(size_t)j]) : std::vector<int64_t>(1, 0);
+    } else {
+      const bool fp = c->data_type == PG_TYPE_FLOAT || c->data_type == PG_TYPE_DOUBLE;
+      res->group_key_type[(size_t)j] = fp ? PG_GROUP_KEY_DOUBLE_VALUES : PG_GROUP_KEY_LONG_VALUES;
+      res->group_values[(size_t)j] = std::move(vals[(size_t)j]);
+    }
+  }
+  // work areas beyond 64 MiB (the sort tier's pairs) are not kept by the calling thread
+  for (DeviceBuffer* b : {&ctx.sel_keys, &ctx.sel_docs, &ctx.sel_keys2, &ctx.sel_docs2, &ctx.sel_tmp, &ctx.sel_vals, &ctx.sel_bytes})
+    if (b->size > ((size_t)64 << 20)) b->release();
   fill_result_schema(seg, q, *res);
   st.host_ms_plan = (float)(t_plan - t0);
   st.host_ms_total = (float)(now_ms() - t0);

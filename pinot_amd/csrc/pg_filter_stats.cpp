@@ -1174,12 +1174,17 @@ struct DevEval {
 }  // namespace
 
 // `root`: the physical filter tree of the plan; `leaves`: the match bitmap of every Scan / Inverted leaf in it (from the GPU).
-int64_t emulate_entries_scanned_in_filter(const FilterOp& root, const StatLeafBits& leaves, int32_t n_docs) {
+int64_t emulate_entries_scanned_in_filter(const FilterOp& root, const StatLeafBits& leaves, int32_t n_docs, int64_t max_next) {
   Emu emu{leaves, n_docs, {}};
   SetPtr set = emu.trues(root);
   ItPtr it = emu.iterator(*set);
-  if (it->kind != ItKind::Bitmap && it->kind != ItKind::Sorted)   // an index-only iterator scans nothing while it is drained
-    while (it->next() != kEof) {}   // DocIdSetOperator drains the iterator
+  if (it->kind != ItKind::Bitmap && it->kind != ItKind::Sorted) {   // an index-only iterator scans nothing while it is drained
+    if (max_next < 0) {
+      while (it->next() != kEof) {}   // DocIdSetOperator drains the iterator
+    } else {
+      for (int64_t i = 0; i < max_next && it->next() != kEof; i++) {}   // ... or stops after max_next docs (SelectionOnlyOperator's LIMIT)
+    }
+  }
   int64_t total = 0;
   for (auto& c : emu.counters) total += c->entries;
   return total;

@@ -226,7 +226,8 @@ struct HostBits {
 };
 struct FilterOp;
 using StatLeafBits = std::unordered_map<const FilterOp*, HostBits>;
-int64_t emulate_entries_scanned_in_filter(const FilterOp& root, const StatLeafBits& leaves, int32_t n_docs);
+// max_next >= 0: the count at the point where the consumer stopped after that many next() calls (a selection's LIMIT), not drained
+int64_t emulate_entries_scanned_in_filter(const FilterOp& root, const StatLeafBits& leaves, int32_t n_docs, int64_t max_next = -1);
 // The same count without the bitmaps leaving HBM, for the shapes whose automaton decomposes into tiles (pg_filter_stats_tiles.h): an AND whose
 // children are scans, index-based leaves and flat ORs of both, under any nest of drained ORs / NOTs.  `filter_stats_on_device`: does the plan's
 // tree have such a shape; `entries_scanned_on_device`: the count, given every Scan / Inverted / RangeIdx leaf's match bitmap on the device
@@ -343,6 +344,15 @@ struct DistinctShape {
   bool ordered = false;            // ORDER BY present
 };
 DistinctShape distinct_shape(Segment& seg, const pg_query& q);
+// selection queries (PG_QUERY_FLAG_SELECTION): the checked output columns and ORDER BY (pg_plan.cpp); execute_selection runs them (pg_exec.hip)
+struct SelectionShape {
+  std::vector<Column*> cols;                 // per output column (extractExpressions order)
+  std::vector<std::pair<int, bool>> order;   // the distinct ORDER BY columns: (output column, ascending), most significant first
+  int key_bits = 0;                          // width of the order-space key (<= 64)
+  int n_distinct = 0;                        // distinct output columns (ProjectOperator#getNumColumnsProjected)
+};
+SelectionShape selection_shape(Segment& seg, const pg_query& q);
+std::vector<std::pair<const FilterOp*, std::shared_ptr<CompiledPlan>>> stat_leaf_plans(Segment& seg, const CompiledPlan& P);
 std::string query_signature(const pg_filter_node* filter, const pg_query* query, int32_t flags = 0);
 
 // ---- results --------------------------------------------------------------------------------------------------------------------
@@ -424,6 +434,7 @@ struct Result {
   std::vector<std::vector<uint8_t>> agg_nulls, key_nulls;
   bool null_handling = false;   // the query ran with PG_QUERY_FLAG_NULL_HANDLING (its data table carries the columns' null bitmaps)
   bool distinct = false;        // PG_QUERY_FLAG_DISTINCT: the groups are the distinct tuples, no aggregation (never merged in the library)
+  bool selection = false;       // PG_QUERY_FLAG_SELECTION: the groups are the selected rows (never merged in the library)
   pg_exec_stats stats{};
 };
 struct DocIdSet {
@@ -447,6 +458,7 @@ std::unique_ptr<Result> execute_query(Segment& seg, const pg_query& q, const Can
 // three-valued logic even where the reference's FastFilteredCountOperator would not (a lone COUNT(*) over an index-only filter)
 constexpr int32_t kQueryFlagNullPartition = 0x40000000;
 std::unique_ptr<Result> execute_distinct(Segment& seg, const pg_query& q, const CancelToken* cancel);   // PG_QUERY_FLAG_DISTINCT (pg_exec.hip)
+std::unique_ptr<Result> execute_selection(Segment& seg, const pg_query& q, const CancelToken* cancel);  // PG_QUERY_FLAG_SELECTION (pg_exec.hip)
 std::unique_ptr<Result> execute_query_plain(Segment& seg, const pg_query& q, const CancelToken* cancel);   // ... the executor proper (pg_exec.hip)
 void fill_result_schema(Segment& seg, const pg_query& q, Result& r);
 int64_t hll_cardinality(const uint8_t* regs, int log2m);   // HyperLogLog#cardinality of one register row (pg_exec.hip)
@@ -507,6 +519,7 @@ struct Knobs {
   int64_t exact_stats_max_docs = (int64_t)1 << 22;
   int64_t exact_stats_device_max_docs = (int64_t)1 << 27;   // PG_EXACT_STATS_DEVICE_MAX_DOCS: ... and where the device counts it (pg_filter_stats_tiles.h: ~1 ms per 10^8 docs)
   bool filter_stats_host = false;   // PG_FILTER_STATS_HOST: the iterator automaton always walks on the host (pg_filter_stats.cpp), also for shapes the device counts
+  int64_t select_sort_max_bytes = (int64_t)8 << 30;   // PG_SELECT_SORT_MAX_BYTES: work area of a selection's sort tier (larger ones are refused)
   int64_t limit_prefix_min_docs = (int64_t)1 << 20;   // PG_LIMIT_PREFIX_MIN_DOCS: smallest doc prefix of the numGroupsLimit admission pass (tests lower it)
   std::string oct_passes;      // PG_OCT_PASSES: cumulative fractions, e.g. "0.02,0.08,0.3,1"
   // pg_comm.cpp

@@ -2597,3 +2597,81 @@ DistinctShape distinct_shape(Segment& seg, const pg_query& q) {
 }
 
 }  // namespace pg
+
+namespace pg {
+
+// ---- selection queries ----------------------------------------------------------------------------------------------------------------------
+// SelectionPlanNode#run (core/plan/SelectionPlanNode.java:58-125): LIMIT 0 -> EmptySelectionOperator; no ORDER BY -> SelectionOnlyOperator; an
+// ORDER BY whose first expression is a sorted column -> the linear SelectionPartiallyOrdered{ByAsc,ByDesc} operators (refused here: the Java plan
+// answers); otherwise SelectionOrderByOperator.  The output columns arrive in SelectionOperatorUtils#extractExpressions order (:83-125).
+SelectionShape selection_shape(Segment& seg, const pg_query& q) {
+  if (q.n_aggregations != 0) fail(PG_ERR_INVALID_ARGUMENT, "PG_QUERY_FLAG_SELECTION with %d aggregations (must be 0)", q.n_aggregations);
+  if (q.n_group_by < 1 || !q.group_by_columns) fail(PG_ERR_INVALID_ARGUMENT, "a selection needs at least one output column");
+  if (q.n_group_by > PG_SELECT_MAX_OUT_COLS) fail(PG_ERR_UNSUPPORTED, "selection of more than %d columns", PG_SELECT_MAX_OUT_COLS);
+  if (q.limit < 0) fail(PG_ERR_INVALID_ARGUMENT, "selection with LIMIT %d", q.limit);
+  if (q.n_order_by < 0 || (q.n_order_by > 0 && !q.order_by)) fail(PG_ERR_INVALID_ARGUMENT, "order_by is null");
+  SelectionShape S;
+  const int n = q.n_group_by;
+  for (int j = 0; j < n; j++) {
+    const char* name = q.group_by_columns[j];
+    Column* c = name ? seg.find(name) : nullptr;
+    if (!c) {
+      bool identifier = name && *name;
+      for (const char* p = name; identifier && *p; p++) identifier = isalnum((unsigned char)*p) || *p == '_' || *p == '.' || *p == '$';
+      if (!identifier) fail(PG_ERR_UNSUPPORTED, "selection of the expression %s", name ? name : "(null)");
+      fail(PG_ERR_NOT_FOUND, "column not found: %s", name);
+    }
+    if (c->is_mv || c->raw_mv) fail(PG_ERR_UNSUPPORTED, "selection of the multi-value column %s", c->name.c_str());
+    if (q.flags & PG_QUERY_FLAG_NULL_HANDLING) {
+      auto it = seg.null_vectors.find(c->name);
+      if (it != seg.null_vectors.end() && it->second && !it->second->posting_card.empty() && it->second->posting_card[0] > 0)
+        fail(PG_ERR_UNSUPPORTED, "enableNullHandling: selection of %s, which holds nulls", c->name.c_str());
+    }
+    const bool dict = c->has_dictionary && c->col_kind == PG_COL_FIXED_BIT && c->bits >= 1 && c->bits <= 31;
+    if (!dict && c->col_kind != PG_COL_RAW32 && c->col_kind != PG_COL_RAW64 && c->col_kind != PG_COL_VAR_BYTES)
+      fail(PG_ERR_UNSUPPORTED, "selection of the column %s (layout %d)", c->name.c_str(), c->col_kind);
+    S.cols.push_back(c);
+  }
+  for (int j = 0; j < n; j++) {   // numColumnsProjected counts each column once
+    bool seen = false;
+    for (int i = 0; i < j; i++) seen = seen || S.cols[(size_t)i] == S.cols[(size_t)j];
+    S.n_distinct += seen ? 0 : 1;
+  }
+  if (q.limit == 0) return S;   // EmptySelectionOperator: the ORDER BY is not looked at
+  if (q.n_order_by > PG_SELECT_MAX_KEY_COLS) fail(PG_ERR_UNSUPPORTED, "selection ordered by more than %d expressions", PG_SELECT_MAX_KEY_COLS);
+  int key_bits = 0;
+  for (int32_t i = 0; i < q.n_order_by; i++) {
+    const pg_order_by& ob = q.order_by[i];
+    if (ob.kind != PG_ORDER_BY_GROUP_KEY) fail(PG_ERR_INVALID_ARGUMENT, "selection ordered by an expression of kind %d", ob.kind);
+    if (ob.index < 0 || ob.index >= n) fail(PG_ERR_INVALID_ARGUMENT, "ORDER BY output column %d of %d", ob.index, n);
+    Column* c = S.cols[(size_t)ob.index];
+    if (i == 0 && c->is_sorted)
+      fail(PG_ERR_UNSUPPORTED, "selection ordered by the sorted column %s first (SelectionPartiallyOrdered operators)", c->name.c_str());
+    if (c->col_kind == PG_COL_VAR_BYTES) fail(PG_ERR_UNSUPPORTED, "selection ordered by the raw STRING / BYTES column %s", c->name.c_str());
+    bool repeated = false;   // QueryContext dedupes the ORDER BY expressions: a repeated column decides nothing more
+    for (const auto& o : S.order) repeated = repeated || S.cols[(size_t)o.first] == c;
+    if (repeated) continue;
+    S.order.push_back({ob.index, ob.ascending != 0});
+    key_bits += c->has_dictionary ? c->bits : (c->col_kind == PG_COL_RAW32 ? 32 : 64);
+    if (key_bits > 64) fail(PG_ERR_UNSUPPORTED, "selection ORDER BY key of more than 64 bits");
+  }
+  S.key_bits = key_bits;
+  return S;
+}
+
+// Filter-only plans of every Scan / Inverted / range-index leaf of P's filter tree, whose match bitmaps feed the iterator automaton
+// (pg_filter_stats.cpp).  Plans whose kernels count the statistic themselves carry none: they are compiled here, per call.
+std::vector<std::pair<const FilterOp*, std::shared_ptr<CompiledPlan>>> stat_leaf_plans(Segment& seg, const CompiledPlan& P) {
+  if (!P.stat_leaves.empty() || !P.root_op) return P.stat_leaves;
+  std::vector<const FilterOp*> leaves;
+  collect_stat_leaves(*P.root_op, leaves);
+  std::vector<std::pair<const FilterOp*, std::shared_ptr<CompiledPlan>>> out;
+  std::lock_guard<std::mutex> lock(seg.mu);
+  for (const FilterOp* leaf : leaves) {
+    if (leaf->kind == OpKind::Inverted && (leaf->eval.exclusive ? leaf->eval.non_matching : leaf->eval.matching).empty()) continue;
+    out.push_back({leaf, compile_in_space(seg, clone_leaf(*leaf), nullptr, nullptr, -1)});
+  }
+  return out;
+}
+
+}  // namespace pg

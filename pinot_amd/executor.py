@@ -111,7 +111,7 @@ class NativeSegment:
     # -- FilterOperator / DocIdSetOperator ------------------------------------------------------------------------
     def filter(self, q, null_handling: bool = False) -> "DocIdSet":
         qc = parse_sql(q) if isinstance(q, str) else q
-        cq = CQuery(qc)
+        cq = CQuery(qc, tuple(self.host.columns))
         h = C.c_void_p()
         if null_handling or (qc.flags & capi.QUERY_FLAG_NULL_HANDLING):   # enableNullHandling=true: three-valued filter
             self.api.call("filter_exec_flags", self.handle, cq.filter_ptr(), capi.QUERY_FLAG_NULL_HANDLING, C.byref(h))
@@ -125,9 +125,10 @@ class NativeSegment:
         if profile:
             qc.flags |= capi.QUERY_FLAG_PROFILE
         cached = getattr(qc, "_cquery", None)     # the C structs of a QueryContext are reusable across executions
-        key = (qc.flags, qc.num_groups_limit, qc.limit, qc.min_segment_group_trim_size)
+        cols = tuple(self.host.columns) if qc.selection else ()
+        key = (qc.flags, qc.num_groups_limit, qc.limit, qc.min_segment_group_trim_size, cols)
         if cached is None or cached[0] != key:
-            cached = (key, CQuery(qc))
+            cached = (key, CQuery(qc, cols))
             qc._cquery = cached
         cq = cached[1]
         h = C.c_void_p()
@@ -143,11 +144,12 @@ class NativeSegment:
         qc = parse_sql(q) if isinstance(q, str) else q
         flags = qc.flags | (capi.QUERY_FLAG_KEEP_DEVICE_TABLE if keep_device_table else 0)
         cache = getattr(qc, "_cquery_native", None)
-        key = (flags, qc.num_groups_limit, qc.limit, qc.min_segment_group_trim_size)
+        cols = tuple(self.host.columns) if qc.selection else ()
+        key = (flags, qc.num_groups_limit, qc.limit, qc.min_segment_group_trim_size, cols)
         if cache is None or cache[0] != key:
             saved = qc.flags
             qc.flags = flags
-            cache = (key, CQuery(qc))
+            cache = (key, CQuery(qc, cols))
             qc.flags = saved
             qc._cquery_native = cache
         h = C.c_void_p()
@@ -308,6 +310,13 @@ class DocIdSet:
             pass
 
 
+def _key_columns(qc: QueryContext, host: HostSegment) -> List[str]:
+    """The columns whose values come back as group keys: GROUP BY columns, DISTINCT columns, or a selection's output columns."""
+    if qc.selection:
+        return qc.extract_expressions(host.columns)
+    return qc.distinct or qc.group_by
+
+
 def _key_repr(v):
     """Group key component as a dict key: floats keep their sign of zero (-0.0 and 0.0 are two groups in the reference's
     Float2Int / Double2Int maps, but equal as Python floats) and NaN compares equal to itself."""
@@ -345,7 +354,8 @@ class ResultsBlock:
         n = C.c_int32()
         api.call("result_num_groups", h, C.byref(n))
         ng = n.value
-        keys = qc.distinct or qc.group_by   # SELECT DISTINCT: the tuples come back as group keys
+        keys = _key_columns(qc, host)   # SELECT DISTINCT: the tuples, a selection: the rows come back as group keys
+        rb.key_columns = keys
         ngb = len(keys)
         ids = np.zeros((ngb, ng), dtype=np.int32)
         rb.group_values = None
@@ -445,7 +455,14 @@ class ResultsBlock:
 
     @property
     def num_groups(self) -> int:
-        return self.group_dict_ids.shape[1] if (self.query.distinct or self.query.group_by) else 1
+        return self.group_dict_ids.shape[1] if (self.query.distinct or self.query.group_by or self.query.selection) else 1
+
+    @property
+    def selection_rows(self) -> List[tuple]:
+        """A selection: the rows in result order (sorted under ORDER BY, else in docId order), one value per output column
+        (`key_columns`, extractExpressions order), decoded as distinct_rows are."""
+        assert self.query.selection, "not a selection query"
+        return self.group_keys
 
     @property
     def distinct_rows(self) -> List[tuple]:
@@ -464,7 +481,7 @@ class ResultsBlock:
             vcols = getattr(self, "group_value_columns", {})
             ng = self.num_groups
             per_col = []
-            for j, g in enumerate(self.query.distinct or self.query.group_by):
+            for j, g in enumerate(getattr(self, "key_columns", None) or self.query.distinct or self.query.group_by):
                 if j in vcols:   # raw values; a NaN key is one group: give it a key that compares equal to itself
                     v = vcols[j]
                     per_col.append(list(v) if v.dtype == object else ([int(x) for x in v] if v.dtype == np.int64 else [float(x) for x in v]))
@@ -630,7 +647,7 @@ class GpuInstancePlanMaker:
 
     def make_segment_plan_node(self, segment: NativeSegment, query):
         qc = parse_sql(query) if isinstance(query, str) else query
-        cq = CQuery(qc)
+        cq = CQuery(qc, tuple(segment.host.columns))
         self.api.call("query_supported", segment.handle, cq.ptr())
         return _SegmentPlanNode(segment, qc)
 

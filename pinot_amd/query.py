@@ -101,6 +101,25 @@ class QueryContext:
     has_group_by: bool = False
     min_segment_group_trim_size: int = -1   # InstancePlanMakerImplV2.DEFAULT_MIN_SEGMENT_GROUP_TRIM_SIZE: the segment's groups are not trimmed
     distinct: List[str] = field(default_factory=list)   # SELECT DISTINCT a, b: the DISTINCT columns (empty: not a DISTINCT query)
+    selection: List[str] = field(default_factory=list)  # a selection query (no aggregation, GROUP BY or DISTINCT): its select list, "*" kept
+
+    def extract_expressions(self, column_names) -> List[str]:
+        """The output columns of a selection on a segment with these columns: SelectionOperatorUtils#extractExpressions (:83-125) — the
+        ORDER BY expressions first (none under LIMIT 0), then the select list without them; SELECT * is every column not starting with '$',
+        sorted by name."""
+        out = []
+        if self.limit > 0:
+            for text, _ in self.order_by:
+                if text not in out:
+                    out.append(text)
+        if self.selection == ["*"]:
+            rest = sorted(c for c in column_names if not c.startswith("$"))
+        else:
+            rest = self.selection
+        for c in rest:
+            if c not in out:
+                out.append(c)
+        return out
 
     def resolved_order_by(self) -> "Optional[List[Tuple[int, int, bool]]]":
         """(kind, index, ascending) per ORDER BY expression as TableResizer resolves them (TableResizer.java:129-161): a group-by expression
@@ -279,6 +298,9 @@ class _Parser:
     # --- select -------------------------------------------------------------------------------------------------
     def select_item(self, q: QueryContext):
         t = self.take()
+        if t == ("op", "*"):   # SELECT *
+            q.select_columns.append("*")
+            return
         if t[0] != "id":
             raise SqlError(f"bad select item {t}")
         if self.peek() == ("op", "("):
@@ -381,6 +403,12 @@ class _Parser:
                 raise SqlError("ORDER BY of a DISTINCT query must name DISTINCT columns")
             q.distinct = list(q.select_columns)
             q.flags |= capi.QUERY_FLAG_DISTINCT
+        elif not q.aggregations and not q.has_group_by:
+            # SelectionPlanNode: a query without aggregations, GROUP BY or DISTINCT selects rows; SELECT * stands alone
+            if "*" in q.select_columns and len(q.select_columns) > 1:
+                raise SqlError("SELECT * cannot be combined with other select expressions")
+            q.selection = list(q.select_columns)
+            q.flags |= capi.QUERY_FLAG_SELECTION
         return q
 
 
@@ -399,7 +427,8 @@ _PRED_TYPES = {"EQ": capi.PRED_EQ, "NOT_EQ": capi.PRED_NOT_EQ, "IN": capi.PRED_I
 
 
 class CQuery:
-    def __init__(self, q: QueryContext):
+    def __init__(self, q: QueryContext, column_names=None):
+        """`column_names`: the segment's columns — a selection's output list (SELECT *) is built when the query is bound to a segment."""
         self._keep = []
         self.query = capi.PgQuery()
         if q.filter is not None:
@@ -409,7 +438,13 @@ class CQuery:
             self.query.filter = C.pointer(root)
         else:
             self.query.filter = None
-        keys = q.distinct or q.group_by
+        if q.selection:
+            if q.selection == ["*"] and column_names is None:
+                raise SqlError("SELECT * needs the segment's column names")
+            keys = q.extract_expressions(column_names if column_names is not None else [])
+        else:
+            keys = q.distinct or q.group_by
+        self.output_columns = keys
         ng = len(keys)
         self.query.n_group_by = ng
         if ng:
@@ -428,10 +463,13 @@ class CQuery:
             self.query.aggregations = aggs
         self.query.num_groups_limit = q.num_groups_limit
         self.query.max_initial_result_holder_capacity = q.max_initial_result_holder_capacity
-        self.query.flags = q.flags | (capi.QUERY_FLAG_DISTINCT if q.distinct else 0)
+        self.query.flags = q.flags | (capi.QUERY_FLAG_DISTINCT if q.distinct else 0) | (capi.QUERY_FLAG_SELECTION if q.selection else 0)
         # segment-level group trim (GroupByOperator.java:120-133): ORDER BY + LIMIT + minSegmentGroupTrimSize travel with group-by queries
         if q.distinct:   # ORDER BY over DISTINCT columns: group-key entries
             ob = [(capi.ORDER_BY_GROUP_KEY, q.distinct.index(text), asc) for text, asc in q.order_by] or None
+        elif q.selection:   # ORDER BY over output columns (ignored under LIMIT 0: EmptySelectionOperator)
+            ob = [(capi.ORDER_BY_GROUP_KEY, keys.index(text), asc) for text, asc in q.order_by] if q.limit > 0 else None
+            ob = ob or None
         else:
             ob = q.resolved_order_by() if (ng and q.order_by) else None
         self.query.limit = q.limit
