@@ -16,6 +16,40 @@ SV_FILTER = (" WHERE column1 > 100000000"
              " AND daysSinceEpoch = 126164076")
 
 
+def compare_with_oracle(gb, ob, what):
+    """A ResultsBlock of the HIP path against the oracle's: rows exactly, and the ExecutionStatistics of the query's filter and operator."""
+    gr, orr = gb.rows(), ob.rows()
+    assert set(gr) == set(orr), what
+    for k in orr:
+        assert gr[k] == orr[k], (what, k, gr[k], orr[k])
+    assert gb.stats.num_docs_scanned == ob.stats.num_docs_scanned, what
+    assert gb.stats.num_entries_scanned_post_filter == ob.stats.num_entries_scanned_post_filter, what
+    assert gb.stats.num_groups_limit_reached == ob.stats.num_groups_limit_reached, what
+    assert gb.stats.stats_exact == 1, what
+    assert gb.stats.num_entries_scanned_in_filter == ob.stats.num_entries_scanned_in_filter, what
+
+
+def wide_segment(n=180_003, seed=21):
+    """Wide group columns and 64-bit sources (the `wide` table of tests/test_gpu_parity.py): an 11-bit key, raw LONG / DOUBLE / FLOAT
+    metrics, a dictionary-encoded LONG, a raw INT scan column, an inverted-index column, and `kq` — a dictionary INT column of squares
+    (no arithmetic form, <= 3 000 values)."""
+    rng = np.random.default_rng(seed)
+    data = {
+        "k": rng.integers(0, 2000, n).astype(np.int32),            # 11-bit dictionary column
+        "k2": rng.integers(0, 7, n).astype(np.int32),
+        "lm": rng.integers(-10**12, 10**12, n).astype(np.int64),    # raw LONG metric
+        "dm": (rng.integers(-10**6, 10**6, n) * 0.25).astype(np.float64),   # raw DOUBLE, exactly representable sums
+        "fm": (rng.integers(-1000, 1000, n) * 0.5).astype(np.float32),      # raw FLOAT
+        "ld": rng.integers(0, 300, n).astype(np.int64) * 10**10,     # dictionary-encoded LONG
+        "r": rng.integers(0, 1000, n).astype(np.int32),
+        "inv": rng.integers(0, 5, n).astype(np.int32),
+    }
+    data["kq"] = (rng.integers(0, 3000, n) ** 2).astype(np.int32)
+    return build_segment("wide", data, {"k": "INT", "k2": "INT", "lm": "LONG", "dm": "DOUBLE", "fm": "FLOAT", "ld": "LONG",
+                                        "r": "INT", "inv": "INT", "kq": "INT"},
+                         inverted_index_columns=["inv"], no_dictionary_columns=["lm", "dm", "fm", "r"])
+
+
 def sv_segment(sv_data, name="testTable_126164076_167572854"):
     data = {k: (v.tolist() if v.dtype.kind == "U" else v) for k, v in sv_data.items()}
     return build_segment(name, data, SV_SCHEMA, inverted_index_columns=SV_INVERTED)

@@ -59,6 +59,33 @@ def build_with_raw_twins(rows, name="mvTable", compression=(0, 3, 4, 2, 5)) -> H
     return seg
 
 
+def group_table(n, seed) -> HostSegment:
+    """The table of tests/test_gpu_mv_group.py (the kernels for GROUP BY one multi-value column and the *MV functions): built from numpy
+    draws, so it scales to segments of 10^5 - 10^6 docs."""
+    rng = np.random.default_rng(seed)
+
+    def mv(card, lo, hi, empty=False):
+        lens = rng.integers(lo, hi + 1, n)
+        if empty:
+            lens[rng.random(n) < 0.05] = 0     # the segment creator stores the default null value for an empty row
+        flat = rng.integers(0, card, int(lens.sum()))
+        out, at = [], 0
+        for k in lens.tolist():
+            out.append(flat[at:at + k].tolist())
+            at += k
+        return out
+    seg = HostSegment("mvg", n)
+    seg.columns["mvA"] = build_mv_column("mvA", mv(20, 1, 3), "INT")               # <= 4 entries: pg_mv_group_4
+    seg.columns["mvB"] = build_mv_column("mvB", mv(1000, 1, 6, empty=True), "INT")  # <= 8: pg_mv_group_8, never the tail
+    seg.columns["mvC"] = build_mv_column("mvC", mv(50, 1, 11), "LONG")              # up to 11: pg_mv_group_8 + the tail loop
+    seg.columns["mvD"] = build_mv_column("mvD", [[v * 7 - 20000 for v in row] for row in mv(6000, 1, 3)], "INT")   # > 4 096 values: the dictionary stays in global memory
+    seg.columns["mvS"] = build_mv_column("mvS", [[f"k{v % 7}" for v in row] for row in mv(40, 1, 4)], "STRING")
+    seg.columns["m"] = build_column("m", rng.integers(-(1 << 31), 1 << 31, n).astype(np.int64).tolist(), "INT", dictionary=False)
+    seg.columns["md"] = build_column("md", rng.integers(0, 300, n).tolist(), "INT")                      # dictionary-encoded value: not this kernel's shape
+    seg.columns["s1"] = build_column("s1", rng.integers(0, 5, n).tolist(), "INT")
+    return seg
+
+
 INT_DEFAULT = -(1 << 31)
 
 

@@ -9,6 +9,7 @@ import pytest
 
 from pinot_amd import capi
 from pinot_amd.executor import NativeSegment
+from tests.fixtures import compare_with_oracle
 from tests.fuzz_queries import Gen, clone, describe, eval_filter, fuzz_segment
 
 
@@ -127,18 +128,6 @@ def test_oracle_raw_key_groups_match_brute_force(oracle_api, fuzz):
     o.destroy()
 
 
-def _compare(gb, ob, what):
-    gr, orr = gb.rows(), ob.rows()
-    assert set(gr) == set(orr), what
-    for k in orr:
-        assert gr[k] == orr[k], (what, k, gr[k], orr[k])
-    assert gb.stats.num_docs_scanned == ob.stats.num_docs_scanned, what
-    assert gb.stats.num_entries_scanned_post_filter == ob.stats.num_entries_scanned_post_filter, what
-    assert gb.stats.num_groups_limit_reached == ob.stats.num_groups_limit_reached, what
-    assert gb.stats.stats_exact == 1, what
-    assert gb.stats.num_entries_scanned_in_filter == ob.stats.num_entries_scanned_in_filter, what
-
-
 # The -m gpu suite runs inside a time limit of the driver's: the default number of random queries per test is 60 % of what the tests were
 # written with (PG_FUZZ_SCALE=1 for the full count, larger for a soak; PG_FUZZ_SEED_BASE for other queries)
 FUZZ_SCALE = float(os.environ.get("PG_FUZZ_SCALE", "0.6"))
@@ -173,7 +162,7 @@ def test_gpu_matches_oracle_on_random_queries(gpu_api, oracle_api, fuzz, seed, w
             unsupported.append((what, str(e)))
             continue
         try:
-            _compare(gb, ob, what)
+            compare_with_oracle(gb, ob, what)
             if i % 3 == 0:              # the filter-only entry point (FilterOperator + DocIdSetOperator): same docIds
                 gd, od = g.filter(clone(q)), o.filter(clone(q))
                 assert gd.cardinality() == od.cardinality(), what
@@ -304,7 +293,7 @@ def test_gpu_star_tree_matches_oracle_on_random_queries(gpu_api, oracle_api):
         gb, ob = g.execute(clone(q)), o.execute(clone(q))
         try:
             assert gb.stats.star_tree_index == ob.stats.star_tree_index, what
-            _compare(gb, ob, what)
+            compare_with_oracle(gb, ob, what)
         except AssertionError as e:
             mismatches.append(str(e)[:600])
     assert not mismatches, "\n".join(mismatches[:12])
@@ -325,7 +314,7 @@ def test_gpu_raw_key_groups_match_oracle_on_random_queries(gpu_api, oracle_api, 
         what = f"raw keys #{i} {describe(q)}"
         gb, ob = g.execute(clone(q)), o.execute(clone(q))
         try:
-            _compare(gb, ob, what)
+            compare_with_oracle(gb, ob, what)
         except AssertionError as e:
             mismatches.append(str(e)[:600])
     assert not mismatches, "\n".join(mismatches[:12])

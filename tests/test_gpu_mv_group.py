@@ -7,40 +7,14 @@ pg_mv_aggr_*: the *MV functions over one multi-value INT column grouped by singl
 (SumMVAggregationFunction.java, CountMVAggregationFunction.java:62-96, MinMV / MaxMV / AvgMV / MinMaxRangeMV)."""
 import os
 
-import numpy as np
 import pytest
 
 from pinot_amd import capi
 from pinot_amd.executor import NativeSegment
-from pinot_amd.segment import HostSegment, build_column, build_mv_column
+from tests.mv_fixture import group_table as table
 
 pytestmark = pytest.mark.gpu
 STATS = ("num_docs_scanned", "num_entries_scanned_in_filter", "num_entries_scanned_post_filter", "num_total_docs")
-
-
-def table(n, seed):
-    rng = np.random.default_rng(seed)
-
-    def mv(card, lo, hi, empty=False):
-        lens = rng.integers(lo, hi + 1, n)
-        if empty:
-            lens[rng.random(n) < 0.05] = 0     # the segment creator stores the default null value for an empty row
-        flat = rng.integers(0, card, int(lens.sum()))
-        out, at = [], 0
-        for k in lens.tolist():
-            out.append(flat[at:at + k].tolist())
-            at += k
-        return out
-    seg = HostSegment("mvg", n)
-    seg.columns["mvA"] = build_mv_column("mvA", mv(20, 1, 3), "INT")               # <= 4 entries: pg_mv_group_4
-    seg.columns["mvB"] = build_mv_column("mvB", mv(1000, 1, 6, empty=True), "INT")  # <= 8: pg_mv_group_8, never the tail
-    seg.columns["mvC"] = build_mv_column("mvC", mv(50, 1, 11), "LONG")              # up to 11: pg_mv_group_8 + the tail loop
-    seg.columns["mvD"] = build_mv_column("mvD", [[v * 7 - 20000 for v in row] for row in mv(6000, 1, 3)], "INT")   # > 4 096 values: the dictionary stays in global memory
-    seg.columns["mvS"] = build_mv_column("mvS", [[f"k{v % 7}" for v in row] for row in mv(40, 1, 4)], "STRING")
-    seg.columns["m"] = build_column("m", rng.integers(-(1 << 31), 1 << 31, n).astype(np.int64).tolist(), "INT", dictionary=False)
-    seg.columns["md"] = build_column("md", rng.integers(0, 300, n).tolist(), "INT")                      # dictionary-encoded value: not this kernel's shape
-    seg.columns["s1"] = build_column("s1", rng.integers(0, 5, n).tolist(), "INT")
-    return seg
 
 
 QUERIES = [

@@ -9,7 +9,7 @@ import pytest
 from pinot_amd import synth
 from pinot_amd.executor import NativeSegment
 from pinot_amd.segment import build_segment
-from tests.fixtures import SV_FILTER, sv_segment
+from tests.fixtures import SV_FILTER, sv_segment, wide_segment
 from tests.test_oracle_goldens import AGGREGATION_QUERY, FFC_CASES, RANGE_CASES, check_agg
 
 pytestmark = pytest.mark.gpu
@@ -416,21 +416,7 @@ def test_plain_c_caller_of_the_abi():
 # ---- LDS aggregation over wide group columns and 64-bit sources (pg_fast_none_w / pg_fast_multi_w, general aggregator) ----------
 @pytest.fixture(scope="module")
 def wide_seg(gpu_api, oracle_api):
-    rng = np.random.default_rng(21)
-    n = 180_003
-    data = {
-        "k": rng.integers(0, 2000, n).astype(np.int32),            # 11-bit dictionary column
-        "k2": rng.integers(0, 7, n).astype(np.int32),
-        "lm": rng.integers(-10**12, 10**12, n).astype(np.int64),    # raw LONG metric
-        "dm": (rng.integers(-10**6, 10**6, n) * 0.25).astype(np.float64),   # raw DOUBLE, exactly representable sums
-        "fm": (rng.integers(-1000, 1000, n) * 0.5).astype(np.float32),      # raw FLOAT
-        "ld": rng.integers(0, 300, n).astype(np.int64) * 10**10,     # dictionary-encoded LONG
-        "r": rng.integers(0, 1000, n).astype(np.int32),
-        "inv": rng.integers(0, 5, n).astype(np.int32),
-    }
-    host = build_segment("wide", data, {"k": "INT", "k2": "INT", "lm": "LONG", "dm": "DOUBLE", "fm": "FLOAT", "ld": "LONG",
-                                         "r": "INT", "inv": "INT"},
-                         inverted_index_columns=["inv"], no_dictionary_columns=["lm", "dm", "fm", "r"])
+    host = wide_segment()
     g, o = both(gpu_api, oracle_api, host)
     yield g, o
     g.destroy()
