@@ -11,8 +11,12 @@ in HBM; segments share dictionaries).  Segments shard one per GPU (`scaling: wea
 merge.  `--gpus N` without a torchrun environment re-executes itself under `python -m torch.distributed.run` with N ranks.
 
 Prints ONE JSON line (rank 0) with the contract fields plus `roofline` (HBM-bound: algorithmic bytes per launch ÷ HIP-event
-kernel time ÷ 8 TB/s) and `cpu_baseline` (the C restatement of the reference algorithm, oracle/, one thread per segment
-as the reference runs it, on a bounded prefix sample of the same segment).
+kernel time of the timed steps ÷ 8 TB/s).  A plain run does only what that line's headline needs: set-up, warm-up, the timed steps,
+`--dump-outputs`, the line.  `--full` adds everything else the benchmark measures or checks, each in runs of its own after the timed
+steps: `roofline.traffic` (PMC child runs), `cpu_baseline` (the C restatement of the reference algorithm, oracle/, one thread per
+segment as the reference runs it, on a bounded prefix sample of the same segment) with the full-size oracle check of the timed
+result, the north-star variant, the concurrency block, BASELINE configs 2 and 5 and the dictionary-encoded config 3 next to the
+headline, and, for N > 1, `multi_gpu_validation`.  The `--no-*` options each take one of those away from a `--full` run.
 """
 import argparse
 import ctypes as C
@@ -46,6 +50,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--docs", type=int, default=int(os.environ.get("PG_BENCH_DOCS", "1000000000")),
                     help="rows per segment (BASELINE config 3: 1e9)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run everything else the benchmark measures or checks (CPU baseline and oracle checks, HBM "
+                         "traffic passes, north-star variant, concurrency block, BASELINE configs 2 and 5, dictionary-encoded config 3, N > 1 "
+                         "parity checks); a run without it stops at the headline line.  The --no-* options below narrow a --full run")
     ap.add_argument("--no-validation", action="store_true", help="N > 1: skip the parity checks of the merged table (multi_gpu_validation)")
     ap.add_argument("--query", choices=["cfg3", "northstar", "cfg2", "cfg5", "cfg3_dict", "cfg3_sparse"], default="cfg3",
                     help="cfg5: BASELINE config 5 — 4-dim GROUP BY (12 800 groups) + DISTINCTCOUNTHLL, flat segment timed like the others, "
@@ -56,8 +64,8 @@ def main():
                     help="skip the rocprofv3 PMC passes (FETCH_SIZE, WRITE_SIZE in their own runs) that measure roofline.traffic")
     ap.add_argument("--no-full-check", action="store_true",
                     help="skip the one full-size oracle run that checks the timed GPU result (about 4 s of CPU per 1e9 rows)")
-    ap.add_argument("--no-variants", action="store_true", help="skip the north-star (2-key) variant of the default run")
-    ap.add_argument("--no-concurrency", action="store_true", help="skip the concurrent-callers block of the default run")
+    ap.add_argument("--no-variants", action="store_true", help="skip the north-star (2-key) variant and the blocks of the other configurations of a --full run")
+    ap.add_argument("--no-concurrency", action="store_true", help="skip the concurrent-callers block of a --full run")
     ap.add_argument("--require-library-merge", action="store_true",
                     help="N > 1: exit non-zero when the library's own RCCL communicator cannot be created on every rank, instead of "
                          "falling back to the torch collective + host reduce")
@@ -67,6 +75,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if not args.full:   # a plain run: the headline alone
+        args.no_validation = args.no_cpu_baseline = args.no_traffic = args.no_variants = args.no_concurrency = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # not launched by torchrun: spawn the N ranks ourselves (one process per GPU, rendezvous on 127.0.0.1)
@@ -304,7 +314,7 @@ def main():
         out["concurrency"] = concurrency_block(api, args, bg_seg=seg, bg_sql=synth.QUERY_CFG3)
         log(f"concurrency block {time.time() - t_blocks:.1f}s")
     if args.query == "cfg3" and not args.no_variants and rank == 0 and world == 1:
-        # BASELINE configs 2 and 5 next to the headline (same timing discipline, their own segments): every default run carries them
+        # BASELINE configs 2 and 5 next to the headline (same timing discipline, their own segments): every --full run carries them
         headline_rows = dense.rows() if hasattr(dense, "rows") else None
         seg.destroy()
         seg = None
@@ -572,7 +582,7 @@ def abi_call_latency(api, seg, qc, warmup, steps):
 
 
 def extra_block(api, args, query, docs, bytes_per_row, columns, sql, same_rows_as=None):
-    """One more BASELINE configuration inside the default run: its own segment of `docs` rows pinned in HBM, `steps` timed executions
+    """One more BASELINE configuration inside a --full run: its own segment of `docs` rows pinned in HBM, `steps` timed executions
     after `warmup`, HIP-event kernel time → roofline fraction, HBM traffic from the PMC passes (child runs), and an oracle equality
     flag — the whole segment for config 2 (0.3 s of CPU), a 10 M-row prefix for config 5 (its oracle needs minutes at 1 B rows) plus
     a full-size invariant (the groups' counts add up to the segment's rows)."""
@@ -725,8 +735,7 @@ def measure_traffic(query, docs, kernel):
     for counter in ("FETCH_SIZE", "WRITE_SIZE"):
         d = tempfile.mkdtemp(prefix="pg_pmc_", dir="/tmp")
         cmd = ["rocprofv3", "--pmc", counter, "--kernel-trace", "-d", d, "-o", "x", "--", sys.executable, os.path.abspath(__file__),
-               "--docs", str(docs), "--query", query, "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--no-variants",
-               "--no-traffic"]
+               "--docs", str(docs), "--query", query, "--steps", "5", "--warmup", "2"]   # (a plain run: the query's kernels alone)
         env = dict(os.environ, TMPDIR="/tmp")
         try:
             subprocess.run(cmd, cwd="/tmp", env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=240, check=True)
@@ -776,7 +785,7 @@ def cpu_baseline(args, sql, gpu_block, gpu_seg):
     if sample == args.docs:   # the sample is the whole segment: check the timed GPU result right away
         assert gpu_block.rows() == block.rows(), "GPU result differs from the oracle"
         full_checked = True
-    # parity at sample scale in every run: the same prefix segment through the GPU library must equal the oracle bit for bit
+    # parity at sample scale in every --full run: the same prefix segment through the GPU library must equal the oracle bit for bit
     # (group keys, SUM / MAX values, ExecutionStatistics)
     from pinot_amd import capi
     gpu_prefix = NativeSegment(capi.gpu_api(), host)

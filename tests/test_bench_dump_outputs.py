@@ -65,3 +65,11 @@ def test_size_limit_takes_the_same_sample_every_time(blocks, tmp_path):
     idx = [pos[tuple(k)] for k in a["group_keys"].tolist()]
     assert idx == sorted(idx)
     assert all(np.array_equal(a[k], full[k][idx]) for k in a if k != "stats")
+
+
+def test_full_is_an_option():
+    """`--full` exists (what it gates needs a GPU: tests/test_gpu_bench_contract.py); checked on the parser's own help, before anything is imported."""
+    import subprocess
+    import sys
+    out = subprocess.run([sys.executable, bench.__file__, "--help"], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and "--full" in out.stdout.split("options:")[0], out.stdout[:500]

@@ -7,7 +7,7 @@ cd $R
 for spec in $1; do
   v=${spec%%:*}; w=${spec##*:}
   if [ "$v" = nopipe ]; then envs="PG_NO_PIPE=1"; else envs="PG_GPU_LIB=$R/tools/variants/libpinot_gpu_$v.so PG_PIPE_WGS_PER_CU=$w"; fi
-  out=$(env $envs timeout 120 python bench.py --no-cpu-baseline --no-traffic --no-full-check --steps 20 --warmup 5 2>/dev/null < /dev/null | tail -1)
+  out=$(env $envs timeout 120 python bench.py --full --no-cpu-baseline --no-traffic --no-full-check --steps 20 --warmup 5 2>/dev/null < /dev/null | tail -1)
   python - "$spec" "$out" <<'PY'
 import json, sys
 v, out = sys.argv[1:3]

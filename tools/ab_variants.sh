@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 cd $R
 for v in $1; do
   for w in ${2:-1}; do
-    out=$(PG_GPU_LIB=$R/tools/variants/libpinot_gpu_$v.so PG_WGS_PER_CU=$w timeout 120 python bench.py --no-cpu-baseline --steps 20 --warmup 5 2>/dev/null < /dev/null | tail -1)
+    out=$(PG_GPU_LIB=$R/tools/variants/libpinot_gpu_$v.so PG_WGS_PER_CU=$w timeout 120 python bench.py --full --no-cpu-baseline --steps 20 --warmup 5 2>/dev/null < /dev/null | tail -1)
     python - "$v" "$w" "$out" <<'PY'
 import json, sys
 v, w, out = sys.argv[1:4]

@@ -10,7 +10,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$R/gpurun_out
 mkdir -p "$OUT"
 cd "$R" || exit 1
-timeout 240 python bench.py > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.log" < /dev/null
+timeout 240 python bench.py --full > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.log" < /dev/null
 tail -c 600 "$OUT/${TAG}_bench.json"; echo
 ( cd /tmp && export TMPDIR=/tmp && timeout 150 rocprofv3 --kernel-trace -d "$OUT/${TAG}_prof" -o x -- \
     python "$R/bench.py" --no-cpu-baseline --no-variants --steps 20 --warmup 5 > "$OUT/${TAG}_bench_under_rocprof.json" 2> /dev/null < /dev/null )

@@ -2,7 +2,7 @@
 # round 3, GPU call F: whole GPU suite + default bench (with the cfg2 / cfg5 blocks)
 R=${GRAFT_REPO_ROOT:-/root/repo}; cd $R; O=$R/gpurun_out; mkdir -p $O; TAG=${1:-r03_f}
 timeout 900 python -m pytest tests -x -q -m gpu > $O/${TAG}_tests.log 2>&1; echo "gpu suite rc=$?"; tail -6 $O/${TAG}_tests.log
-( time timeout 600 python bench.py > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err ) 2> $O/${TAG}_bench.time; echo "bench rc=$?"; cat $O/${TAG}_bench.time | grep real
+( time timeout 600 python bench.py --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err ) 2> $O/${TAG}_bench.time; echo "bench rc=$?"; cat $O/${TAG}_bench.time | grep real
 tail -3 $O/${TAG}_bench.err
 python - <<PY
 import json

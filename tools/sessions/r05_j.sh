@@ -1,7 +1,7 @@
 #!/bin/bash
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}
 OUT=$R/gpurun_out; mkdir -p $OUT; cd $R
-nproc > $OUT/r05_j_nproc.txt; timeout 600 python bench.py --docs 200000000 --no-cpu-baseline --no-traffic --steps 5 --warmup 2 > $OUT/r05_j_bench.json 2> $OUT/r05_j_bench.log
+nproc > $OUT/r05_j_nproc.txt; timeout 600 python bench.py --full --docs 200000000 --no-cpu-baseline --no-traffic --steps 5 --warmup 2 > $OUT/r05_j_bench.json 2> $OUT/r05_j_bench.log
 tail -5 $OUT/r05_j_bench.log
 python - <<'PY'
 import json
