@@ -416,6 +416,16 @@ struct PgQueryPlan {
   int32_t mvg_has_entries;          // pg_mv_aggr_*: an accumulator reads the entries' values (else only their number)
   int32_t mvg_dict_card;            // ... and the entries' dictionary (<= 4 096 values) is copied into LDS behind the table; 0: gathered from global memory
   int32_t p2_no_pack;               // PG_P2_NO_PACK (measurement knob): COUNT and SUM keep an LDS atomic each in pg_p2_aggregate_*s
+  // pg_fast_i32range_s / _st (pg_kernels_spec.hip): narrow images of the raw INT scan column scans[fast_scan] and of the value column
+  // srcs[pipe_src] (pg_segment.cpp, narrow_image: value - int_min in 8 / 16 / 24 bits, byte planes per wave tile, host byte order).  Appended so
+  // that every other kernel sees the argument layout it was tuned on.  spec_sbits / spec_vbits: 32 (or 0: a plan that never had them set) = the
+  // raw big-endian column, else the width of the image the loaders stream; patched per execution (pg_exec.hip), like the pointers.
+  int32_t spec_sbits, spec_vbits;
+  const uint8_t* spec_simg;         // the scan column's image (spec_sbits < 32)
+  const uint8_t* spec_vimg;         // the value column's image (spec_vbits < 32)
+  uint32_t spec_slo, spec_sspan;    // the range over the STORED scan values, clamped to the column's range on the host: (stored - spec_slo) <= spec_sspan
+  int32_t spec_sempty;              // ... or no stored value passes (the range misses the column's range, or hi < lo)
+  int32_t spec_vmin;                // value = stored + spec_vmin (the value column's smallest value)
 };
 
 #if defined(__HIPCC__)

@@ -482,6 +482,25 @@ static int pinned_spec_shape(const CompiledPlan& P, int agg_mode) {
   return 0;   // not pinned: the pipelined kernels
 }
 static bool uses_spec_kernel(const CompiledPlan& P, int agg_mode) { return pinned_spec_shape(P, agg_mode) != 0; }
+// The layouts pg_fast_i32range_s / _st stream in THIS execution (shape 1 / 5): the narrow image of the scan column and of the value column where
+// the plan names the column (pg_plan.cpp), PG_NO_NARROW_IMAGE is not set at this moment and the image exists or can be built now; the raw
+// column otherwise, column by column.  Returns the bytes of forward index the images save the kernel (pg_exec_stats.algorithmic_bytes reports
+// what the executed kernel streamed).
+static int64_t spec_images(Segment& seg, const CompiledPlan& P, PgQueryPlan& D, int shape) {
+  D.spec_sbits = D.spec_vbits = 32;
+  D.spec_simg = D.spec_vimg = nullptr;
+  if ((shape != 1 && shape != 5) || knobs().no_narrow_image) return 0;
+  int64_t saved = 0;
+  auto image_of = [&](Column* c, int32_t* bits, const uint8_t** img) {
+    if (!c || !narrow_image(seg, *c)) return;
+    *bits = c->img_bits;
+    *img = c->img_dev.as<uint8_t>();
+    saved += (int64_t)c->fwd_bytes_logical - ((int64_t)seg.total_docs * c->img_bits + 7) / 8;
+  };
+  image_of(P.spec_scan_col, &D.spec_sbits, &D.spec_simg);
+  image_of(P.spec_val_col, &D.spec_vbits, &D.spec_vimg);
+  return saved;
+}
 
 extern "C" void pg_trim_launch(const PgTrimArgs* args, int grid, hipStream_t stream);
 extern "C" void pg_distinct_launch_keys(const PgDistinctArgs* args, int mode, int grid, hipStream_t stream);   // pg_kernels_distinct.hip
@@ -868,6 +887,7 @@ struct HostTable {
   std::vector<int64_t> hash_keys;        // PG_AGG_RADIX_HASH: raw key of every group of the compact table
   int64_t full_scan_entries = 0;
   int64_t total_docs = 0;
+  int64_t image_saved_bytes = 0;         // forward-index bytes the executed kernel did not stream: it read narrow images (spec_images)
   // numGroupsLimit decided by a prefix pass (execute_limit_by_prefix): the first matching docId of every group that occurs in the prefix
   // (INT64_MAX elsewhere) and the limit itself — the plan that filled `table` carries neither
   const int64_t* admit_first = nullptr;
@@ -1982,6 +2002,7 @@ static std::unique_ptr<Result> execute_query_impl(Segment& seg, const pg_query& 
   if (oct_lds) split_shift = 0;
   D.tile_split_shift = split_shift;
   t_spec_pin = {&P, D.agg_mode, spec_shape(P, D.agg_mode)};   // (cleared when the query has been submitted: the plan may die before this thread's next query)
+  const int64_t image_saved_bytes = spec_images(seg, P, D, t_spec_pin.shape);
   LaunchShape shape = launch_shape(P, D.n_wtiles << split_shift, D.agg_mode);
   if (oct_lds) shape = {std::max(1, std::min((D.n_wtiles + PG_WAVES_PER_BLOCK - 1) / PG_WAVES_PER_BLOCK, num_cus())), PG_BLOCK, (D.oct_dword ? (size_t)D.aux[0].lds_offset + (size_t)D.aux[0].rep_bytes * 4 : P.lds_bytes) + 64};
   const int64_t n_out = (int64_t)D.n_ops * D.n_groups;
@@ -2659,6 +2680,7 @@ static std::unique_ptr<Result> execute_query_impl(Segment& seg, const pg_query& 
   H.hash_keys = std::move(hash_keys_host);
   H.full_scan_entries = P.full_scan_entries;
   H.total_docs = seg.total_docs;
+  H.image_saved_bytes = image_saved_bytes;
   if (opt.admit) { H.admit_first = opt.admit->first; H.admit_limit = opt.admit->limit; }
   if (opt.admit_on_device > 0) H.admit_limit = opt.admit_on_device;   // (the rows that came back ARE the admitted groups)
   if (opt.prefix_groups_out) {   // the caller wanted the count only
@@ -2775,6 +2797,7 @@ static void assemble_result(Result& res, const CompiledPlan& P, int32_t n_group_
   double ta1 = 0, ta2 = 0;
   const pg_exec_stats keep = res.stats;   // timings / kernel name survive a re-assembly after a merge
   fill_stats(res.stats, P, H.full_scan_entries, H.total_docs, H.stats);
+  res.stats.algorithmic_bytes -= H.image_saved_bytes;
   if ((P.dev.pipe_fit || P.dev.pipe_general) && H.total_docs > 0) {   // (see spec_shape)
     int64_t cand = 0;
     for (int i = 1; i < P.n_stat_slots; i++) cand += (int64_t)H.stats[i];

@@ -103,6 +103,12 @@ struct Column {
   uint64_t max_abs_int = 0;                     // LONG: largest |value|
   bool has_int_range = false;                   // raw INT / LONG: smallest and largest value (tuple packing of the partition pipeline)
   int64_t int_min = 0, int_max = 0;
+  // narrow image of a single-value raw INT column whose range needs <= 24 bits (pg_segment.cpp, narrow_image): value - int_min in img_bits
+  // (8 / 16 / 24) bits, byte planes per wave tile, beside fwd_dev; built on the device at first use by pg_fast_i32range_s / _st, under the
+  // segment's lock.  img_state: 0 not tried, 1 built, 2 not to be had (not eligible, or no memory: the plans keep the raw layout)
+  DeviceBuffer img_dev;
+  int32_t img_bits = 0;
+  int32_t img_state = 0;
   bool dict_affine = false;                     // INT / LONG dictionary whose values are base + step x dictId (ids, dense enumerations)
   int64_t dict_base = 0, dict_step = 0;
   uint64_t dict_hash = 0;                       // FNV-1a of the dictionary bytes: tables merge element-wise only over equal dictionaries
@@ -294,6 +300,10 @@ struct CompiledPlan {
   bool match_all = false;            // the filter is MatchAllFilterOperator: no filter pass in front of the partition pipeline
   int32_t n_projected_columns = 0;
   int64_t algorithmic_bytes = 0;
+  // pg_fast_i32range_s / _st: the raw INT scan column and the value column where their ranges allow a narrow image (Column::img_dev), else null;
+  // the executor asks for the images when it launches that kernel (narrow_image) and falls back to the raw layout column by column
+  Column* spec_scan_col = nullptr;
+  Column* spec_val_col = nullptr;
   // aggregation
   std::vector<AggOut> aggs;
   std::vector<Column*> group_cols;
@@ -512,6 +522,7 @@ struct Knobs {
   // executor (pg_exec.hip)
   bool force_interpreter = false, no_scan_pipe = false, no_pipe = false, no_dense_fused = false, no_part_grid_clamp = false, no_spin_wait = false;
   bool trace_oct = false, no_tile_split = false, no_oct_exec = false, no_p2_simple = false, no_dense_count = false, no_direct_result = false, trace_host = false, no_limit_prefix = false, no_device_trim = false, no_fused_finish = false;
+  bool no_narrow_image = false;   // PG_NO_NARROW_IMAGE: pg_fast_i32range_s / _st stream the raw columns also where a narrow image could be had
   bool wave_specialised = false, no_wave_specialised = false;   // PG_WAVE_SPECIALISED: pg_fast_i32range_s whatever the filter lets through; PG_NO_WAVE_SPECIALISED: never
   int wave_specialised_min_permille = 150;                     // PG_WAVE_SPECIALISED_MIN_PERMILLE: ... by default from this candidate rate on (profiles/r05_wave_specialised.txt)
   int max_inflight = 16;   // PG_MAX_INFLIGHT: queries between submission and result per device (<= 0: unbounded)
@@ -527,4 +538,8 @@ struct Knobs {
 };
 const Knobs& knobs();
 void knobs_reload();
+// The narrow image of `c` (see Column::img_dev), built on the first call; false: the column has none (then it never will).  Takes seg.mu.
+bool narrow_image_eligible(const Column& c);
+bool narrow_image(Segment& seg, Column& c);
+inline int64_t narrow_image_tile_bytes(int bits) { return (int64_t)(PG_WAVE_DOCS / 8) * bits; }
 }  // namespace pg

@@ -2228,6 +2228,29 @@ static std::shared_ptr<CompiledPlan> compile_in_space(Segment& seg, OpPtr root_o
       D.pipe_vscan = -1;
     }
   }
+  // pg_fast_i32range_s / _st can stream a narrow image of the scan column and of the value column in place of the raw columns (pg_kernels_spec.hip;
+  // Column::img_dev).  Which columns qualify, the scan's bounds over the STORED values (value - int_min) and the value column's minimum are plan
+  // facts and set here; the images are built, and the widths and pointers patched in, when the executor first launches that kernel (pg_exec.hip,
+  // spec_images: it follows PG_NO_NARROW_IMAGE and the outcome of the allocation, column by column).
+  D.spec_sbits = D.spec_vbits = 32;
+  const bool spec_headline = D.pipe_fit || (D.pipe_general && D.pipe_has_index && D.pipe_has_scan && D.pipe_tail != nullptr && D.pipe_vscan < 0);
+  if (spec_headline && star_index < 0 && D.fast_scan >= 0 && D.pipe_src >= 0) {
+    const PgScanLeaf& S = em.scans[(size_t)D.fast_scan];
+    for (Column* c : em.scanned_cols)
+      if (c->fwd_dev.as<uint8_t>() == S.data && narrow_image_eligible(*c) && S.pred_kind == PG_P_RANGE) {
+        P.spec_scan_col = c;
+        // bounds clamped to the column's range: an all-true range tests 0 <= stored <= int_max - int_min, a range that misses the column is empty
+        const int64_t lo = std::max<int64_t>(S.lo, c->int_min), hi = std::min<int64_t>(S.hi, c->int_max);
+        D.spec_sempty = hi < lo ? 1 : 0;
+        D.spec_slo = hi < lo ? 0u : (uint32_t)(lo - c->int_min);
+        D.spec_sspan = hi < lo ? 0u : (uint32_t)(hi - lo);
+      }
+    Column* v = srcs[(size_t)D.pipe_src];
+    if (v->fwd_dev.as<uint8_t>() == D.srcs[D.pipe_src].data && narrow_image_eligible(*v)) {
+      P.spec_val_col = v;
+      D.spec_vmin = (int32_t)v->int_min;
+    }
+  }
   // The candidate rate of the index program is known at plan time — posting cardinalities are exact, an AND over columns multiplies them (the
   // reference orders an AND's children by the same numbers, AndDocIdSet.java:110) — so a plan's FIRST execution already takes the kernel its
   // filter calls for (pg_fast_i32range_s streams everything, _p skips quads without candidates: pg_exec.hip, spec_shape); later executions

@@ -70,6 +70,42 @@ extern "C" __global__ void __launch_bounds__(256) pg_column_int_range_kernel(con
   }
 }
 
+// Narrow image of a raw INT column (Column::img_dev; read by the loaders of pg_fast_i32range_s / _st, pg_kernels_spec.hip): per wave tile of
+// 2 048 docs, at tile x 256 x bits bytes, the docs' stored = value - min in host byte order as byte planes.  The tile is cut into four blocks
+// b of 512 docs: lane l of block b owns quad (b, l) = docs 4 (64 b + l) .. + 3 and quad (4 + b, l).  16-bit plane (bits >= 16), 1 KB per block at
+// b x 1024: 16 bytes per lane, the low halves of its eight docs in doc order.  Byte plane (bits 8 and 24), 512 bytes per block behind the
+// 16-bit plane: 8 bytes per lane, bits 16 .. 23 (bits = 8: bits 0 .. 7) of the same docs.  One thread per (tile, block, lane): two 16-byte
+// reads of the column, both coalesced 1 KB rows, one 16-byte and / or one 8-byte write.  Docs of the padding behind the segment's last doc
+// hold whatever the column's padding gives, cut to the width: no kernel consumes them.
+extern "C" __global__ void __launch_bounds__(256) pg_column_narrow_image_kernel(const uint8_t* __restrict__ data, uint8_t* __restrict__ img,
+                                                                                int64_t n_wtiles, int32_t vmin, int bits) {
+  const int64_t n = n_wtiles * 256;
+  const int64_t tile_bytes = (int64_t)(PG_WAVE_DOCS / 8) * bits;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t wt = i >> 8;
+    const int b = (int)(i >> 6) & 3, l = (int)i & 63;
+    const uint4 qa = *reinterpret_cast<const uint4*>(data + wt * (PG_WAVE_DOCS * 4) + (int64_t)b * 1024 + l * 16);
+    const uint4 qb = *reinterpret_cast<const uint4*>(data + wt * (PG_WAVE_DOCS * 4) + (int64_t)(4 + b) * 1024 + l * 16);
+    const uint32_t raw[8] = {qa.x, qa.y, qa.z, qa.w, qb.x, qb.y, qb.z, qb.w};
+    uint32_t s[8];
+    for (int e = 0; e < 8; e++) s[e] = (__builtin_bswap32(raw[e]) - (uint32_t)vmin) & (bits == 24 ? 0xFFFFFFu : (bits == 16 ? 0xFFFFu : 0xFFu));
+    uint8_t* tile = img + wt * tile_bytes;
+    if (bits >= 16) {
+      uint4 lo;
+      lo.x = (s[0] & 0xFFFFu) | (s[1] << 16); lo.y = (s[2] & 0xFFFFu) | (s[3] << 16);
+      lo.z = (s[4] & 0xFFFFu) | (s[5] << 16); lo.w = (s[6] & 0xFFFFu) | (s[7] << 16);
+      *reinterpret_cast<uint4*>(tile + (int64_t)b * 1024 + l * 16) = lo;
+    }
+    if (bits != 16) {
+      const int sh = bits == 24 ? 16 : 0;
+      uint2 hi;
+      hi.x = ((s[0] >> sh) & 0xFFu) | (((s[1] >> sh) & 0xFFu) << 8) | (((s[2] >> sh) & 0xFFu) << 16) | (((s[3] >> sh) & 0xFFu) << 24);
+      hi.y = ((s[4] >> sh) & 0xFFu) | (((s[5] >> sh) & 0xFFu) << 8) | (((s[6] >> sh) & 0xFFu) << 16) | (((s[7] >> sh) & 0xFFu) << 24);
+      *reinterpret_cast<uint2*>(tile + (bits == 24 ? 4096 : 0) + (int64_t)b * 512 + l * 8) = hi;
+    }
+  }
+}
+
 // Largest dictId of a bit-packed forward index (PinotDataBitSet layout: value i at bit i x bits, most significant bit first).  A forward
 // index whose width leaves room above the cardinality (7 bits, 100 values) can HOLD dictIds the dictionary does not have — a corrupt or
 // mismatched file; the reference would throw ArrayIndexOutOfBoundsException on the first such doc, the kernels here would index past a
@@ -955,6 +991,40 @@ void segment_add_column(Segment& seg, const pg_column_desc& d) {
 
   seg.device_bytes += c.fwd_dev.size + c.dict_dev.size + c.containers_dev.size + c.descs_dev.size + c.mv_offsets_dev.size + c.vb_offsets_dev.size;
   seg.columns.emplace(c.name, std::move(col));
+}
+
+// Which columns can have a narrow image: single-value raw INT columns whose values span less than 2^24.  The width is whole bytes: the
+// loaders turn a byte plane into docs with one permute per doc; an exact bit width (20 for the headline's columns) would need the consumers
+// relieved first (profiles/narrow_image_headline.txt).
+bool narrow_image_eligible(const Column& c) {
+  return !c.has_dictionary && !c.is_mv && !c.raw_mv && c.col_kind == PG_COL_RAW32 && c.val_type == PG_V_I32 && c.has_int_range &&
+         c.int_max - c.int_min < ((int64_t)1 << 24);
+}
+
+bool narrow_image(Segment& seg, Column& c) {
+  std::lock_guard<std::mutex> g(seg.mu);
+  if (c.img_state != 0) return c.img_state == 1;
+  c.img_state = 2;
+  const int64_t n_wtiles = (int64_t)seg.n_tiles * PG_WTILES_PER_TILE;
+  if (!narrow_image_eligible(c) || n_wtiles <= 0 || c.fwd_dev.size < (size_t)n_wtiles * (PG_WAVE_DOCS * 4)) return false;
+  const int64_t span = c.int_max - c.int_min;
+  const int bits = span < 256 ? 8 : (span < 65536 ? 16 : 24);
+  void* ptr = nullptr;
+  const size_t bytes = (size_t)(n_wtiles * narrow_image_tile_bytes(bits));
+  if (hipMalloc(&ptr, bytes) != hipSuccess) {   // no room for it: the plans keep the raw layout, which is not an error
+    (void)hipGetLastError();
+    return false;
+  }
+  c.img_dev.ptr = ptr; c.img_dev.size = bytes; c.img_dev.device = seg.device;
+  const int grid = (int)std::min<int64_t>((n_wtiles * 256 + 255) / 256, 8192);
+  hipLaunchKernelGGL(pg_column_narrow_image_kernel, dim3(grid), dim3(256), 0, 0, c.fwd_dev.as<uint8_t>(), c.img_dev.as<uint8_t>(), n_wtiles,
+                     (int32_t)c.int_min, bits);
+  PG_HIP(hipGetLastError());
+  PG_HIP(hipDeviceSynchronize());
+  c.img_bits = bits;
+  c.img_state = 1;
+  seg.device_bytes += bytes;
+  return true;
 }
 
 }  // namespace pg
