@@ -368,27 +368,19 @@ int default_device() {
 static int num_cus() { return g_devices[t_device].num_cus; }
 static size_t lds_per_cu() { return g_devices[t_device].lds_per_cu; }
 
-static bool uses_fast_kernel(const CompiledPlan& P, int agg_mode) {
-  const bool force_interpreter = knobs().force_interpreter;   // measurement knob
-  if (force_interpreter || P.dev.mv) return false;   // multi-value plans: pg_mv_query_* (the interpreter's frame)
+// The fast kernels' frame (16-wavefront workgroups) against the interpreter's: every knob read below comes from the one snapshot `K` an
+// execution takes (knobs_reload may publish another at any moment)
+static bool uses_fast_kernel(const CompiledPlan& P, int agg_mode, const Knobs& K) {
+  if (K.force_interpreter || P.dev.mv) return false;   // (measurement knob); multi-value plans: pg_mv_query_* (the interpreter's frame)
   const bool agg = agg_mode != PG_AGG_NONE;
   return P.fast_filter != -2 && (!agg || ((P.fast_agg || P.wide_agg) && agg_mode != PG_AGG_GLOBAL));
 }
 
-// pg_mv_group_* (pg_kernels_mvg.hip): GROUP BY one multi-value column, decided at plan time (PgQueryPlan::mvg)
-static bool uses_mvg(const CompiledPlan& P, int agg_mode) { return P.dev.mv && P.dev.mvg && agg_mode == PG_AGG_LDS && !knobs().no_mvg; }
-// pg_fast_i32range_fp (double-buffered raw-INT range scan over the whole segment, filter only: pg_kernels_scan.hip)
-static bool uses_scan_kernel(const CompiledPlan& P, int agg_mode) {
-  const bool no_scan = knobs().no_scan_pipe;   // measurement knob
-  return !no_scan && agg_mode == PG_AGG_NONE && uses_fast_kernel(P, agg_mode) && P.fast_filter == 4 && P.dev.n_index_instr == 0 &&
-         P.dev.fast_scan_pushed;
-}
 // pg_nogroup_s1 / _s2 (pg_kernels_scan.hip): no GROUP BY, no filter, integer accumulators over one or two raw INT columns — streamed with the
 // accumulators in registers; returns the number of columns (0: another kernel)
-static int uses_nogroup_stream(const CompiledPlan& P, int agg_mode) {
+static int nogroup_stream_cols(const CompiledPlan& P) {
   const PgQueryPlan& D = P.dev;
-  if (knobs().no_scan_pipe || agg_mode != PG_AGG_SINGLE || !uses_fast_kernel(P, agg_mode) || P.fast_filter != -1 || D.n_index_instr != 0 || D.tail_posting >= 0 ||
-      D.n_group_cols != 0 || D.n_groups != 1 || D.n_aux != 0 || D.n_ops <= 0 || D.n_ops > PG_MAX_OPS)
+  if (P.fast_filter != -1 || D.n_index_instr != 0 || D.tail_posting >= 0 || D.n_group_cols != 0 || D.n_groups != 1 || D.n_aux != 0 || D.n_ops <= 0 || D.n_ops > PG_MAX_OPS)
     return 0;
   int a = -1, b = -1;
   for (int o = 0; o < D.n_ops; o++) {
@@ -402,47 +394,31 @@ static int uses_nogroup_stream(const CompiledPlan& P, int agg_mode) {
   }
   return a < 0 ? 0 : (b < 0 ? 1 : 2);
 }
-// pg_nogroup_da / _dg (pg_kernels_scan.hip): the same over one dictionary-encoded INT column — decided at plan time (PgQueryPlan::nogroup_d)
-static bool uses_nogroup_dict(const CompiledPlan& P, int agg_mode) {
-  return P.dev.nogroup_d != 0 && agg_mode == PG_AGG_SINGLE && uses_fast_kernel(P, agg_mode) && !knobs().no_scan_pipe;
+// distinct dense posting slots of the index program (the planner pads the eight slots with repeats of slot 0)
+static int dense_slots(const PgQueryPlan& D) {
+  int n = 1;
+  for (int j = 1; j < 8; j++) if (D.dense_ptr[j] != D.dense_ptr[0] || D.dense_group[j] != D.dense_group[0]) n = j + 1;
+  return n;
 }
-// pg_dictrange_fo (pg_kernels_scan.hip): filter only, [index program AND] one dictId-interval scan — decided at plan time (PgQueryPlan::dict_filter_only)
-static bool uses_dict_filter_only(const CompiledPlan& P, int agg_mode) {
-  return P.dev.dict_filter_only != 0 && agg_mode == PG_AGG_NONE && uses_fast_kernel(P, agg_mode) && !knobs().no_scan_pipe;
-}
-// pg_fast_dictrange_s family (pg_kernels_specd.hip): the loader / consumer frame over dictionary-encoded scan / value columns — decided at plan
-// time (PgQueryPlan::specd), whatever the filter lets through
-static bool uses_specd(const CompiledPlan& P, int agg_mode) {
-  return P.dev.specd && (agg_mode == PG_AGG_LDS || (agg_mode == PG_AGG_SINGLE && P.dev.n_group_cols == 0)) && uses_fast_kernel(P, agg_mode) && P.fast_agg && !P.wide_agg && !knobs().no_specd;
-}
+// pg_fast_dictrange_s family (pg_kernels_specd.hip): a private strip of LDS per wavefront
 static size_t specd_stage_bytes(const CompiledPlan& P) {
   return ((size_t)pg_specd_stage_bytes(P.dev.specd_sbits, P.dev.specd_vbits, P.dev.n_group_cols > 0 ? P.dev.gcols[0].bits : 0, P.dev.n_group_cols > 1 ? P.dev.gcols[1].bits : 0, P.dev.specd_dma ? 2 : 1) + 15) & ~(size_t)15;
 }
 // ... in the shared-stage frame (PgQueryPlan::specd == 2, pg_kernels_specw.hip): two stage buffers + one selection list per wavefront
-static bool uses_specw(const CompiledPlan& P, int agg_mode) { return uses_specd(P, agg_mode) && P.dev.specd == 2; }
 static size_t specw_stage_bytes(const CompiledPlan& P) {
-  int n_bm = 0;
-  if (P.dev.pipe_has_index) {
-    n_bm = 8;
-    while (n_bm > 1 && P.dev.dense_ptr[n_bm - 1] == P.dev.dense_ptr[0] && P.dev.dense_group[n_bm - 1] == P.dev.dense_group[0]) n_bm--;
-  }
-  if (P.dev.pipe_tail != nullptr) n_bm++;
+  const int n_bm = (P.dev.pipe_has_index ? dense_slots(P.dev) : 0) + (P.dev.pipe_tail != nullptr ? 1 : 0);
   return 2 * (size_t)pg_specw_stage_bytes(P.dev.specd_sbits, P.dev.specd_vbits, P.dev.gcols[0].bits, P.dev.n_group_cols > 1 ? P.dev.gcols[1].bits : 0, n_bm) + (size_t)pg_specw_list_bytes() + 16;
 }
-// pg_fast_i32range_p (software-pipelined headline shape, pg_kernels_pipe.hip): its own workgroup size
-static bool uses_pipe_general(const CompiledPlan& P, int agg_mode) {   // pg_pipe_*: the pipeline's other filter shapes
-  const bool no_pipe = knobs().no_pipe;   // measurement knob
-  return !no_pipe && uses_fast_kernel(P, agg_mode) && agg_mode == PG_AGG_LDS && !P.wide_agg && P.fast_agg && P.dev.pipe_general;
-}
-static bool uses_pipe_wide(const CompiledPlan& P, int agg_mode) {   // pg_pipe_w_*: raw LONG values / group columns of 9 .. 16 bits
-  const bool no_pipe = knobs().no_pipe;   // measurement knob
-  return !no_pipe && uses_fast_kernel(P, agg_mode) && (agg_mode == PG_AGG_LDS || agg_mode == PG_AGG_SINGLE) && P.wide_agg && P.dev.pipe_wide;
-}
-static bool uses_pipe_kernel(const CompiledPlan& P, int agg_mode) {
-  const bool no_pipe = knobs().no_pipe || knobs().no_dense_fused;   // measurement knobs
-  if (uses_pipe_general(P, agg_mode) || uses_pipe_wide(P, agg_mode)) return true;
-  return !no_pipe && uses_fast_kernel(P, agg_mode) && agg_mode == PG_AGG_LDS && !P.wide_agg && P.fast_agg && P.fast_filter == 4 &&
-         P.dev.dense_fused && P.dev.pipe_fit;
+// The software-pipelined kernels (pg_kernels_pipe.hip, their own workgroup size) a plan takes in `agg_mode`: pg_pipe_w* (raw LONG values /
+// group columns of 9 .. 16 bits), pg_pipe_* (the pipeline's other filter shapes) or pg_fast_i32range_p (the headline shape).  Wide needs
+// wide_agg, the other two !wide_agg; a plan that is both general and headline is general.
+enum PipeFamily { PIPE_NO = 0, PIPE_HEADLINE, PIPE_GENERAL, PIPE_WIDE };
+static PipeFamily pipe_family(const CompiledPlan& P, int agg_mode, const Knobs& K) {
+  if (K.no_pipe || !uses_fast_kernel(P, agg_mode, K)) return PIPE_NO;   // (measurement knob)
+  if ((agg_mode == PG_AGG_LDS || agg_mode == PG_AGG_SINGLE) && P.wide_agg && P.dev.pipe_wide) return PIPE_WIDE;
+  if (agg_mode != PG_AGG_LDS || P.wide_agg || !P.fast_agg) return PIPE_NO;
+  if (P.dev.pipe_general) return PIPE_GENERAL;
+  return !K.no_dense_fused && P.fast_filter == 4 && P.dev.dense_fused && P.dev.pipe_fit ? PIPE_HEADLINE : PIPE_NO;
 }
 
 // pg_fast_i32range_s (pg_kernels_spec.hip): the same plans as pg_fast_i32range_p with loader / consumer wavefronts — PG_WAVE_SPECIALISED only
@@ -453,13 +429,15 @@ static size_t spec_stage_bytes(const CompiledPlan& P) {
 // index).  It streams every column whole (84-92 % of 8 TB/s whatever the filter); the pipelined kernels request only the quads that hold a
 // candidate / a match and win where the filter is selective — so the candidate rate the plan's LAST execution counted decides (a plan's first
 // execution takes the pipelined kernel): >= 15 % candidates behind the index.  The general shapes: only when forced (below).
-static int spec_shape(const CompiledPlan& P, int agg_mode) {   // 0: no; 1 index + scan; 2 none; 3 scan; 4 index; 5 index + scan + upsert snapshot
-  if (knobs().no_wave_specialised || !uses_pipe_kernel(P, agg_mode) || uses_pipe_wide(P, agg_mode)) return 0;
+// The rates move under concurrent executions of the same plan, so an execution asks once and hands the answer to dispatch() and spec_images().
+static int spec_shape(const CompiledPlan& P, int agg_mode, const Knobs& K) {   // 0: no; 1 index + scan; 2 none; 3 scan; 4 index; 5 index + scan + upsert snapshot
+  const PipeFamily fam = pipe_family(P, agg_mode, K);
+  if (K.no_wave_specialised || fam == PIPE_NO || fam == PIPE_WIDE) return 0;
   if (P.dev.n_group_cols < 1 || P.dev.n_group_cols > 2 || P.lds_bytes + 256 + 2 * spec_stage_bytes(P) + 512 * (size_t)P.dev.n_ops > (size_t)160 * 1024 - 8192) return 0;   // (the dynamic-LDS limit device_init asks for)
-  const bool force = knobs().wave_specialised;
-  const int cand = P.observed_candidate_permille.load(std::memory_order_relaxed), match = P.observed_match_permille.load(std::memory_order_relaxed);
-  const int min_cand = knobs().wave_specialised_min_permille;
-  if (uses_pipe_general(P, agg_mode)) {
+  const bool force = K.wave_specialised;
+  const int cand = P.observed_candidate_permille.load(std::memory_order_relaxed);
+  const int min_cand = K.wave_specialised_min_permille;
+  if (fam == PIPE_GENERAL) {
     const bool idx = P.dev.pipe_has_index != 0, scan = P.dev.pipe_has_scan != 0;
     if (P.dev.pipe_vscan >= 0) return 0;
     if (idx && scan && P.dev.pipe_tail != nullptr) return force || cand >= min_cand ? 5 : 0;   // the headline shape behind an upsert snapshot (pg_pipe_index_scan_tail)
@@ -467,29 +445,19 @@ static int spec_shape(const CompiledPlan& P, int agg_mode) {   // 0: no; 1 index
     // Measured over 10^9 docs (profiles/r05_wave_specialised.txt): no filter 1.096 ms against pg_pipe_none's 0.926, a lone scan 1.394 = 1.394, index
     // only 1.017 against 0.918 — these shapes stream 5 - 9 bytes per doc and EVERY candidate matches, so the eight consumers' LDS atomics, not
     // the stream, are the long path.  Only when forced (tests, measurements).
-    (void)match;
     if (!force) return 0;
     return !idx && !scan ? 2 : (scan ? 3 : 4);
   }
   return force || cand >= min_cand ? 1 : 0;
 }
-// One decision per execution: the rates move under concurrent executions of the same plan, and the launch shape (12 wavefronts, stage buffers)
-// and the kernel must agree.  execute_query_plain pins it before it sizes the launch.
-struct SpecPin { const CompiledPlan* plan = nullptr; int agg_mode = 0, shape = 0; };
-static thread_local SpecPin t_spec_pin;
-static int pinned_spec_shape(const CompiledPlan& P, int agg_mode) {
-  if (t_spec_pin.plan == &P && t_spec_pin.agg_mode == agg_mode) return t_spec_pin.shape;
-  return 0;   // not pinned: the pipelined kernels
-}
-static bool uses_spec_kernel(const CompiledPlan& P, int agg_mode) { return pinned_spec_shape(P, agg_mode) != 0; }
 // The layouts pg_fast_i32range_s / _st stream in THIS execution (shape 1 / 5): the narrow image of the scan column and of the value column where
 // the plan names the column (pg_plan.cpp), PG_NO_NARROW_IMAGE is not set at this moment and the image exists or can be built now; the raw
 // column otherwise, column by column.  Returns the bytes of forward index the images save the kernel (pg_exec_stats.algorithmic_bytes reports
 // what the executed kernel streamed).
-static int64_t spec_images(Segment& seg, const CompiledPlan& P, PgQueryPlan& D, int shape) {
+static int64_t spec_images(Segment& seg, const CompiledPlan& P, PgQueryPlan& D, int shape, const Knobs& K) {
   D.spec_sbits = D.spec_vbits = 32;
   D.spec_simg = D.spec_vimg = nullptr;
-  if ((shape != 1 && shape != 5) || knobs().no_narrow_image) return 0;
+  if ((shape != 1 && shape != 5) || K.no_narrow_image) return 0;
   int64_t saved = 0;
   auto image_of = [&](Column* c, int32_t* bits, const uint8_t** img) {
     if (!c || !narrow_image(seg, *c)) return;
@@ -521,119 +489,6 @@ extern "C" hipError_t pg_select_sort_pairs(void* tmp, size_t* tmp_bytes, const u
 extern "C" void pg_trim_launch_keys(const PgTrimArgs* args, int grid, hipStream_t stream);
 extern "C" void pg_trim_launch_select(const PgTrimArgs* args, int grid, hipStream_t stream);
 typedef void (*QueryKernel)(const PgQueryPlan);
-static QueryKernel select_kernel(const CompiledPlan& P, int agg_mode, const char** name) {
-  const bool agg = agg_mode != PG_AGG_NONE;
-  if (uses_dict_filter_only(P, agg_mode)) { *name = "pg_dictrange_fo"; return pg_dictrange_fo; }
-  if (uses_nogroup_dict(P, agg_mode)) {
-    if (P.dev.nogroup_d == 1) { *name = "pg_nogroup_da"; return pg_nogroup_da; }
-    *name = P.dev.nogroup_lds_card > 0 ? "pg_nogroup_dl" : "pg_nogroup_dg";
-    return P.dev.nogroup_lds_card > 0 ? pg_nogroup_dl : pg_nogroup_dg;
-  }
-  if (const int ns = uses_nogroup_stream(P, agg_mode)) { *name = ns == 1 ? "pg_nogroup_s1" : "pg_nogroup_s2"; return ns == 1 ? pg_nogroup_s1 : pg_nogroup_s2; }
-  if (uses_fast_kernel(P, agg_mode)) {
-    if (agg && uses_pipe_wide(P, agg_mode)) {
-      // one kernel per value width (no value column / raw INT / raw LONG) and filter shape
-      static const struct { const char* name; QueryKernel fn; } kWide[4][4] = {
-          {{"pg_pipe_w0_none", pg_pipe_w0_none}, {"pg_pipe_w0_index", pg_pipe_w0_index}, {"pg_pipe_w0_scan", pg_pipe_w0_scan}, {"pg_pipe_w0_index_scan", pg_pipe_w0_index_scan}},
-          {{"pg_pipe_w32_none", pg_pipe_w32_none}, {"pg_pipe_w32_index", pg_pipe_w32_index}, {"pg_pipe_w32_scan", pg_pipe_w32_scan}, {"pg_pipe_w32_index_scan", pg_pipe_w32_index_scan}},
-          {{"pg_pipe_w64_none", pg_pipe_w64_none}, {"pg_pipe_w64_index", pg_pipe_w64_index}, {"pg_pipe_w64_scan", pg_pipe_w64_scan}, {"pg_pipe_w64_index_scan", pg_pipe_w64_index_scan}},
-          {{"pg_pipe_wd_none", pg_pipe_wd_none}, {"pg_pipe_wd_index", pg_pipe_wd_index}, {"pg_pipe_wd_scan", pg_pipe_wd_scan}, {"pg_pipe_wd_index_scan", pg_pipe_wd_index_scan}}};
-      const int vw = P.dev.pipe_src >= 0 ? P.dev.pipe_wide : 0;
-      const int shape = (P.dev.pipe_has_scan ? 2 : 0) + (P.dev.pipe_has_index ? 1 : 0);
-      *name = kWide[vw][shape].name;
-      return kWide[vw][shape].fn;
-    }
-    if (agg && P.wide_agg) {
-      if (P.fast_filter == -1) { *name = P.digit_ops ? "pg_fast_none_wd" : "pg_fast_none_w"; return P.digit_ops ? pg_fast_none_wd : pg_fast_none_w; }
-      *name = P.digit_ops ? "pg_fast_multi_wd" : "pg_fast_multi_w";
-      return P.digit_ops ? pg_fast_multi_wd : pg_fast_multi_w;
-    }
-    if (uses_specd(P, agg_mode)) {
-      // one kernel per value kind (raw INT / arithmetic dictionary / gathered dictionary) and filter shape
-      static const struct { const char* name; QueryKernel fn; } kSpecd[3][5] = {
-          {{"pg_specd_none_r", pg_specd_none_r}, {"pg_specd_index_r", pg_specd_index_r}, {"pg_specd_scan_r", pg_specd_scan_r}, {"pg_fast_dictrange_s_r", pg_fast_dictrange_s_r}, {"pg_fast_dictrange_st_r", pg_fast_dictrange_st_r}},
-          {{"pg_specd_none_a", pg_specd_none_a}, {"pg_specd_index_a", pg_specd_index_a}, {"pg_specd_scan_a", pg_specd_scan_a}, {"pg_fast_dictrange_s_a", pg_fast_dictrange_s_a}, {"pg_fast_dictrange_st_a", pg_fast_dictrange_st_a}},
-          {{"pg_specd_none_g", pg_specd_none_g}, {"pg_specd_index_g", pg_specd_index_g}, {"pg_specd_scan_g", pg_specd_scan_g}, {"pg_fast_dictrange_s_g", pg_fast_dictrange_s_g}, {"pg_fast_dictrange_st_g", pg_fast_dictrange_st_g}}};
-      const int shape = P.dev.pipe_tail != nullptr ? 4 : (P.dev.pipe_has_scan ? 2 : 0) + (P.dev.pipe_has_index ? 1 : 0);
-      if (P.dev.specd == 2) {
-        static const struct { const char* name; QueryKernel fn; } kSpecw[3][5] = {
-            {{"pg_specw_none_r", pg_specw_none_r}, {"pg_specw_index_r", pg_specw_index_r}, {"pg_specw_scan_r", pg_specw_scan_r}, {"pg_fast_dictrange_w_r", pg_fast_dictrange_w_r}, {"pg_fast_dictrange_wt_r", pg_fast_dictrange_wt_r}},
-            {{"pg_specw_none_a", pg_specw_none_a}, {"pg_specw_index_a", pg_specw_index_a}, {"pg_specw_scan_a", pg_specw_scan_a}, {"pg_fast_dictrange_w_a", pg_fast_dictrange_w_a}, {"pg_fast_dictrange_wt_a", pg_fast_dictrange_wt_a}},
-            {{"pg_specw_none_g", pg_specw_none_g}, {"pg_specw_index_g", pg_specw_index_g}, {"pg_specw_scan_g", pg_specw_scan_g}, {"pg_fast_dictrange_w_g", pg_fast_dictrange_w_g}, {"pg_fast_dictrange_wt_g", pg_fast_dictrange_wt_g}}};
-        *name = kSpecw[P.dev.specd_vkind - 1][shape].name;
-        return kSpecw[P.dev.specd_vkind - 1][shape].fn;
-      }
-      if (P.dev.specd_dma && shape == 3) {   // the headline shape's columns by LDS-DMA (two column areas per strip: the planner found room)
-        static const struct { const char* name; QueryKernel fn; } kDma[3] = {
-            {"pg_fast_dictrange_s_r_dma", pg_fast_dictrange_s_r_dma}, {"pg_fast_dictrange_s_a_dma", pg_fast_dictrange_s_a_dma}, {"pg_fast_dictrange_s_g_dma", pg_fast_dictrange_s_g_dma}};
-        *name = kDma[P.dev.specd_vkind - 1].name;
-        return kDma[P.dev.specd_vkind - 1].fn;
-      }
-      *name = kSpecd[P.dev.specd_vkind - 1][shape].name;
-      return kSpecd[P.dev.specd_vkind - 1][shape].fn;
-    }
-    const bool no_dense = knobs().no_dense_fused;   // measurement knob
-    switch (pinned_spec_shape(P, agg_mode)) {
-      case 1: *name = "pg_fast_i32range_s"; return pg_fast_i32range_s;
-      case 2: *name = "pg_spec_none"; return pg_spec_none;
-      case 3: *name = "pg_spec_scan"; return pg_spec_scan;
-      case 4: *name = "pg_spec_index"; return pg_spec_index;
-      case 5: *name = "pg_fast_i32range_st"; return pg_fast_i32range_st;
-      default: break;
-    }
-    if (uses_pipe_general(P, agg_mode)) {
-      const bool idx = P.dev.pipe_has_index != 0, scan = P.dev.pipe_has_scan != 0, tail = P.dev.pipe_tail != nullptr;
-      if (scan && P.dev.pipe_vscan >= 0) {
-        *name = idx ? "pg_pipe_index_scan_vscan" : "pg_pipe_scan_vscan";
-        return idx ? pg_pipe_index_scan_vscan : pg_pipe_scan_vscan;
-      }
-      if (scan) {
-        if (idx) { *name = "pg_pipe_index_scan_tail"; return pg_pipe_index_scan_tail; }   // (index + scan without a tail is pg_fast_i32range_p)
-        *name = tail ? "pg_pipe_scan_tail" : "pg_pipe_scan";
-        return tail ? pg_pipe_scan_tail : pg_pipe_scan;
-      }
-      if (idx) {
-        int n_ptr = 0;   // distinct dense posting pointers (the planner pads the eight slots with repeats of slot 0)
-        for (int j = 0; j < 8; j++) if (j == 0 || P.dev.dense_ptr[j] != P.dev.dense_ptr[0] || P.dev.dense_group[j] != P.dev.dense_group[0]) n_ptr = j + 1;
-        if (n_ptr <= 2) { *name = tail ? "pg_pipe_index2_tail" : "pg_pipe_index2"; return tail ? pg_pipe_index2_tail : pg_pipe_index2; }
-        *name = tail ? "pg_pipe_index_tail" : "pg_pipe_index";
-        return tail ? pg_pipe_index_tail : pg_pipe_index;
-      }
-      *name = tail ? "pg_pipe_tail" : "pg_pipe_none";
-      return tail ? pg_pipe_tail : pg_pipe_none;
-    }
-    if (uses_pipe_kernel(P, agg_mode)) { *name = "pg_fast_i32range_p"; return pg_fast_i32range_p; }
-    if (uses_scan_kernel(P, agg_mode)) { *name = "pg_fast_i32range_fp"; return pg_fast_i32range_fp; }
-    if (agg && P.fast_filter == 4 && P.dev.dense_fused && !no_dense && P.fast_agg && agg_mode == PG_AGG_LDS) { *name = "pg_fast_i32range_d"; return pg_fast_i32range_d; }
-    switch (P.fast_filter) {
-      case -1: *name = agg ? "pg_fast_none_a" : "pg_fast_none_f"; return agg ? pg_fast_none_a : pg_fast_none_f;
-      case 4: *name = agg ? "pg_fast_i32range_a" : "pg_fast_i32range_f"; return agg ? pg_fast_i32range_a : pg_fast_i32range_f;
-      case 0: *name = agg ? "pg_fast_dictrange_a" : "pg_fast_dictrange_f"; return agg ? pg_fast_dictrange_a : pg_fast_dictrange_f;
-      case 2: *name = agg ? "pg_fast_dictlut_a" : "pg_fast_dictlut_f"; return agg ? pg_fast_dictlut_a : pg_fast_dictlut_f;
-      case 100: *name = agg ? "pg_fast_multi_a" : "pg_fast_multi_f"; return agg ? pg_fast_multi_a : pg_fast_multi_f;
-      default: break;
-    }
-  }
-  if (P.dev.mv) {   // a multi-value column in the filter, the group key or an aggregation (pg_kernels_mv.hip)
-    if (uses_mvg(P, agg_mode)) {   // ... GROUP BY one multi-value column, no filter: its own kernel (pg_kernels_mvg.hip)
-      if (P.dev.mvg >= 16) {   // the *MV functions over one multi-value column, single-value keys
-        *name = P.dev.mvg == 20 ? "pg_mv_aggr_4" : "pg_mv_aggr_8";
-        return P.dev.mvg == 20 ? pg_mv_aggr_4 : pg_mv_aggr_8;
-      }
-      *name = P.dev.mvg == 4 ? "pg_mv_group_4" : "pg_mv_group_8";
-      return P.dev.mvg == 4 ? pg_mv_group_4 : pg_mv_group_8;
-    }
-    if (agg_mode == PG_AGG_NONE) { *name = "pg_mv_query_f"; return pg_mv_query_f; }
-    if (agg_mode == PG_AGG_GLOBAL) { *name = "pg_mv_query_g"; return pg_mv_query_g; }
-    *name = "pg_mv_query_l";
-    return pg_mv_query_l;
-  }
-  if (agg_mode == PG_AGG_NONE) { *name = "pg_generic_query_f"; return pg_generic_query_f; }
-  if (agg_mode == PG_AGG_GLOBAL) { *name = P.digit_ops ? "pg_generic_query_gd" : "pg_generic_query_g"; return P.digit_ops ? pg_generic_query_gd : pg_generic_query_g; }
-  *name = P.digit_ops ? "pg_generic_query_ld" : "pg_generic_query_l";
-  return P.digit_ops ? pg_generic_query_ld : pg_generic_query_l;
-}
-
 struct ThreadCtx {
   hipStream_t stream = nullptr;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -727,66 +582,187 @@ std::shared_ptr<CompiledPlan> get_plan(Segment& seg, const pg_filter_node* filte
   return plan;
 }
 
-struct LaunchShape { int grid; int block; size_t lds; };
-static LaunchShape launch_shape(const CompiledPlan& P, int n_wtiles, int agg_mode) {
-  size_t lds = P.lds_bytes + 64;
-  if (P.dev.agg_mode == PG_AGG_LDS_PART && agg_mode == PG_AGG_LDS_PART) {
-    // range-partitioned aggregation: one workgroup per CU, 8 x per_xcd of them with per_xcd a multiple of the range count
-    int per_xcd = std::max(num_cus() / 8, 1);
-    const int block = uses_fast_kernel(P, agg_mode) ? PG_BLOCK : PG_GENERIC_BLOCK;
+// ---- dispatch: which kernel runs an execution, under which name, with which grid, block and dynamic LDS --------------------------------------
+// One ladder, one branch per kernel family, and each branch decides the kernel and its launch together: the kernels index stage buffers in
+// dynamic LDS by the size their own family assumes, so a kernel never meets another family's shape.  Nothing here outlives the call.
+struct Kernel { const char* name; QueryKernel fn; };
+struct Dispatch {
+  QueryKernel fn;
+  const char* name;   // what pg_exec_stats.kernel reports
+  int grid, block;
+  size_t lds;
+  int spec;           // the wave-specialised shape that runs (spec_shape's answer where its kernels were taken, else 0): spec_images follows it
+};
+// `spec`: spec_shape(P, agg_mode, K) for the aggregating launch of an execution; 0 for a filter pass and every other PG_AGG_NONE launch
+static Dispatch dispatch(const CompiledPlan& P, int agg_mode, int n_wtiles, int spec, const Knobs& K = knobs()) {
+  const PgQueryPlan& D = P.dev;
+  const bool agg = agg_mode != PG_AGG_NONE, fast = uses_fast_kernel(P, agg_mode, K);
+  const size_t lds = P.lds_bytes + 64;
+  // workgroups of `waves` wavefronts over the wave tiles, at most `per_cu` per CU
+  auto tiles_grid = [&](int waves, int per_cu) { return std::max(1, std::min((n_wtiles + waves - 1) / waves, num_cus() * per_cu)); };
+  // PG_AGG_LDS_PART (range-partitioned aggregation) sets the grid of whichever kernel follows: one workgroup per CU, 8 x per_xcd of them with
+  // per_xcd a multiple of the range count.  It reaches the two frames below only — every other family asks for PG_AGG_NONE, _SINGLE or _LDS —
+  // and there pg_fast_none_w* / pg_fast_multi_w* (the planner gives these plans wide_agg, never fast_agg), pg_mv_query_l and pg_generic_query_l*.
+  const bool part = D.agg_mode == PG_AGG_LDS_PART && agg_mode == PG_AGG_LDS_PART;
+  auto part_grid = [&](int block) {
     // (a small doc space — a star-tree's pre-aggregated docs — does not need every CU: a workgroup without tiles still fills and flushes its table)
     const int chunks = (n_wtiles + block / 64 - 1) / (block / 64);
-    const bool no_clamp = knobs().no_part_grid_clamp;   // measurement knob
-    int per_range = std::max(per_xcd / P.dev.n_parts, 1);
-    if (!no_clamp) per_range = std::max(1, std::min(per_range, (chunks + 7) / 8));
-    return {8 * per_range * P.dev.n_parts, block, lds};
-  }
-  if (uses_scan_kernel(P, agg_mode) || uses_nogroup_stream(P, agg_mode) || uses_nogroup_dict(P, agg_mode) || uses_dict_filter_only(P, agg_mode)) {
-    // tuning knob; the dictId stream of pg_nogroup_d* is 1-3 bytes per doc — 5 KB per tile at 20 bits: two workgroups per CU keep as many bytes in
-    // flight as one does over a raw column (0.143 -> 0.102 ms per 2 x 10^8 docs; three to five: 0.105-0.112, profiles/r06_nogroup_stream.txt)
-    const size_t dict_lds = uses_nogroup_dict(P, agg_mode) && P.dev.nogroup_d == 2 ? (size_t)P.dev.nogroup_lds_card * 4 : 0;   // pg_nogroup_dl: the dictionary's copy
-    // pg_dictrange_fo waits for its posting dwords once per tile (the index program is not prefetched): four workgroups per CU hide that
-    // (two: 0.181 ms per 2 x 10^8 docs, four: 0.139, six: 0.151)
-    const int wgs_per_cu = knobs().scan_wgs_per_cu * (uses_dict_filter_only(P, agg_mode) ? 4 : ((uses_nogroup_dict(P, agg_mode) && 2 * (dict_lds + 4096) <= lds_per_cu()) ? 2 : 1));
+    int per_range = std::max(std::max(num_cus() / 8, 1) / D.n_parts, 1);
+    if (!K.no_part_grid_clamp) per_range = std::max(1, std::min(per_range, (chunks + 7) / 8));   // (measurement knob)
+    return 8 * per_range * D.n_parts;
+  };
+  // the fast kernels' frame: one 16-wavefront workgroup per CU (tuning knob); fewer when the segment has fewer wave tiles than that
+  auto fast_frame = [&](Kernel k) -> Dispatch {
+    if (part) return {k.fn, k.name, part_grid(PG_BLOCK), PG_BLOCK, lds, 0};
+    const int per_cu = ((size_t)K.wgs_per_cu * (lds + 4096) <= lds_per_cu()) ? K.wgs_per_cu : 1;
+    return {k.fn, k.name, tiles_grid(PG_WAVES_PER_BLOCK, per_cu), PG_BLOCK, lds, 0};
+  };
+  // the interpreter's frame (also pg_mv_query_*): 8-wavefront workgroups, two per CU when both LDS tables fit
+  auto generic_frame = [&](Kernel k) -> Dispatch {
+    if (part) return {k.fn, k.name, part_grid(PG_GENERIC_BLOCK), PG_GENERIC_BLOCK, lds, 0};
+    return {k.fn, k.name, tiles_grid(PG_GENERIC_BLOCK / 64, (2 * (lds + 4096) <= lds_per_cu()) ? 2 : 1), PG_GENERIC_BLOCK, lds, 0};
+  };
+  // the software-pipelined kernels' frame (pg_kernels_pipe.hip)
+  auto pipe_frame = [&](Kernel k) -> Dispatch {
+    const int per_cu = ((size_t)K.pipe_wgs_per_cu * (lds + 4096) <= lds_per_cu()) ? K.pipe_wgs_per_cu : 1;   // tuning knob
+    return {k.fn, k.name, tiles_grid(pg_pipe_waves_per_block, per_cu), pg_pipe_waves_per_block * 64, lds, 0};
+  };
+
+  if (fast && !K.no_scan_pipe && (agg_mode == PG_AGG_NONE || agg_mode == PG_AGG_SINGLE)) {
+    // ---- the streams of pg_kernels_scan.hip: registers only, but for pg_nogroup_dl's copy of the dictionary.  Filter only (PG_AGG_NONE) or no
+    //      GROUP BY (PG_AGG_SINGLE).  The PG_AGG_NONE ones may stand in front of every family below because none between here and the plain
+    //      fast kernels takes PG_AGG_NONE; the PG_AGG_SINGLE ones take precedence over wide pipe, wide and the dictionary family, which serve
+    //      plans without GROUP BY as well.
     const int waves = pg_scan_waves_per_block;
-    int grid = std::min((n_wtiles + waves - 1) / waves, num_cus() * std::max(wgs_per_cu, 1));
-    return {std::max(grid, 1), waves * 64, dict_lds};
+    auto stream_frame = [&](Kernel k, int wgs_factor, size_t dict_lds) -> Dispatch {
+      return {k.fn, k.name, tiles_grid(waves, std::max(K.scan_wgs_per_cu * wgs_factor, 1)), waves * 64, dict_lds, 0};   // tuning knob
+    };
+    // pg_dictrange_fo: [index program AND] one dictId-interval scan, decided at plan time.  It waits for its posting dwords once per tile (the
+    // index program is not prefetched): four workgroups per CU hide that (two: 0.181 ms per 2 x 10^8 docs, four: 0.139, six: 0.151)
+    if (!agg && D.dict_filter_only != 0) return stream_frame({"pg_dictrange_fo", pg_dictrange_fo}, 4, 0);
+    if (agg && D.nogroup_d != 0) {
+      // one dictionary-encoded INT column, decided at plan time.  The dictId stream is 1-3 bytes per doc — 5 KB per tile at 20 bits: two
+      // workgroups per CU keep as many bytes in flight as one does over a raw column (0.143 -> 0.102 ms per 2 x 10^8 docs; three to five:
+      // 0.105-0.112, profiles/r06_nogroup_stream.txt)
+      const size_t dict_lds = D.nogroup_d == 2 ? (size_t)D.nogroup_lds_card * 4 : 0;   // pg_nogroup_dl: the dictionary's copy
+      const Kernel k = D.nogroup_d == 1 ? Kernel{"pg_nogroup_da", pg_nogroup_da} : (D.nogroup_lds_card > 0 ? Kernel{"pg_nogroup_dl", pg_nogroup_dl} : Kernel{"pg_nogroup_dg", pg_nogroup_dg});
+      return stream_frame(k, 2 * (dict_lds + 4096) <= lds_per_cu() ? 2 : 1, dict_lds);
+    }
+    if (agg) {
+      if (const int ns = nogroup_stream_cols(P)) return stream_frame(ns == 1 ? Kernel{"pg_nogroup_s1", pg_nogroup_s1} : Kernel{"pg_nogroup_s2", pg_nogroup_s2}, 1, 0);
+    } else if (P.fast_filter == 4 && D.n_index_instr == 0 && D.fast_scan_pushed) {   // double-buffered raw-INT range scan over the whole segment
+      return stream_frame({"pg_fast_i32range_fp", pg_fast_i32range_fp}, 1, 0);
+    }
   }
-  if (uses_mvg(P, agg_mode))   // one 16-wavefront workgroup per CU; the table and a trash slot per lane and accumulator
-    return {std::max(1, std::min((n_wtiles + PG_WAVES_PER_BLOCK - 1) / PG_WAVES_PER_BLOCK, num_cus())), PG_BLOCK, lds + 64 + 512 * (size_t)P.dev.n_ops + (size_t)P.dev.mvg_dict_card * 4};
-  if (uses_specw(P, agg_mode)) {   // one workgroup per CU walking stages (waves x 512 docs) b, b + grid, ...; table + two stage buffers + the selection lists in LDS
-    const int waves = pg_specw_waves_per_block;
-    const int64_t stage_docs = (int64_t)waves * 512;
-    const int n_stages = (int)(((int64_t)P.dev.num_docs + stage_docs - 1) / stage_docs);
-    return {std::max(1, std::min(n_stages, num_cus() * std::max(1, 16 / waves))), waves * 64, lds + 64 + specw_stage_bytes(P) + 512 * (size_t)P.dev.n_ops};
+  if (fast) {
+    const PipeFamily fam = pipe_family(P, agg_mode, K);
+    const int filter_shape = (D.pipe_has_scan ? 2 : 0) + (D.pipe_has_index ? 1 : 0);
+    if (fam == PIPE_WIDE) {
+      // ---- wide pipe: one kernel per value width (no value column / raw INT / raw LONG) and filter shape
+      static const Kernel kWide[4][4] = {
+          {{"pg_pipe_w0_none", pg_pipe_w0_none}, {"pg_pipe_w0_index", pg_pipe_w0_index}, {"pg_pipe_w0_scan", pg_pipe_w0_scan}, {"pg_pipe_w0_index_scan", pg_pipe_w0_index_scan}},
+          {{"pg_pipe_w32_none", pg_pipe_w32_none}, {"pg_pipe_w32_index", pg_pipe_w32_index}, {"pg_pipe_w32_scan", pg_pipe_w32_scan}, {"pg_pipe_w32_index_scan", pg_pipe_w32_index_scan}},
+          {{"pg_pipe_w64_none", pg_pipe_w64_none}, {"pg_pipe_w64_index", pg_pipe_w64_index}, {"pg_pipe_w64_scan", pg_pipe_w64_scan}, {"pg_pipe_w64_index_scan", pg_pipe_w64_index_scan}},
+          {{"pg_pipe_wd_none", pg_pipe_wd_none}, {"pg_pipe_wd_index", pg_pipe_wd_index}, {"pg_pipe_wd_scan", pg_pipe_wd_scan}, {"pg_pipe_wd_index_scan", pg_pipe_wd_index_scan}}};
+      return pipe_frame(kWide[D.pipe_src >= 0 ? D.pipe_wide : 0][filter_shape]);
+    }
+    if (agg && P.wide_agg) {
+      // ---- wide (its order against the dictionary, wave-specialised and pipe families below is free: they all need !wide_agg)
+      if (P.fast_filter == -1) return fast_frame(P.digit_ops ? Kernel{"pg_fast_none_wd", pg_fast_none_wd} : Kernel{"pg_fast_none_w", pg_fast_none_w});
+      return fast_frame(P.digit_ops ? Kernel{"pg_fast_multi_wd", pg_fast_multi_wd} : Kernel{"pg_fast_multi_w", pg_fast_multi_w});
+    }
+    if (D.specd && (agg_mode == PG_AGG_LDS || (agg_mode == PG_AGG_SINGLE && D.n_group_cols == 0)) && P.fast_agg && !K.no_specd) {
+      // ---- pg_fast_dictrange_s family (pg_kernels_specd.hip): the loader / consumer frame over dictionary-encoded scan / value columns, decided at
+      //      plan time (PgQueryPlan::specd) whatever the filter lets through; one kernel per value kind (raw INT / arithmetic dictionary / gathered
+      //      dictionary) and filter shape.  (The planner sets specd only where neither pipe_fit nor pipe_general holds: such a plan has no `spec`.)
+      const int shape = D.pipe_tail != nullptr ? 4 : filter_shape, vkind = D.specd_vkind - 1;
+      if (D.specd == 2) {   // the shared-stage frame (pg_kernels_specw.hip): one workgroup per CU walking stages (waves x 512 docs) b, b + grid, ...; table + two stage buffers + the selection lists in LDS
+        static const Kernel kSpecw[3][5] = {
+            {{"pg_specw_none_r", pg_specw_none_r}, {"pg_specw_index_r", pg_specw_index_r}, {"pg_specw_scan_r", pg_specw_scan_r}, {"pg_fast_dictrange_w_r", pg_fast_dictrange_w_r}, {"pg_fast_dictrange_wt_r", pg_fast_dictrange_wt_r}},
+            {{"pg_specw_none_a", pg_specw_none_a}, {"pg_specw_index_a", pg_specw_index_a}, {"pg_specw_scan_a", pg_specw_scan_a}, {"pg_fast_dictrange_w_a", pg_fast_dictrange_w_a}, {"pg_fast_dictrange_wt_a", pg_fast_dictrange_wt_a}},
+            {{"pg_specw_none_g", pg_specw_none_g}, {"pg_specw_index_g", pg_specw_index_g}, {"pg_specw_scan_g", pg_specw_scan_g}, {"pg_fast_dictrange_w_g", pg_fast_dictrange_w_g}, {"pg_fast_dictrange_wt_g", pg_fast_dictrange_wt_g}}};
+        const int waves = pg_specw_waves_per_block;
+        const int64_t stage_docs = (int64_t)waves * 512;
+        const int n_stages = (int)(((int64_t)D.num_docs + stage_docs - 1) / stage_docs);
+        const Kernel& k = kSpecw[vkind][shape];
+        return {k.fn, k.name, std::max(1, std::min(n_stages, num_cus() * std::max(1, 16 / waves))), waves * 64, lds + 64 + specw_stage_bytes(P) + 512 * (size_t)D.n_ops, 0};
+      }
+      static const Kernel kSpecd[3][5] = {
+          {{"pg_specd_none_r", pg_specd_none_r}, {"pg_specd_index_r", pg_specd_index_r}, {"pg_specd_scan_r", pg_specd_scan_r}, {"pg_fast_dictrange_s_r", pg_fast_dictrange_s_r}, {"pg_fast_dictrange_st_r", pg_fast_dictrange_st_r}},
+          {{"pg_specd_none_a", pg_specd_none_a}, {"pg_specd_index_a", pg_specd_index_a}, {"pg_specd_scan_a", pg_specd_scan_a}, {"pg_fast_dictrange_s_a", pg_fast_dictrange_s_a}, {"pg_fast_dictrange_st_a", pg_fast_dictrange_st_a}},
+          {{"pg_specd_none_g", pg_specd_none_g}, {"pg_specd_index_g", pg_specd_index_g}, {"pg_specd_scan_g", pg_specd_scan_g}, {"pg_fast_dictrange_s_g", pg_fast_dictrange_s_g}, {"pg_fast_dictrange_st_g", pg_fast_dictrange_st_g}}};
+      // the headline shape's columns by LDS-DMA (two column areas per strip: the planner found room)
+      static const Kernel kDma[3] = {
+          {"pg_fast_dictrange_s_r_dma", pg_fast_dictrange_s_r_dma}, {"pg_fast_dictrange_s_a_dma", pg_fast_dictrange_s_a_dma}, {"pg_fast_dictrange_s_g_dma", pg_fast_dictrange_s_g_dma}};
+      // behind the table and its trash slots a private strip of LDS per wavefront; two workgroups per CU where their LDS fits
+      const int waves = pg_specd_waves_per_block;
+      const size_t need = lds + 64 + specd_stage_bytes(P) + 512 * (size_t)D.n_ops;
+      const int per_cu = K.specd_wgs_per_cu > 0 && (size_t)K.specd_wgs_per_cu * (need + 1024) <= lds_per_cu() ? K.specd_wgs_per_cu : 1;
+      const Kernel& k = D.specd_dma && shape == 3 ? kDma[vkind] : kSpecd[vkind][shape];
+      return {k.fn, k.name, tiles_grid(waves, per_cu), waves * 64, need, 0};
+    }
+    if (fam != PIPE_NO) {   // (PIPE_HEADLINE or PIPE_GENERAL: what spec_shape asks before it answers anything but 0)
+      if (spec != 0) {
+        // ---- wave-specialised (pg_kernels_spec.hip): one 12-wavefront workgroup per CU walking tiles b, b + grid, ...; table (+ 64 trash slots
+        //      per accumulator) + two stage buffers in LDS
+        static const Kernel kSpec[6] = {{nullptr, nullptr}, {"pg_fast_i32range_s", pg_fast_i32range_s}, {"pg_spec_none", pg_spec_none}, {"pg_spec_scan", pg_spec_scan},
+                                        {"pg_spec_index", pg_spec_index}, {"pg_fast_i32range_st", pg_fast_i32range_st}};
+        if (spec < 1 || spec > 5) fail(PG_ERR_INTERNAL, "wave-specialised shape %d", spec);
+        return {kSpec[spec].fn, kSpec[spec].name, std::max(1, std::min(n_wtiles, num_cus())), pg_spec_waves_per_block * 64, lds + 64 + 2 * spec_stage_bytes(P) + 512 * (size_t)D.n_ops, spec};
+      }
+      // ---- pipe: the headline shape (index + scan without a tail), else the pipeline's general shapes
+      if (fam == PIPE_HEADLINE) return pipe_frame({"pg_fast_i32range_p", pg_fast_i32range_p});
+      const bool idx = D.pipe_has_index != 0, scan = D.pipe_has_scan != 0, tail = D.pipe_tail != nullptr;
+      if (scan && D.pipe_vscan >= 0) return pipe_frame(idx ? Kernel{"pg_pipe_index_scan_vscan", pg_pipe_index_scan_vscan} : Kernel{"pg_pipe_scan_vscan", pg_pipe_scan_vscan});
+      if (scan && idx) return pipe_frame({"pg_pipe_index_scan_tail", pg_pipe_index_scan_tail});
+      if (scan) return pipe_frame(tail ? Kernel{"pg_pipe_scan_tail", pg_pipe_scan_tail} : Kernel{"pg_pipe_scan", pg_pipe_scan});
+      if (idx && dense_slots(D) <= 2) return pipe_frame(tail ? Kernel{"pg_pipe_index2_tail", pg_pipe_index2_tail} : Kernel{"pg_pipe_index2", pg_pipe_index2});
+      if (idx) return pipe_frame(tail ? Kernel{"pg_pipe_index_tail", pg_pipe_index_tail} : Kernel{"pg_pipe_index", pg_pipe_index});
+      return pipe_frame(tail ? Kernel{"pg_pipe_tail", pg_pipe_tail} : Kernel{"pg_pipe_none", pg_pipe_none});
+    }
+    // ---- dense `_d`: index AND raw-INT range scan where the pipelined kernels do not apply (PG_NO_PIPE, a value column they do not take)
+    if (agg_mode == PG_AGG_LDS && P.fast_filter == 4 && D.dense_fused && !K.no_dense_fused && P.fast_agg) return fast_frame({"pg_fast_i32range_d", pg_fast_i32range_d});
+    // ---- fast: one kernel per kind of the single scan
+    switch (P.fast_filter) {
+      case -1: return fast_frame(agg ? Kernel{"pg_fast_none_a", pg_fast_none_a} : Kernel{"pg_fast_none_f", pg_fast_none_f});
+      case 4: return fast_frame(agg ? Kernel{"pg_fast_i32range_a", pg_fast_i32range_a} : Kernel{"pg_fast_i32range_f", pg_fast_i32range_f});
+      case 0: return fast_frame(agg ? Kernel{"pg_fast_dictrange_a", pg_fast_dictrange_a} : Kernel{"pg_fast_dictrange_f", pg_fast_dictrange_f});
+      case 2: return fast_frame(agg ? Kernel{"pg_fast_dictlut_a", pg_fast_dictlut_a} : Kernel{"pg_fast_dictlut_f", pg_fast_dictlut_f});
+      case 100: return fast_frame(agg ? Kernel{"pg_fast_multi_a", pg_fast_multi_a} : Kernel{"pg_fast_multi_f", pg_fast_multi_f});
+      // -2 is the interpreter's (uses_fast_kernel); the planner's scan_kind (pg_plan.cpp) yields 0, 2 or 4 and compile_plan adds -1 and 100
+      default: fail(PG_ERR_INTERNAL, "no fast kernel for fast_filter %d", P.fast_filter);
+    }
   }
-  if (uses_specd(P, agg_mode)) {   // behind the table and its trash slots a private strip of LDS per wavefront; two workgroups per CU where their LDS fits
-    const int waves = pg_specd_waves_per_block;
-    const size_t need = lds + 64 + specd_stage_bytes(P) + 512 * (size_t)P.dev.n_ops;
-    const int per_cu = knobs().specd_wgs_per_cu > 0 ? ((size_t)knobs().specd_wgs_per_cu * (need + 1024) <= lds_per_cu() ? knobs().specd_wgs_per_cu : 1) : 1;
-    return {std::max(1, std::min((n_wtiles + waves - 1) / waves, num_cus() * per_cu)), waves * 64, need};
+  if (D.mv) {   // a multi-value column in the filter, the group key or an aggregation (the planner leaves these fast_filter -2: never `fast`)
+    if (D.mvg && agg_mode == PG_AGG_LDS && !K.no_mvg) {
+      // ---- mvg (pg_kernels_mvg.hip): GROUP BY one multi-value column, no filter, decided at plan time (PgQueryPlan::mvg; >= 16: the *MV functions
+      //      over one multi-value column, single-value keys).  One 16-wavefront workgroup per CU; the table and a trash slot per lane and accumulator
+      const Kernel k = D.mvg >= 16 ? (D.mvg == 20 ? Kernel{"pg_mv_aggr_4", pg_mv_aggr_4} : Kernel{"pg_mv_aggr_8", pg_mv_aggr_8})
+                                   : (D.mvg == 4 ? Kernel{"pg_mv_group_4", pg_mv_group_4} : Kernel{"pg_mv_group_8", pg_mv_group_8});
+      return {k.fn, k.name, tiles_grid(PG_WAVES_PER_BLOCK, 1), PG_BLOCK, lds + 64 + 512 * (size_t)D.n_ops + (size_t)D.mvg_dict_card * 4, 0};
+    }
+    // ---- mv (pg_kernels_mv.hip)
+    if (agg_mode == PG_AGG_NONE) return generic_frame({"pg_mv_query_f", pg_mv_query_f});
+    return generic_frame(agg_mode == PG_AGG_GLOBAL ? Kernel{"pg_mv_query_g", pg_mv_query_g} : Kernel{"pg_mv_query_l", pg_mv_query_l});
   }
-  if (uses_spec_kernel(P, agg_mode))   // one 12-wavefront workgroup per CU walking tiles b, b + grid, ...; table + two stage buffers in LDS
-    return {std::max(1, std::min(n_wtiles, num_cus())), pg_spec_waves_per_block * 64, lds + 64 + 2 * spec_stage_bytes(P) + 512 * (size_t)P.dev.n_ops};   // (+ 64 trash slots per accumulator)
-  if (uses_pipe_kernel(P, agg_mode)) {
-    const int wgs_per_cu = knobs().pipe_wgs_per_cu;   // tuning knob
-    const int per_cu = ((size_t)wgs_per_cu * (lds + 4096) <= lds_per_cu()) ? wgs_per_cu : 1;
-    const int waves = pg_pipe_waves_per_block;
-    int grid = std::min((n_wtiles + waves - 1) / waves, num_cus() * per_cu);
-    return {std::max(grid, 1), waves * 64, lds};
-  }
-  if (uses_fast_kernel(P, agg_mode)) {
-    // one 16-wave workgroup per CU; fewer when the segment has fewer wave tiles than that
-    const int wgs_per_cu = knobs().wgs_per_cu;   // tuning knob
-    const int per_cu = ((size_t)wgs_per_cu * (lds + 4096) <= lds_per_cu()) ? wgs_per_cu : 1;
-    int grid = std::min((n_wtiles + PG_WAVES_PER_BLOCK - 1) / PG_WAVES_PER_BLOCK, num_cus() * per_cu);
-    return {std::max(grid, 1), PG_BLOCK, lds};
-  }
-  // interpreter kernel: 8-wave workgroups, two per CU when both LDS tables fit
-  const int waves = PG_GENERIC_BLOCK / 64;
-  const int per_cu = (2 * (lds + 4096) <= lds_per_cu()) ? 2 : 1;
-  int grid = std::min((n_wtiles + waves - 1) / waves, num_cus() * per_cu);
-  return {std::max(grid, 1), PG_GENERIC_BLOCK, lds};
+  // ---- interpreter
+  if (agg_mode == PG_AGG_NONE) return generic_frame({"pg_generic_query_f", pg_generic_query_f});
+  if (agg_mode == PG_AGG_GLOBAL) return generic_frame(P.digit_ops ? Kernel{"pg_generic_query_gd", pg_generic_query_gd} : Kernel{"pg_generic_query_g", pg_generic_query_g});
+  return generic_frame(P.digit_ops ? Kernel{"pg_generic_query_ld", pg_generic_query_ld} : Kernel{"pg_generic_query_l", pg_generic_query_l});
+}
+static void launch(const Dispatch& d, hipStream_t stream, const PgQueryPlan& D) {
+  hipLaunchKernelGGL(d.fn, dim3(d.grid), dim3(d.block), d.lds, stream, D);
+  PG_HIP(hipGetLastError());
+}
+// The filter alone, as a pass of its own in front of kernels that take match words (one bit per doc, in ctx.words): queued behind whatever
+// the stream holds; its match count lands in ctx.stats[0]
+static uint32_t* filter_pass(const CompiledPlan& P, const PgQueryPlan& D, ThreadCtx& ctx) {
+  ThreadCtx::grow(ctx.words, (size_t)D.n_wtiles * 64 * 4);
+  PgQueryPlan F = D;
+  F.agg_mode = PG_AGG_NONE;
+  F.out_words = ctx.words.as<uint64_t>();
+  launch(dispatch(P, PG_AGG_NONE, D.n_wtiles, 0), ctx.stream, F);
+  return ctx.words.as<uint32_t>();
 }
 
 static void fill_stats(pg_exec_stats& st, const CompiledPlan& P, int64_t full_scan_entries, int64_t total_docs, const uint64_t* stats_host) {
@@ -856,10 +832,7 @@ static int64_t exact_entries_scanned(CompiledPlan& P, ThreadCtx& ctx, const Canc
     HostBits hb;
     if (!on_device) hb.resize_for(n_docs);
     if (n_docs > 0) {
-      const LaunchShape shape = launch_shape(L, D.n_wtiles, PG_AGG_NONE);
-      const char* kname = "";
-      hipLaunchKernelGGL(select_kernel(L, PG_AGG_NONE, &kname), dim3(shape.grid), dim3(shape.block), shape.lds, ctx.stream, D);
-      PG_HIP(hipGetLastError());
+      launch(dispatch(L, PG_AGG_NONE, D.n_wtiles, 0), ctx.stream, D);
       if (on_device) { dev_bits.emplace(lf.first, D.out_words); continue; }
       PG_HIP(hipMemcpyAsync(hb.w.data(), ctx.words.ptr, (size_t)(((int64_t)n_docs + 63) / 64) * 8, hipMemcpyDeviceToHost, ctx.stream));
       PG_HIP(hipStreamSynchronize(ctx.stream));
@@ -1041,18 +1014,8 @@ static std::vector<int> oct_pass_bounds(int n_wtiles, int64_t registers) {
 static void run_oct_pruned(CompiledPlan& P, PgQueryPlan& D, ThreadCtx& ctx, const CancelToken* cancel, const std::vector<uint32_t*>& aux_final, int64_t n_out) {
   const size_t G = (size_t)D.n_groups, G_pad = (G + 3) & ~(size_t)3;
   const int NB = D.radix_buckets, Q = pg_p2_round_quads[1];
-  D.match_words = nullptr;
-  if (!P.match_all) {   // the filter's match words first (one launch, no host round trip: nothing here is sized by the match count)
-    ThreadCtx::grow(ctx.words, (size_t)D.n_wtiles * 64 * 4);
-    PgQueryPlan F = D;
-    F.agg_mode = PG_AGG_NONE;
-    F.out_words = ctx.words.as<uint64_t>();
-    const char* fname = "";
-    const LaunchShape fshape = launch_shape(P, D.n_wtiles, PG_AGG_NONE);
-    hipLaunchKernelGGL(select_kernel(P, PG_AGG_NONE, &fname), dim3(fshape.grid), dim3(fshape.block), fshape.lds, ctx.stream, F);
-    PG_HIP(hipGetLastError());
-    D.match_words = ctx.words.as<uint32_t>();
-  }
+  // the filter's match words first (one launch, no host round trip: nothing here is sized by the match count)
+  D.match_words = P.match_all ? nullptr : filter_pass(P, D, ctx);
   const std::vector<int> bounds = oct_pass_bounds(D.n_wtiles, (int64_t)G << D.aux[0].log2m);
   const int n_pass = (int)bounds.size();
   int max_tiles = 0;
@@ -1973,6 +1936,7 @@ static std::unique_ptr<Result> execute_query_impl(Segment& seg, const pg_query& 
     return res;
   }
 
+  const Knobs& K = knobs();   // the one snapshot that decides this execution's kernel and launch (knobs_reload may publish another meanwhile)
   PgQueryPlan D = P.dev;
   int64_t space_docs = P.space_docs;
   if (opt.doc_limit > 0 && opt.doc_limit < space_docs) {   // a doc prefix (the partition pipeline honours D.num_docs / D.n_wtiles everywhere)
@@ -1983,13 +1947,13 @@ static std::unique_ptr<Result> execute_query_impl(Segment& seg, const pg_query& 
   // small doc spaces with per-doc state merges (PgQueryPlan::tile_split_shift): up to 128 wavefronts share a wave tile
   int split_shift = 0;
   {
-    const bool no_split = knobs().no_tile_split;   // measurement knob
+    const bool no_split = K.no_tile_split;   // measurement knob
     const bool table_mode = D.agg_mode == PG_AGG_LDS || D.agg_mode == PG_AGG_SINGLE || D.agg_mode == PG_AGG_LDS_PART || D.agg_mode == PG_AGG_GLOBAL;
-    if (!no_split && table_mode && D.n_aux > 0 && !uses_fast_kernel(P, D.agg_mode))
+    if (!no_split && table_mode && D.n_aux > 0 && !uses_fast_kernel(P, D.agg_mode, K))
     {
       // (serialized-HyperLogLog merges — a star-tree's pair column — are a serial chain of loads and compare-and-swaps per wavefront: 16 docs
       // each; the other states take one atomic per doc and stop at 64 docs per wavefront)
-      const int knob = knobs().tile_split_max;   // tuning knob (≤ 9: 8 quad slots x 64 lanes)
+      const int knob = K.tile_split_max;   // tuning knob (≤ 9: 8 quad slots x 64 lanes)
       bool merges = false;
       for (int x = 0; x < D.n_aux; x++) merges |= D.aux[x].kind == PG_AUX_HLL_BYTES;
       const int max_split = knob >= 0 ? knob : (merges ? 7 : 5);
@@ -1997,14 +1961,18 @@ static std::unique_ptr<Result> execute_query_impl(Segment& seg, const pg_query& 
     }
   }
   // oct-layout kernels (pg_kernels_oct.hip): one 16-wavefront workgroup per CU, no tile splitting
-  const bool no_oct = knobs().no_oct_exec;   // measurement knob: plans keep D.oct, the round-3 kernels run them
+  const bool no_oct = K.no_oct_exec;   // measurement knob: plans keep D.oct, the round-3 kernels run them
   const bool oct_lds = D.oct == 1 && !no_oct, oct_pruned = D.oct == 2 && (!no_oct || D.p2_byte_regs) && D.agg_mode == PG_AGG_RADIX && D.p2;
   if (oct_lds) split_shift = 0;
   D.tile_split_shift = split_shift;
-  t_spec_pin = {&P, D.agg_mode, spec_shape(P, D.agg_mode)};   // (cleared when the query has been submitted: the plan may die before this thread's next query)
-  const int64_t image_saved_bytes = spec_images(seg, P, D, t_spec_pin.shape);
-  LaunchShape shape = launch_shape(P, D.n_wtiles << split_shift, D.agg_mode);
-  if (oct_lds) shape = {std::max(1, std::min((D.n_wtiles + PG_WAVES_PER_BLOCK - 1) / PG_WAVES_PER_BLOCK, num_cus())), PG_BLOCK, (D.oct_dword ? (size_t)D.aux[0].lds_offset + (size_t)D.aux[0].rep_bytes * 4 : P.lds_bytes) + 64};
+  // the kernel of this execution and its launch (the wave-specialised choice follows rates that move: asked once)
+  Dispatch shape = dispatch(P, D.agg_mode, D.n_wtiles << split_shift, spec_shape(P, D.agg_mode, K), K);
+  const int64_t image_saved_bytes = spec_images(seg, P, D, shape.spec, K);
+  if (oct_lds) {   // pg_oct_* run in place of the dispatched kernel, in a frame of their own
+    shape.grid = std::max(1, std::min((D.n_wtiles + PG_WAVES_PER_BLOCK - 1) / PG_WAVES_PER_BLOCK, num_cus()));
+    shape.block = PG_BLOCK;
+    shape.lds = (D.oct_dword ? (size_t)D.aux[0].lds_offset + (size_t)D.aux[0].rep_bytes * 4 : P.lds_bytes) + 64;
+  }
   const int64_t n_out = (int64_t)D.n_ops * D.n_groups;
   // The stats counters are zero on entry: the reduce kernel of the previous query on this stream re-zeroes them after
   // moving them behind the result table (one device→host copy per query).
@@ -2094,19 +2062,10 @@ static std::unique_ptr<Result> execute_query_impl(Segment& seg, const pg_query& 
     unsigned long long matched_now = (unsigned long long)space_docs;
     D.match_words = nullptr;
     if (!P.match_all) {
-      const size_t n_words = (size_t)D.n_wtiles * 64;
-      ThreadCtx::grow(ctx.words, n_words * 4);
-      PgQueryPlan F = D;
-      F.agg_mode = PG_AGG_NONE;
-      F.out_words = ctx.words.as<uint64_t>();
-      const char* fname = "";
-      const LaunchShape fshape = launch_shape(P, D.n_wtiles, PG_AGG_NONE);
-      hipLaunchKernelGGL(select_kernel(P, PG_AGG_NONE, &fname), dim3(fshape.grid), dim3(fshape.block), fshape.lds, ctx.stream, F);
-      PG_HIP(hipGetLastError());
+      D.match_words = filter_pass(P, D, ctx);
       // the tuple area is sized by the docs that passed the filter
       PG_HIP(hipMemcpyAsync(&matched_now, ctx.stats.ptr, 8, hipMemcpyDeviceToHost, ctx.stream));
       stream_wait(ctx, cancel);
-      D.match_words = ctx.words.as<uint32_t>();
     }
     const int T = D.p2_planes, NB = D.radix_buckets, Q = pg_p2_round_quads[T];
     const size_t nbp = (size_t)((NB + 63) & ~63);
@@ -2214,15 +2173,7 @@ static std::unique_ptr<Result> execute_query_impl(Segment& seg, const pg_query& 
   } else if (has_docs && radix) {
     // ---- radix-partitioned group-by: filter → match words; count; offsets; scatter; per-bucket LDS aggregation; merge ---------
     kname = "pg_radix_group_by";
-    const size_t n_words = (size_t)D.n_wtiles * 64;
-    ThreadCtx::grow(ctx.words, n_words * 4);
-    PgQueryPlan F = D;
-    F.agg_mode = PG_AGG_NONE;
-    F.out_words = ctx.words.as<uint64_t>();
-    const char* fname = "";
-    const LaunchShape fshape = launch_shape(P, D.n_wtiles, PG_AGG_NONE);
-    hipLaunchKernelGGL(select_kernel(P, PG_AGG_NONE, &fname), dim3(fshape.grid), dim3(fshape.block), fshape.lds, ctx.stream, F);
-    PG_HIP(hipGetLastError());
+    D.match_words = filter_pass(P, D, ctx);
     // the tuple area is sized by the docs that passed the filter, not by the segment (48 B x 2^31 docs would not fit)
     unsigned long long matched_now = 0;
     PG_HIP(hipMemcpyAsync(&matched_now, ctx.stats.ptr, 8, hipMemcpyDeviceToHost, ctx.stream));
@@ -2250,7 +2201,6 @@ static std::unique_ptr<Result> execute_query_impl(Segment& seg, const pg_query& 
     }
     const size_t pad_tuples = D.radix_stage ? (size_t)rgrid * (size_t)D.radix_buckets * (size_t)stage_waves * (size_t)D.radix_stage : 0;
     ThreadCtx::grow(ctx.radix_tuples, ((size_t)matched_now + pad_tuples) * (size_t)D.radix_stride + 256);
-    D.match_words = ctx.words.as<uint32_t>();
     D.radix_hist = ctx.radix_hist.as<uint32_t>();
     D.radix_bucket_start = ctx.radix_start.as<uint32_t>();
     D.radix_tuples = ctx.radix_tuples.as<uint8_t>();
@@ -2321,18 +2271,7 @@ static std::unique_ptr<Result> execute_query_impl(Segment& seg, const pg_query& 
     }
   } else if (has_docs && oct_lds) {
     // ---- LDS-resident DISTINCTCOUNTHLL / DISTINCTCOUNT next to a small key (pg_kernels_oct.hip): [filter -> match words;] one pass ----
-    D.match_words = nullptr;
-    if (!P.match_all) {
-      ThreadCtx::grow(ctx.words, (size_t)D.n_wtiles * 64 * 4);
-      PgQueryPlan F = D;
-      F.agg_mode = PG_AGG_NONE;
-      F.out_words = ctx.words.as<uint64_t>();
-      const char* fname = "";
-      const LaunchShape fshape = launch_shape(P, D.n_wtiles, PG_AGG_NONE);
-      hipLaunchKernelGGL(select_kernel(P, PG_AGG_NONE, &fname), dim3(fshape.grid), dim3(fshape.block), fshape.lds, ctx.stream, F);
-      PG_HIP(hipGetLastError());
-      D.match_words = ctx.words.as<uint32_t>();
-    }
+    D.match_words = P.match_all ? nullptr : filter_pass(P, D, ctx);
     const bool count_only = D.oct_src_kind == 0 && D.n_aux == 0 && !D.match_words && D.n_group_cols >= 1 && !knobs().no_oct_count_kernel;   // plan_oct: COUNT(*) alone
     kname = count_only ? "pg_oct_c" : (D.match_words ? "pg_oct_lm" : "pg_oct_l");
     hipLaunchKernelGGL(count_only ? pg_oct_c : (D.match_words ? pg_oct_lm : pg_oct_l), dim3(shape.grid), dim3(shape.block), shape.lds, ctx.stream, D);
@@ -2340,9 +2279,7 @@ static std::unique_ptr<Result> execute_query_impl(Segment& seg, const pg_query& 
   } else if (has_docs) {
     // COUNT(*) behind an index-only filter of dense postings: the bitmap stream (pg_dense_count_*), not the tile walk
     const bool no_dense_count = knobs().no_dense_count;   // A/B knob
-    int n_ptr = 0;   // distinct dense posting pointers (the planner pads the eight slots with repeats of slot 0)
-    for (int j = 0; j < 8; j++) if (j == 0 || D.dense_ptr[j] != D.dense_ptr[0] || D.dense_group[j] != D.dense_group[0]) n_ptr = j + 1;
-    if (!no_dense_count && D.agg_mode == PG_AGG_NONE && !D.out_words && !D.out_tile_counts && uses_fast_kernel(P, PG_AGG_NONE) && P.fast_filter == -1 &&
+    if (!no_dense_count && D.agg_mode == PG_AGG_NONE && !D.out_words && !D.out_tile_counts && uses_fast_kernel(P, PG_AGG_NONE, K) && P.fast_filter == -1 &&
         D.dense_fused && D.n_index_instr > 0 && !D.mv) {
       static const QueryKernel kCount[8] = {pg_dense_count_1, pg_dense_count_2, pg_dense_count_3, pg_dense_count_4,
                                             pg_dense_count_5, pg_dense_count_6, pg_dense_count_7, pg_dense_count_8};
@@ -2350,8 +2287,8 @@ static std::unique_ptr<Result> execute_query_impl(Segment& seg, const pg_query& 
       const int wgs_per_cu = knobs().dense_count_wgs;   // tuning knob
       const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((n_q + 2047) / 2048, (int64_t)num_cus() * std::max(wgs_per_cu, 1)));
       kname = "pg_dense_count";
-      hipLaunchKernelGGL(kCount[n_ptr - 1], dim3(grid), dim3(1024), 0, ctx.stream, D);
-    } else if (!no_dense_count && D.agg_mode == PG_AGG_NONE && !D.out_words && !D.out_tile_counts && uses_fast_kernel(P, PG_AGG_NONE) &&
+      hipLaunchKernelGGL(kCount[dense_slots(D) - 1], dim3(grid), dim3(1024), 0, ctx.stream, D);
+    } else if (!no_dense_count && D.agg_mode == PG_AGG_NONE && !D.out_words && !D.out_tile_counts && uses_fast_kernel(P, PG_AGG_NONE, K) &&
                (P.fast_filter == 0 || P.fast_filter == 2) && D.n_index_instr == 0 && D.fast_scan_pushed && !D.mv) {
       // COUNT(*) behind one scan of a <= 8-bit dictionary column over the whole segment: the bit stream, 32 docs per thread (pg_dict_count_*)
       static const QueryKernel kDict[8] = {pg_dict_count_1, pg_dict_count_2, pg_dict_count_3, pg_dict_count_4,
@@ -2362,8 +2299,8 @@ static std::unique_ptr<Result> execute_query_impl(Segment& seg, const pg_query& 
       kname = "pg_dict_count";
       hipLaunchKernelGGL(kDict[bits - 1], dim3(grid), dim3(1024), 0, ctx.stream, D);
     } else {
-      QueryKernel kern = select_kernel(P, D.agg_mode, &kname);
-      hipLaunchKernelGGL(kern, dim3(shape.grid), dim3(shape.block), shape.lds, ctx.stream, D);
+      kname = shape.name;
+      launch(shape, ctx.stream, D);
     }
     PG_HIP(hipGetLastError());
   }
@@ -3369,13 +3306,12 @@ std::unique_ptr<DocIdSet> execute_filter(Segment& seg, const pg_filter_node* fil
   D.out_words = out->words.as<uint64_t>();
   D.out_tile_counts = ctx.tile_counts.as<uint32_t>();
   D.agg_mode = PG_AGG_NONE;
-  const LaunchShape shape = launch_shape(P, P.dev.n_wtiles, PG_AGG_NONE);
   PG_HIP(hipEventRecord(ctx.ev[0], ctx.stream));
   const char* kname = "";
   if (seg.total_docs > 0) {
-    QueryKernel kern = select_kernel(P, PG_AGG_NONE, &kname);
-    hipLaunchKernelGGL(kern, dim3(shape.grid), dim3(shape.block), shape.lds, ctx.stream, D);
-    PG_HIP(hipGetLastError());
+    const Dispatch d = dispatch(P, PG_AGG_NONE, P.dev.n_wtiles, 0);
+    kname = d.name;
+    launch(d, ctx.stream, D);
   }
   PG_HIP(hipEventRecord(ctx.ev[1], ctx.stream));
   uint64_t stats_host[PG_MAX_STATS];

@@ -2641,7 +2641,7 @@ PG_KERNEL __global__ void __launch_bounds__(256) pg_reduce_parts_kernel(const in
   };
   const int64_t wg_stride = (int64_t)n_ops * part_groups;
   const int64_t* src = partials + (int64_t)o * part_groups + l;
-  const int per_range = (n_wg >> 3) / n_parts;   // launch_shape: the grid is 8 x per_range x n_parts
+  const int per_range = (n_wg >> 3) / n_parts;   // dispatch (pg_exec.hip): the grid is 8 x per_range x n_parts
   for (int j = quarter; j < per_range; j += 4) {
     const int64_t w0 = 8 * ((int64_t)range + (int64_t)n_parts * j);
     int64_t v[8];

@@ -1,4 +1,4 @@
-"""Every kernel name `select_kernel` and its neighbours in pinot_amd/csrc/pg_exec.hip can report in pg_exec_stats.kernel, tied to one query
+"""Every kernel name `dispatch` and its neighbours in pinot_amd/csrc/pg_exec.hip can report in pg_exec_stats.kernel, tied to one query
 that reaches it: the segment it runs on, the entry point, the SQL, the knobs, an optional upsert snapshot, and the sizes of the ladder at which
 the planner picks that kernel.  Data plus small helpers; tests/test_kernel_inventory.py checks it against pg_exec.hip on the CPU,
 tests/test_gpu_kernel_matrix.py runs it against the oracle on the GPU."""
@@ -236,7 +236,7 @@ del E
 _TAIL_NEEDS_INDEX_AND_SCAN = (
     "pg_plan.cpp compile_plan: the pipeline sets pipe_tail only in the branch `fast_filter == 100 && n_fast_scans == 1 && tail_posting >= 0`, "
     "which also sets has_scan; tail_posting >= 0 needs an index-only prefix (`n_idx > 0`), so pipe_has_index == 1 too — a tail always comes "
-    "with index AND scan, which select_kernel names pg_pipe_index_scan_tail (or pg_fast_i32range_st)")
+    "with index AND scan, which dispatch names pg_pipe_index_scan_tail (or pg_fast_i32range_st)")
 _RAW_VALUE_NEEDS_DICT_SCAN = (
     "pg_plan.cpp compile_plan (specd): `if (ok && vkind == 1 && (!has_scan || sbits == 32)) ok = false;` — a raw INT value column takes the "
     "specd / specw frame only behind a dictionary-encoded range scan, so the value-kind-r row's filter shapes without a scan (none, index) "
