@@ -2,7 +2,8 @@
 CPU: the oracle's decompressors against the reference's own legacy blobs (FixedByteChunkSVForwardIndexTest /
 VarByteChunkSVForwardIndexTest backward-compatibility fixtures, copied by tests/golden/make_chunk_fixtures.py) and against
 libsnappy / liblz4 (pyarrow) on seeded data.  GPU: columns uploaded compressed and decompressed in HBM (pg_decompress.hip) give
-the oracle's query results, on the same fixtures and on seeded data."""
+the oracle's query results, on the same fixtures and on seeded data.
+The byte-exact check of pg_decompress.hip — hand-built streams, every launch shape, value-by-value readback — is tests/test_gpu_chunk_streams.py."""
 import ctypes as C
 import gzip
 import os
