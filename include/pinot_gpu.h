@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PG_ABI_VERSION 4
+#define PG_ABI_VERSION 5
 
 typedef enum pg_status {
   PG_OK = 0,
@@ -173,7 +173,18 @@ typedef enum pg_agg_function {   /* AggregationFunctionType (subset named by nor
   PG_AGG_AVGMV = 12,
   PG_AGG_MINMAXRANGEMV = 13,
   PG_AGG_DISTINCTCOUNTMV = 14,
-  PG_AGG_DISTINCTCOUNTHLLMV = 15
+  PG_AGG_DISTINCTCOUNTHLLMV = 15,
+  /* exact PERCENTILE(col, p) (PercentileAggregationFunction.java:155-171): the matching values as doubles (getDoubleValuesSV: a LONG cast, a
+   * FLOAT widened exactly), sorted by Double.compare (-0.0 < 0.0, NaN greatest), final = sorted[(int)((double)n * p / 100)], sorted[n - 1]
+   * for p = 100, Double.NEGATIVE_INFINITY over no value.  p comes from pg_query.agg_params.  Single-value INT / LONG / FLOAT / DOUBLE
+   * columns, dictionary-encoded or raw.  The intermediate result is the reference's DoubleArrayList as ascending (value, count) runs:
+   * PG_RESULT_VALUE_COUNTS.  Refused (PG_ERR_UNSUPPORTED, the Java plan answers): STRING / BYTES and multi-value columns (PERCENTILEMV),
+   * multi-value group-by columns next to it, under PG_QUERY_FLAG_NULL_HANDLING an aggregated or group-by column that holds nulls, a
+   * group key space over 2^32, and — by pg_query_exec, which alone knows the matches — a (group key space x value cardinality) beyond
+   * PG_PCTL_HBM_MAX_BYTES of counters (default 256 MiB) whose sort of every matching doc's key would exceed PG_PCTL_SORT_MAX_BYTES
+   * (default 8 GiB).  p outside [0, 100] or NaN, or agg_params == NULL: PG_ERR_INVALID_ARGUMENT.  The star-tree route is never
+   * taken for such a query; pg_result_merge / pg_result_all_reduce refuse its results (the lists merge by value on the Java side). */
+  PG_AGG_PERCENTILE = 16
 } pg_agg_function;
 
 typedef struct pg_agg_spec {
@@ -215,10 +226,13 @@ typedef struct pg_query {
    * groups TIED at the cut survive is unspecified there — a heap — and here).  numGroupsLimitReached is decided before the trim.
    * Dense key spaces without DISTINCTCOUNT / HLL state select the survivors on the device: only they cross PCIe; ordered by a distinct count
    * (the set's size, HyperLogLog#cardinality: extractFinalResult, TableResizer.java:406-445) or a multi-value function the assembly trims. */
+  /* An ORDER BY that names a PERCENTILE aggregation leaves the segment untrimmed (trimming only ever drops groups the broker would drop). */
   int32_t n_order_by;                           /* 0 => no ORDER BY (no trim) */
   const pg_order_by* order_by;
   int32_t limit;                                /* QueryContext#getLimit (read with n_order_by > 0 only) */
   int32_t min_segment_group_trim_size;          /* <= 0: the segment's groups are never trimmed */
+  /* ABI 5: NULL, or n_aggregations doubles — entry a is the parameter of aggregation a; read for PG_AGG_PERCENTILE only (its p in [0, 100]) */
+  const double* agg_params;
 } pg_query;
 
 #define PG_QUERY_FLAG_PROFILE 0x1          /* record per-kernel HIP-event timings into pg_exec_stats */
@@ -288,6 +302,9 @@ typedef struct pg_query {
    filter's plan is cached.  pg_result_merge / pg_result_all_reduce refuse selection results (SelectionCombineOperator and the broker merge
    them by value). */
 #define PG_QUERY_FLAG_SELECTION 0x100
+/* PERCENTILE aggregations come back as their FINAL value (PG_RESULT_DOUBLE: extractFinalResult), not as (value, count) runs: only one double
+   per group and aggregation crosses PCIe.  For a caller that merges nothing afterwards. */
+#define PG_QUERY_FLAG_FINAL_PERCENTILE 0x200
 #define PG_QUERY_FLAG_KEEP_DEVICE_TABLE 0x4 /* keep the dense accumulator table in HBM with the result (pg_result_merge / _all_reduce) */
 
 /* ExecutionStatistics (pinot-core/.../operator/ExecutionStatistics.java) + device timings. */
@@ -311,6 +328,8 @@ typedef struct pg_exec_stats {
   int32_t filter_stats_path;      /* how num_entries_scanned_in_filter was counted — 0: by the query's own kernels (shapes with a closed form), 1: the reference's
                                      iterator automaton walked on the host over the leaves' match bitmaps, 2: the same automaton in tiles on the device
                                      (pg_filter_stats_tiles.h) */
+  int32_t percentile_passes;      /* ABI 5: counting passes the PERCENTILE path launched — one per distinct percentile column whatever the number of
+                                     percentiles asked of it (pg_pctl_lds / pg_pctl_hbm / pg_pctl_sort; 0 for every other query) */
 } pg_exec_stats;
 
 /* Intermediate result kinds (AggregationFunction#getIntermediateResultColumnType). */
@@ -321,8 +340,10 @@ typedef enum pg_result_kind {
   PG_RESULT_MINMAX_PAIR = 3,
   PG_RESULT_DICTID_SET = 4,/* DISTINCTCOUNT over a dictionary column: set of dictIds (decoded by the caller) */
   PG_RESULT_HLL = 5,       /* HyperLogLog registers, m = 2^log2m bytes per group */
-  PG_RESULT_VALUE_SET = 6  /* DISTINCTCOUNT over a raw (no-dictionary) INT / LONG / FLOAT / DOUBLE column: set of VALUES — the typed open-hash sets of
+  PG_RESULT_VALUE_SET = 6, /* DISTINCTCOUNT over a raw (no-dictionary) INT / LONG / FLOAT / DOUBLE column: set of VALUES — the typed open-hash sets of
                               BaseDistinctAggregateAggregationFunction.java:325-380 (pg_result_set_sizes + pg_result_set_values_long / _double) */
+  PG_RESULT_VALUE_COUNTS = 7 /* PERCENTILE: the group's DoubleArrayList as runs — pg_result_set_sizes gives the runs per group, pg_result_set_values_double
+                              the runs' values (ascending under Double.compare within a group), pg_result_set_counts how often each occurs */
 } pg_result_kind;
 
 /* ------------------------------------------------------------------------------------------------------------------
@@ -484,6 +505,8 @@ int32_t pg_result_set_dict_ids(pg_result_t result, int32_t agg, int32_t* out_dic
  * _long for INT / LONG columns, _double for FLOAT / DOUBLE columns (a FLOAT widened exactly); the other one returns PG_ERR_INVALID_ARGUMENT */
 int32_t pg_result_set_values_long(pg_result_t result, int32_t agg, int64_t* out_values, int64_t capacity);
 int32_t pg_result_set_values_double(pg_result_t result, int32_t agg, double* out_values, int64_t capacity);
+/* PERCENTILE (PG_RESULT_VALUE_COUNTS): the count of every run, parallel to pg_result_set_values_double */
+int32_t pg_result_set_counts(pg_result_t result, int32_t agg, int64_t* out_counts, int64_t capacity);
 /* DISTINCTCOUNTHLL: num_groups * 2^log2m register bytes, group-major */
 int32_t pg_result_hll_registers(pg_result_t result, int32_t agg, uint8_t* out_registers, int64_t capacity);
 /* The result as the bytes of a DataTableImplV4 carrying INTERMEDIATE results — what GroupByResultsBlock#getDataTable

@@ -310,6 +310,8 @@ public class GpuGroupByOperator extends BaseOperator<BaseResultsBlock> {
         return GpuResultObjects.valueSets(result, a, n, _segment, function);     // dictIds -> typed value Set (BaseDistinctAggregate...:671-694)
       case PinotGpu.RESULT_VALUE_SET:
         return GpuResultObjects.rawValueSets(result, a, n, _segment, function);  // a raw column's values -> typed value Set (:325-380)
+      case PinotGpu.RESULT_VALUE_COUNTS:
+        return GpuResultObjects.doubleLists(result, a, n);                       // PERCENTILE: (value, count) runs -> DoubleArrayList (PercentileAggregationFunction.java:77-100)
       default:
         return GpuResultObjects.hyperLogLogs(result, a, n, function);            // register bytes -> com.clearspring HyperLogLog (RegisterSet)
     }

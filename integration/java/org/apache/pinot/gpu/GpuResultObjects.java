@@ -186,6 +186,45 @@ public final class GpuResultObjects {
     return out;
   }
 
+  /** PERCENTILE (pg_result_kind PG_RESULT_VALUE_COUNTS): per group the reference's DoubleArrayList of every matching value, expanded from the
+   *  library's ascending (value, count) runs — merge is addAll and extractFinalResult sorts, so the order is free
+   *  (PercentileAggregationFunction.java:139-171). */
+  public static Object[] doubleLists(long result, int aggregation, int numGroups) {
+    int[] sizes = new int[numGroups];
+    PinotGpu.resultSetSizes(result, aggregation, sizes);
+    long total = 0;
+    for (int s : sizes) {
+      total += s;
+    }
+    if (total > Integer.MAX_VALUE - 8) {
+      throw new UnsupportedOperationException("PERCENTILE state of " + total + " runs exceeds one Java array");
+    }
+    double[] values = new double[(int) total];
+    long[] counts = new long[(int) total];
+    PinotGpu.resultSetValuesDouble(result, aggregation, values);
+    PinotGpu.resultSetCounts(result, aggregation, counts);
+    Object[] out = new Object[numGroups];
+    int at = 0;
+    for (int g = 0; g < numGroups; g++) {
+      long n = 0;
+      for (int i = 0; i < sizes[g]; i++) {
+        n += counts[at + i];
+      }
+      if (n > Integer.MAX_VALUE - 8) {
+        throw new UnsupportedOperationException("PERCENTILE list of " + n + " values exceeds one Java array");
+      }
+      double[] list = new double[(int) n];
+      int k = 0;
+      for (int i = 0; i < sizes[g]; i++) {
+        java.util.Arrays.fill(list, k, k + (int) counts[at + i], values[at + i]);
+        k += (int) counts[at + i];
+      }
+      out[g] = it.unimi.dsi.fastutil.doubles.DoubleArrayList.wrap(list);
+      at += sizes[g];
+    }
+    return out;
+  }
+
   /** One HyperLogLog per group from its 2^log2m register bytes. */
   public static Object[] hyperLogLogs(long result, int aggregation, int numGroups, AggregationFunction function) {
     int log2m = ((org.apache.pinot.core.query.aggregation.function.DistinctCountHLLAggregationFunction) function).getLog2m();

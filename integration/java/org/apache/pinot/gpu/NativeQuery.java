@@ -98,6 +98,13 @@ public final class NativeQuery implements AutoCloseable {
       }
       b.putInt(fn).putInt(0);   // log2m 0: DEFAULT_HYPERLOGLOG_LOG2M (a literal second argument is not expressible here)
       putString(b, args.isEmpty() ? "*" : args.get(0).getIdentifier());
+      if (fn == 16) {   // PG_AGG_PERCENTILE: its p as one double right after the column (records without a PERCENTILE are unchanged)
+        double p = percentileOf(f);
+        if (!(p >= 0.0 && p <= 100.0)) {
+          return null;
+        }
+        b.putDouble(p);
+      }
     }
     if (orderBy != null) {
       for (int v : orderBy) {
@@ -214,6 +221,30 @@ public final class NativeQuery implements AutoCloseable {
     return out;
   }
 
+  /**
+   * The p of an exact PERCENTILE: PercentileAggregationFunction keeps it in a protected field, but names its result column by it —
+   * "percentile95(col)" for the legacy form, "percentile(col, 99.9)" otherwise (PercentileAggregationFunction.java:60-64).  NaN when the
+   * name has neither shape.  The parse assumes the argument is a plain identifier (no "(" and no ", " inside it), which from() has already
+   * checked when it calls this; a column whose name held either would give NaN or a wrong p, so from() refuses anything that is not
+   * Type.IDENTIFIER first and an out-of-range or NaN p afterwards.
+   */
+  static double percentileOf(AggregationFunction f) {
+    String name = f.getResultColumnName();
+    try {
+      int open = name.indexOf('(');
+      int comma = name.lastIndexOf(", ");
+      if (open > "percentile".length()) {
+        return Integer.parseInt(name.substring("percentile".length(), open));
+      }
+      if (comma > open && name.endsWith(")")) {
+        return Double.parseDouble(name.substring(comma + 2, name.length() - 1));
+      }
+    } catch (NumberFormatException e) {
+      return Double.NaN;
+    }
+    return Double.NaN;
+  }
+
   /** pg_agg_function of a star-tree function-column pair's function type; -1 for functions the GPU path never reads. */
   static int functionCode(org.apache.pinot.segment.spi.AggregationFunctionType type) {
     switch (type) {
@@ -248,6 +279,8 @@ public final class NativeQuery implements AutoCloseable {
       case MINMAXRANGEMV: return 13;
       case DISTINCTCOUNTMV: return 14;
       case DISTINCTCOUNTHLLMV: return 15;
+      // exact PERCENTILE only: the digest-based members of the family (TDigest, KLL, ...) are other types and stay with the Java plan
+      case PERCENTILE: return f instanceof org.apache.pinot.core.query.aggregation.function.PercentileAggregationFunction ? 16 : -1;
       default: return -1;
     }
   }

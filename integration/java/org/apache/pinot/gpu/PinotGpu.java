@@ -21,7 +21,7 @@ public final class PinotGpu {
   public static final int PG_ERR_UNSUPPORTED = -2;
   // pg_result_kind
   public static final int RESULT_LONG = 0, RESULT_DOUBLE = 1, RESULT_AVG_PAIR = 2, RESULT_MINMAX_PAIR = 3, RESULT_DICTID_SET = 4,
-      RESULT_HLL = 5, RESULT_VALUE_SET = 6;
+      RESULT_HLL = 5, RESULT_VALUE_SET = 6, RESULT_VALUE_COUNTS = 7;
   public static final int GROUP_KEY_DICT_IDS = 0, GROUP_KEY_LONG_VALUES = 1, GROUP_KEY_DOUBLE_VALUES = 2, GROUP_KEY_BYTES_VALUES = 3;
 
   public static native int abiVersion();
@@ -66,6 +66,8 @@ public final class PinotGpu {
   /** DISTINCTCOUNT over a raw column (RESULT_VALUE_SET): the groups' values, concatenated — Long for INT / LONG, Double for FLOAT / DOUBLE columns. */
   public static native void resultSetValuesLong(long result, int aggregation, long[] out);
   public static native void resultSetValuesDouble(long result, int aggregation, double[] out);
+  /** PERCENTILE (RESULT_VALUE_COUNTS): resultSetSizes gives the (value, count) runs per group, resultSetValuesDouble their values, this their counts. */
+  public static native void resultSetCounts(long result, int aggregation, long[] out);
   public static native void resultHllRegisters(long result, int aggregation, byte[] out);
   // enableNullHandling: out[g] = 1 where group g's result of the aggregation / key of the group-by column is NULL
   public static native void resultAggNulls(long result, int aggregation, byte[] out);
@@ -80,7 +82,8 @@ public final class PinotGpu {
   // dictionaries merge element-wise in HBM; UnsupportedOperationException -> merge by values (IndexedTable) as usual
   public static final int QUERY_FLAG_SKIP_STAR_TREE = 0x2, QUERY_FLAG_KEEP_DEVICE_TABLE = 0x4, QUERY_FLAG_APPROX_FILTER_STATS = 0x8,
       QUERY_FLAG_EXACT_FILTER_STATS = 0x10, QUERY_FLAG_FINAL_DISTINCT = 0x20, QUERY_FLAG_NULL_HANDLING = 0x40,
-      QUERY_FLAG_DISTINCT = 0x80, QUERY_FLAG_SELECTION = 0x100;
+      QUERY_FLAG_DISTINCT = 0x80, QUERY_FLAG_SELECTION = 0x100,
+      QUERY_FLAG_FINAL_PERCENTILE = 0x200;   // PERCENTILE aggregations come back as their final double (RESULT_DOUBLE)
   public static final int COMM_UNIQUE_ID_BYTES = 128;
   public static native void resultMerge(long dst, long src);                 // same device
   public static native void resultAllReduce(long result, long comm);         // collective over the communicator's ranks (RCCL)

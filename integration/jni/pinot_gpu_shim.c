@@ -30,6 +30,15 @@ static int32_t rd_i32(reader* r) {
   r->pos += 4;
   return (int32_t)((uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16) | ((uint32_t)b[3] << 24));
 }
+static double rd_f64(reader* r) {   /* 8 bytes, little-endian IEEE double */
+  if (r->failed || r->pos + 8 > r->size) { fail(r, "truncated"); return 0; }
+  uint64_t u = 0;
+  for (int i = 7; i >= 0; i--) u = (u << 8) | r->p[r->pos + (size_t)i];
+  r->pos += 8;
+  double d;
+  memcpy(&d, &u, 8);
+  return d;
+}
 static void* arena_alloc(reader* r, size_t n) {
   pgshim_query* q = r->out;
   n = (n + 7) & ~(size_t)7;
@@ -112,12 +121,17 @@ int32_t pgshim_query_parse(const void* record, uint64_t size, pgshim_query** out
   }
   if (!r.failed && q->q.n_aggregations) {
     pg_agg_spec* a = (pg_agg_spec*)arena_alloc(&r, sizeof(pg_agg_spec) * (size_t)q->q.n_aggregations);
-    for (int32_t i = 0; a && i < q->q.n_aggregations && !r.failed; i++) {
+    /* a PERCENTILE carries its p as one 8-byte double right after its column; records without one are what they were before ABI 5 */
+    double* params = (double*)arena_alloc(&r, sizeof(double) * (size_t)q->q.n_aggregations);
+    int any_param = 0;
+    for (int32_t i = 0; a && params && i < q->q.n_aggregations && !r.failed; i++) {
       a[i].function = rd_i32(&r);
       a[i].log2m = rd_i32(&r);
       a[i].column = rd_string(&r);
+      if (!r.failed && a[i].function == PG_AGG_PERCENTILE) { params[i] = rd_f64(&r); any_param = 1; }
     }
     q->q.aggregations = a;
+    if (any_param) q->q.agg_params = params;
   }
   if (!r.failed && q->q.n_order_by) {
     pg_order_by* ob = (pg_order_by*)arena_alloc(&r, sizeof(pg_order_by) * (size_t)q->q.n_order_by);

@@ -12,7 +12,7 @@ from typing import List, Optional, Sequence
 
 import numpy as np
 
-PG_ABI_VERSION = 4
+PG_ABI_VERSION = 5
 
 # pg_status
 PG_OK = 0
@@ -37,10 +37,10 @@ FILTER_AND, FILTER_OR, FILTER_NOT, FILTER_PREDICATE, FILTER_CONSTANT_TRUE, FILTE
 PRED_EQ, PRED_NOT_EQ, PRED_IN, PRED_NOT_IN, PRED_RANGE, PRED_IS_NULL, PRED_IS_NOT_NULL = range(7)
 AGG_FUNCTIONS = {"COUNT": 0, "SUM": 1, "MIN": 2, "MAX": 3, "AVG": 4, "DISTINCTCOUNT": 5, "DISTINCTCOUNTHLL": 6,
                  "MINMAXRANGE": 7, "COUNTMV": 8, "SUMMV": 9, "MINMV": 10, "MAXMV": 11, "AVGMV": 12, "MINMAXRANGEMV": 13,
-                 "DISTINCTCOUNTMV": 14, "DISTINCTCOUNTHLLMV": 15}
+                 "DISTINCTCOUNTMV": 14, "DISTINCTCOUNTHLLMV": 15, "PERCENTILE": 16}
 MV_TO_SV_FUNCTION = {"COUNTMV": "COUNT", "SUMMV": "SUM", "MINMV": "MIN", "MAXMV": "MAX", "AVGMV": "AVG", "MINMAXRANGEMV": "MINMAXRANGE",
                      "DISTINCTCOUNTMV": "DISTINCTCOUNT", "DISTINCTCOUNTHLLMV": "DISTINCTCOUNTHLL"}
-RESULT_LONG, RESULT_DOUBLE, RESULT_AVG_PAIR, RESULT_MINMAX_PAIR, RESULT_DICTID_SET, RESULT_HLL, RESULT_VALUE_SET = range(7)
+RESULT_LONG, RESULT_DOUBLE, RESULT_AVG_PAIR, RESULT_MINMAX_PAIR, RESULT_DICTID_SET, RESULT_HLL, RESULT_VALUE_SET, RESULT_VALUE_COUNTS = range(8)
 
 QUERY_FLAG_PROFILE = 0x1
 QUERY_FLAG_SKIP_STAR_TREE = 0x2
@@ -51,6 +51,7 @@ QUERY_FLAG_FINAL_DISTINCT = 0x20
 QUERY_FLAG_NULL_HANDLING = 0x40
 QUERY_FLAG_DISTINCT = 0x80   # SELECT DISTINCT: group_by_columns are the DISTINCT columns, no aggregation
 QUERY_FLAG_SELECTION = 0x100   # SELECT cols | * ... [ORDER BY] LIMIT n: group_by_columns are the output columns (extractExpressions order)
+QUERY_FLAG_FINAL_PERCENTILE = 0x200   # PERCENTILE aggregations come back as their final double, not as (value, count) runs
 LIMIT_UNBOUNDED = 2**31 - 1   # DISTINCT ... LIMIT Integer.MAX_VALUE: every tuple
 COMM_UNIQUE_ID_BYTES = 128
 GROUP_KEY_DICT_IDS, GROUP_KEY_LONG_VALUES, GROUP_KEY_DOUBLE_VALUES, GROUP_KEY_BYTES_VALUES = 0, 1, 2, 3
@@ -138,6 +139,7 @@ class PgQuery(C.Structure):
         ("order_by", C.POINTER(PgOrderBy)),
         ("limit", C.c_int32),
         ("min_segment_group_trim_size", C.c_int32),
+        ("agg_params", C.POINTER(C.c_double)),   # ABI 5: NULL or n_aggregations doubles (PERCENTILE's p)
     ]
 
 
@@ -159,6 +161,7 @@ class PgExecStats(C.Structure):
         ("kernel", C.c_char * 32),
         ("star_tree_index", C.c_int32),
         ("filter_stats_path", C.c_int32),
+        ("percentile_passes", C.c_int32),
     ]
 
     def as_dict(self) -> dict:
@@ -195,6 +198,7 @@ GPU_ONLY_SYMBOLS = [
     "result_merge", "result_all_reduce", "result_data_table_v4",
     "comm_get_unique_id", "comm_init_rank", "comm_init_all", "comm_world_size", "comm_destroy",
     "options_reload",
+    "result_set_counts",   # PERCENTILE's (value, count) runs: the oracle has no percentile
 ]
 
 
@@ -225,6 +229,7 @@ class NativeApi:
             self.f("comm_world_size").argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
             self.f("comm_destroy").argtypes = [C.c_void_p]
             self.f("options_reload").argtypes = []
+            self.f("result_set_counts").argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64]
         self.f("last_error").argtypes = [C.c_char_p, C.c_size_t]
         self.f("init").argtypes = [C.c_int32]
         self.f("segment_create").argtypes = [C.c_char_p, C.c_int32, C.POINTER(C.c_void_p)]

@@ -40,6 +40,9 @@ static void knobs_read(Knobs& k) {
   k.exact_stats_max_docs = num("PG_EXACT_STATS_MAX_DOCS", (int64_t)1 << 22);
   k.filter_stats_host = flag("PG_FILTER_STATS_HOST"); k.exact_stats_device_max_docs = num("PG_EXACT_STATS_DEVICE_MAX_DOCS", (int64_t)1 << 27);
   k.select_sort_max_bytes = num("PG_SELECT_SORT_MAX_BYTES", (int64_t)8 << 30);
+  k.pctl_lds_max_keys = std::max<int64_t>(1, std::min<int64_t>(32768, num("PG_PCTL_LDS_MAX_KEYS", 32768)));
+  k.pctl_hbm_max_bytes = std::max<int64_t>(4, num("PG_PCTL_HBM_MAX_BYTES", (int64_t)256 << 20));
+  k.pctl_sort_max_bytes = num("PG_PCTL_SORT_MAX_BYTES", (int64_t)8 << 30);
   k.limit_prefix_min_docs = std::max<int64_t>(PG_WAVE_DOCS, num("PG_LIMIT_PREFIX_MIN_DOCS", (int64_t)1 << 20));
   k.oct_passes = str("PG_OCT_PASSES"); k.rccl_library = str("PG_RCCL_LIBRARY");
 }
@@ -264,6 +267,10 @@ int32_t pg_query_supported(pg_segment_t segment, const pg_query* query) {
       (void)get_plan(segment->seg, query->filter, nullptr, query->flags & PG_QUERY_FLAG_NULL_HANDLING);
       return;
     }
+    if (has_percentile(*query)) {   // the checks of the percentile path; the ordinary part's plan is compiled by the execution
+      percentile_check(segment->seg, *query);
+      return;
+    }
     check_null_handling(segment->seg, *query);
     (void)get_plan(segment->seg, query->filter, query);
   });
@@ -306,6 +313,7 @@ int32_t pg_result_merge(pg_result_t dst, pg_result_t src) {
     REQUIRE(dst && src && dst != src, "null or identical results");
     if (dst->r->distinct || src->r->distinct) fail(PG_ERR_UNSUPPORTED, "distinct results are merged by value (DistinctCombineOperator)");
     if (dst->r->selection || src->r->selection) fail(PG_ERR_UNSUPPORTED, "selection results are merged by value (SelectionCombineOperator)");
+    if (dst->r->percentile || src->r->percentile) fail(PG_ERR_UNSUPPORTED, "PERCENTILE results are merged by value (DoubleArrayList#addAll on the Java side)");
     result_merge(*dst->r, *src->r);
   });
 }
@@ -314,6 +322,7 @@ int32_t pg_result_all_reduce(pg_result_t result, pg_comm_t comm) {
     REQUIRE(result && comm && comm->c, "null argument");
     if (result->r->distinct) fail(PG_ERR_UNSUPPORTED, "distinct results are merged by value (DistinctCombineOperator)");
     if (result->r->selection) fail(PG_ERR_UNSUPPORTED, "selection results are merged by value (SelectionCombineOperator)");
+    if (result->r->percentile) fail(PG_ERR_UNSUPPORTED, "PERCENTILE results are merged by value (DoubleArrayList#addAll on the Java side)");
     result_all_reduce(*result->r, *comm->c);
   });
 }
@@ -442,7 +451,7 @@ int32_t pg_result_longs(pg_result_t result, int32_t agg, int32_t component, int6
 int32_t pg_result_set_sizes(pg_result_t result, int32_t agg, int32_t* out_sizes, int32_t capacity) {
   return guarded([&] {
     AggResult& a = agg_of(result, agg);
-    REQUIRE(a.kind == PG_RESULT_DICTID_SET || a.kind == PG_RESULT_VALUE_SET, "aggregation is not a DISTINCTCOUNT");
+    REQUIRE(a.kind == PG_RESULT_DICTID_SET || a.kind == PG_RESULT_VALUE_SET || a.kind == PG_RESULT_VALUE_COUNTS, "aggregation is not a DISTINCTCOUNT or PERCENTILE");
     REQUIRE(capacity >= result->r->num_groups, "capacity too small");
     if (!a.set_sizes.empty()) memcpy(out_sizes, a.set_sizes.data(), a.set_sizes.size() * 4);
   });
@@ -466,9 +475,17 @@ int32_t pg_result_set_values_long(pg_result_t result, int32_t agg, int64_t* out_
 int32_t pg_result_set_values_double(pg_result_t result, int32_t agg, double* out_values, int64_t capacity) {
   return guarded([&] {
     AggResult& a = agg_of(result, agg);
-    REQUIRE(a.kind == PG_RESULT_VALUE_SET && a.set_value_kind >= 2, "aggregation is not a DISTINCTCOUNT over a raw FLOAT / DOUBLE column");
+    REQUIRE((a.kind == PG_RESULT_VALUE_SET && a.set_value_kind >= 2) || a.kind == PG_RESULT_VALUE_COUNTS, "aggregation is not a DISTINCTCOUNT over a raw FLOAT / DOUBLE column or a PERCENTILE");
     REQUIRE(capacity >= (int64_t)a.d[0].size(), "capacity too small");
     if (!a.d[0].empty()) memcpy(out_values, a.d[0].data(), a.d[0].size() * 8);
+  });
+}
+int32_t pg_result_set_counts(pg_result_t result, int32_t agg, int64_t* out_counts, int64_t capacity) {
+  return guarded([&] {
+    AggResult& a = agg_of(result, agg);
+    REQUIRE(a.kind == PG_RESULT_VALUE_COUNTS, "aggregation is not a PERCENTILE");
+    REQUIRE(capacity >= (int64_t)a.l[0].size(), "capacity too small");
+    if (!a.l[0].empty()) memcpy(out_counts, a.l[0].data(), a.l[0].size() * 8);
   });
 }
 int32_t pg_result_hll_registers(pg_result_t result, int32_t agg, uint8_t* out_registers, int64_t capacity) {

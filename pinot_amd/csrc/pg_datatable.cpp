@@ -24,6 +24,7 @@
 // values ascending by dictId, and the metadata section is empty (the server fills ExecutionStatistics in after the block is built).  Every
 // reader of the format rebuilds maps / sets from them.  No JVM exists in this image: the bytes are checked against an independent Python
 // restatement of builder AND reader (oracle/po_datatable.py) — parity unpinned against the reference itself.
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <unordered_map>
@@ -77,6 +78,7 @@ const char* function_name(int32_t fn) {   // AggregationFunctionType#getName().t
     case PG_AGG_MINMAXRANGEMV: return "minmaxrangemv";
     case PG_AGG_DISTINCTCOUNTMV: return "distinctcountmv";
     case PG_AGG_DISTINCTCOUNTHLLMV: return "distinctcounthllmv";
+    case PG_AGG_PERCENTILE: return "percentile";
     default: fail(PG_ERR_INTERNAL, "aggregation function %d has no name", fn);
   }
   return "";
@@ -127,6 +129,19 @@ std::vector<uint8_t> result_data_table_v4(const Result& r) {
     // CountAggregationFunction#getResultColumnName (:64-66): "count(*)" whatever the argument — unless null handling is on, where COUNT(col)
     // counts the non-null values of col and keeps its argument: "count(col)"
     const bool count_star = c.function == PG_AGG_COUNT && (!r.schema_null_handling || c.name == "*");
+    if (c.function == PG_AGG_PERCENTILE) {   // PercentileAggregationFunction#getResultColumnName: percentile95(col) / percentile(col, 99.9)
+      if (r.aggs[(size_t)a].kind != PG_RESULT_VALUE_COUNTS)
+        fail(PG_ERR_INVALID_ARGUMENT, "final PERCENTILE values (PG_QUERY_FLAG_FINAL_PERCENTILE) are not intermediate results: no data table");
+      const double p = r.aggs[(size_t)a].param;
+      char buf[64];
+      if (p == (double)(int)p) snprintf(buf, sizeof(buf), "percentile%d(", (int)p);
+      else snprintf(buf, sizeof(buf), "percentile(");
+      std::string nm = std::string(buf) + c.name;
+      if (p != (double)(int)p) { snprintf(buf, sizeof(buf), ", %.17g", p); for (int prec = 1; prec < 17; prec++) { char t[64]; snprintf(t, sizeof(t), ", %.*g", prec, p); if (strtod(t + 2, nullptr) == p) { snprintf(buf, sizeof(buf), "%s", t); break; } } nm += buf; }
+      names.push_back(nm + ")");
+      types.push_back(C_OBJECT);
+      continue;
+    }
     names.push_back(count_star ? std::string("count(*)") : std::string(function_name(c.function)) + "(" + c.name + ")");
     switch (r.aggs[(size_t)a].kind) {
       case PG_RESULT_LONG:
@@ -281,6 +296,19 @@ std::vector<uint8_t> result_data_table_v4(const Result& r) {
             default: type = 17; for (int32_t e = 0; e < n; e++) p.i64(ar.l[0][at + (size_t)e]); break;
           }
           object(type, p);
+          break;
+        }
+        case PG_RESULT_VALUE_COUNTS: {   // DoubleArrayList (ObjectSerDeUtils.java:482-511): int size, the doubles — the runs expanded, ascending
+          const int32_t n = ar.set_sizes[(size_t)i];
+          const size_t at = set_pos[(size_t)a];
+          set_pos[(size_t)a] += n;
+          int64_t total = 0;
+          for (int32_t e = 0; e < n; e++) total += ar.l[0][at + (size_t)e];
+          if (total > 0x0FFFFFFF) fail(PG_ERR_UNSUPPORTED, "PERCENTILE list of %lld values in a data table", (long long)total);
+          Out p;
+          p.i32((int32_t)total);
+          for (int32_t e = 0; e < n; e++) for (int64_t k = 0; k < ar.l[0][at + (size_t)e]; k++) p.f64(ar.d[0][at + (size_t)e]);
+          object(3, p);
           break;
         }
         default: fail(PG_ERR_INTERNAL, "result kind %d in a data table", ar.kind);

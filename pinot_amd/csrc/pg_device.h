@@ -462,6 +462,18 @@ struct PgDistinctCol {
   int32_t desc;          // the digit is card - 1 - id (ORDER BY ... DESC)
   int32_t pad;
 };
+#if defined(__HIPCC__)
+// id of `doc` in a fixed-bit column (MSB-first, big-endian 32-bit words; 1 <= bits <= 31).  The second word is read only when the value
+// straddles it, so the last value of the stream never reads past it.  Shared by the DISTINCT and PERCENTILE passes.
+__device__ __forceinline__ uint32_t pg_fixed_bit_id_at(const PgDistinctCol& c, uint32_t doc) {
+  const uint64_t bit0 = (uint64_t)doc * (uint32_t)c.bits;
+  const uint32_t* w = reinterpret_cast<const uint32_t*>(c.data) + (bit0 >> 5);
+  const uint32_t sh = (uint32_t)(bit0 & 31);
+  uint64_t win = (uint64_t)__builtin_bswap32(w[0]) << 32;
+  if (sh + (uint32_t)c.bits > 32) win |= __builtin_bswap32(w[1]);
+  return (uint32_t)(win >> (64u - sh - (uint32_t)c.bits)) & ((1u << c.bits) - 1u);
+}
+#endif
 struct PgDistinctArgs {
   const uint64_t* match;       // the filter's match words: bit b of word w is doc 64 w + b
   int64_t w_begin, w_end;      // the match words this pass reads
@@ -473,6 +485,55 @@ struct PgDistinctArgs {
   int64_t key_words;           // 32-bit words of a key bitmap
   const uint32_t* group_rank;  // first-doc pass: rank of the first key of every PG_DISTINCT_GROUP_WORDS-word group among the new keys
   uint32_t* first_doc;         // first-doc pass: per new key (by rank) its smallest matching docId
+};
+
+// ---- PERCENTILE (pg_kernels_percentile.hip) -----------------------------------------------------------------------------------------------------
+// One counting pass per percentile column: every matching doc adds 1 to the 32-bit counter key = groupKey x C + valueId of a dense table
+// [G][C] (G: the group columns' mixed-radix key space, C: the value column's cardinality; ids are dictIds or virtual-dictionary ids, both
+// value-ordered).  Tables of up to PG_PCTL_LDS_KEYS counters are kept per workgroup in LDS and flushed once; larger ones take global atomics.
+#define PG_PCTL_LDS_KEYS 32768   // 128 KiB of the CU's 160 KiB: one persistent workgroup per CU
+#define PG_PCTL_MAX_P 16         // percentiles of one column selected per launch
+struct PgPctlArgs {
+  const uint64_t* match;       // the filter's match words (bit b of word w is doc 64 w + b); NULL: every doc below n_docs matches
+  int64_t n_words;             // ceil(n_docs / 64)
+  int64_t n_docs;
+  int32_t n_gcols;
+  int32_t pad;
+  PgDistinctCol gcols[PG_MAX_GROUP_COLS];   // group columns (mult: weight of the digit in groupKey)
+  PgDistinctCol vcol;          // the value column's ids
+  uint32_t card;               // C
+  uint32_t n_keys;             // G x C (< 2^32)
+  uint32_t* table;             // [n_keys] counters in HBM, zeroed by the caller
+};
+// the sort tier (key spaces beyond the HBM budget): the 64-bit keys of the matching docs written compacted at offsets from the tiles' match
+// counts, sorted, run-length encoded; rank selection is a binary search per admitted group over the runs' cumulative counts
+struct PgPctlSortSelectArgs {
+  const uint64_t* run_keys;    // [n_runs] distinct keys, ascending
+  const uint64_t* run_cum;     // [n_runs] inclusive prefix sums of the runs' counts
+  int64_t n_runs;
+  const uint32_t* rows;        // [n_rows] group keys
+  int32_t n_rows;
+  uint32_t card;
+  int32_t n_p;
+  int32_t pad;
+  double p[PG_PCTL_MAX_P];
+  int64_t* totals;             // [n_rows]
+  uint32_t* nnz;               // [n_rows] runs of the row
+  int64_t* first_run;          // [n_rows] index of the row's first run
+  int32_t* sel;                // [n_rows][n_p]
+};
+// rank selection and run compaction over the rows of the table named by `rows` (group keys of the admitted groups)
+struct PgPctlSelectArgs {
+  const uint32_t* table;
+  const uint32_t* rows;        // [n_rows] group keys (row r of the table starts at rows[r] x card)
+  int32_t n_rows;
+  uint32_t card;
+  int32_t n_p;
+  int32_t pad;
+  double p[PG_PCTL_MAX_P];
+  int64_t* totals;             // [n_rows] values in the row (n)
+  uint32_t* nnz;               // [n_rows] non-zero counters in the row
+  int32_t* sel;                // [n_rows][n_p] the selected value id, -1 for an empty row
 };
 
 // Selection queries (pg_kernels_select.hip): the ORDER BY columns of a doc folded into one 64-bit order-space key (the K smallest keys are

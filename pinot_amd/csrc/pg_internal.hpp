@@ -387,6 +387,9 @@ struct AggResult {
   int64_t hll_stride = 0;
   std::vector<int64_t> hll_gids;
   int32_t log2m = 0;
+  // PG_RESULT_VALUE_COUNTS (PERCENTILE): set_sizes = runs per group, d[0] = the runs' values (ascending under Double.compare within a group),
+  // l[0] = their counts; `param` is the aggregation's p (also kept on a final PG_RESULT_DOUBLE: the data table names the column by it)
+  double param = 0;
 };
 // What pg_result_merge / pg_result_all_reduce need to merge two results of the same query and to re-assemble the groups:
 // the dense accumulator table [n_ops][G] + the statistics counters + the DISTINCTCOUNT / HLL regions, left in HBM.
@@ -445,6 +448,7 @@ struct Result {
   bool null_handling = false;   // the query ran with PG_QUERY_FLAG_NULL_HANDLING (its data table carries the columns' null bitmaps)
   bool distinct = false;        // PG_QUERY_FLAG_DISTINCT: the groups are the distinct tuples, no aggregation (never merged in the library)
   bool selection = false;       // PG_QUERY_FLAG_SELECTION: the groups are the selected rows (never merged in the library)
+  bool percentile = false;      // the query carried a PERCENTILE: its lists merge by value on the Java side (never merged in the library)
   pg_exec_stats stats{};
 };
 struct DocIdSet {
@@ -469,6 +473,20 @@ std::unique_ptr<Result> execute_query(Segment& seg, const pg_query& q, const Can
 constexpr int32_t kQueryFlagNullPartition = 0x40000000;
 std::unique_ptr<Result> execute_distinct(Segment& seg, const pg_query& q, const CancelToken* cancel);   // PG_QUERY_FLAG_DISTINCT (pg_exec.hip)
 std::unique_ptr<Result> execute_selection(Segment& seg, const pg_query& q, const CancelToken* cancel);  // PG_QUERY_FLAG_SELECTION (pg_exec.hip)
+// queries with a PERCENTILE aggregation (pg_exec_percentile.hip): the checks of the path (pg_query_supported), and the query itself — the
+// ordinary part through execute_query, one counting pass per distinct percentile column joined to its groups by key
+// the sort tier's runs (pg_kernels_percentile.hip): the matching docs' keys written compacted, sorted over their significant bits and run-length
+// encoded on `stream`; returns after the stream drained (the number of runs is read back)
+struct PctlSortRuns {
+  DeviceBuffer keys, cum;       // [n_runs] distinct keys ascending, inclusive prefix sums of their counts
+  DeviceBuffer counts;          // [n_runs] uint32
+  int64_t n_runs = 0;
+};
+size_t pctl_sort_bytes(int64_t n_matches);   // bytes of the work area (keys in and out, runs, rocprim's temporaries)
+void pctl_sort_build(const PgPctlArgs& A, int64_t n_matches, int key_bits, hipStream_t stream, PctlSortRuns& out);
+bool has_percentile(const pg_query& q);
+void percentile_check(Segment& seg, const pg_query& q);
+std::unique_ptr<Result> execute_percentile(Segment& seg, const pg_query& q, const CancelToken* cancel);
 std::unique_ptr<Result> execute_query_plain(Segment& seg, const pg_query& q, const CancelToken* cancel);   // ... the executor proper (pg_exec.hip)
 void fill_result_schema(Segment& seg, const pg_query& q, Result& r);
 int64_t hll_cardinality(const uint8_t* regs, int log2m);   // HyperLogLog#cardinality of one register row (pg_exec.hip)
@@ -531,6 +549,12 @@ struct Knobs {
   int64_t exact_stats_device_max_docs = (int64_t)1 << 27;   // PG_EXACT_STATS_DEVICE_MAX_DOCS: ... and where the device counts it (pg_filter_stats_tiles.h: ~1 ms per 10^8 docs)
   bool filter_stats_host = false;   // PG_FILTER_STATS_HOST: the iterator automaton always walks on the host (pg_filter_stats.cpp), also for shapes the device counts
   int64_t select_sort_max_bytes = (int64_t)8 << 30;   // PG_SELECT_SORT_MAX_BYTES: work area of a selection's sort tier (larger ones are refused)
+  // PERCENTILE (pg_exec_percentile.hip): counter tables of up to pctl_lds_max_keys 32-bit counters live in the workgroups' LDS (default and
+  // ceiling PG_PCTL_LDS_KEYS = 32 768: 128 KiB, one persistent workgroup per CU), up to pctl_hbm_max_bytes in HBM (default 256 MiB: 2^26
+  // counters); beyond that the sort tier runs.  Tests lower both to cross the boundaries on small segments.
+  int64_t pctl_lds_max_keys = 32768;          // PG_PCTL_LDS_MAX_KEYS
+  int64_t pctl_hbm_max_bytes = (int64_t)256 << 20;   // PG_PCTL_HBM_MAX_BYTES
+  int64_t pctl_sort_max_bytes = (int64_t)8 << 30;    // PG_PCTL_SORT_MAX_BYTES: work area of the sort tier (larger ones are refused by pg_query_exec, which alone knows the matches)
   int64_t limit_prefix_min_docs = (int64_t)1 << 20;   // PG_LIMIT_PREFIX_MIN_DOCS: smallest doc prefix of the numGroupsLimit admission pass (tests lower it)
   std::string oct_passes;      // PG_OCT_PASSES: cumulative fractions, e.g. "0.02,0.08,0.3,1"
   // pg_comm.cpp

@@ -21,14 +21,7 @@ namespace {
 
 // id of `doc` in a fixed-bit column (MSB-first, big-endian 32-bit words; 1 <= bits <= 31).  The second word is read only when the value
 // straddles it, so the last value of the stream never reads past it.
-DEVFN uint32_t distinct_id_at(const PgDistinctCol& c, uint32_t doc) {
-  const uint64_t bit0 = (uint64_t)doc * (uint32_t)c.bits;
-  const uint32_t* w = reinterpret_cast<const uint32_t*>(c.data) + (bit0 >> 5);
-  const uint32_t sh = (uint32_t)(bit0 & 31);
-  uint64_t win = (uint64_t)__builtin_bswap32(w[0]) << 32;
-  if (sh + (uint32_t)c.bits > 32) win |= __builtin_bswap32(w[1]);
-  return (uint32_t)(win >> (64u - sh - (uint32_t)c.bits)) & ((1u << c.bits) - 1u);
-}
+DEVFN uint32_t distinct_id_at(const PgDistinctCol& c, uint32_t doc) { return pg_fixed_bit_id_at(c, doc); }
 
 DEVFN uint64_t distinct_key_of(const PgDistinctArgs& a, uint32_t doc) {
   uint64_t key = 0;

@@ -428,6 +428,15 @@ class ResultsBlock:
                 flat = np.zeros(max(total, 1), dtype=np.float64 if floating else np.int64)
                 api.call("result_set_values_double" if floating else "result_set_values_long", h, a, flat.ctypes.data, total)
                 rb.arrays.append((k, sizes, flat[:total]))
+            elif k == capi.RESULT_VALUE_COUNTS:   # PERCENTILE: per group the ascending (value, count) runs of its DoubleArrayList
+                sizes = np.zeros(ng, dtype=np.int32)
+                api.call("result_set_sizes", h, a, sizes.ctypes.data, ng)
+                total = int(sizes.sum())
+                values = np.zeros(max(total, 1), dtype=np.float64)
+                counts = np.zeros(max(total, 1), dtype=np.int64)
+                api.call("result_set_values_double", h, a, values.ctypes.data, total)
+                api.call("result_set_counts", h, a, counts.ctypes.data, total)
+                rb.arrays.append((k, sizes, values[:total], counts[:total]))
             elif k == capi.RESULT_HLL:
                 m = 1 << (spec.log2m or 8)
                 regs = np.empty(max(ng * m, 1), dtype=np.uint8)
@@ -519,6 +528,12 @@ class ResultsBlock:
                         col.append(frozenset(arr[2][pos:pos + sz].tolist()))
                         pos += sz
                     cols.append(col)
+                elif k == capi.RESULT_VALUE_COUNTS:   # (values, counts) per group
+                    col, pos = [], 0
+                    for sz in arr[1]:
+                        col.append((arr[2][pos:pos + sz].copy(), arr[3][pos:pos + sz].copy()))
+                        pos += sz
+                    cols.append(col)
                 else:
                     cols.append([bytes(r) for r in arr[1]])
             for a, flags in getattr(self, "agg_nulls", {}).items():   # enableNullHandling: a NULL result
@@ -566,6 +581,23 @@ def hll_cardinality(registers: bytes) -> int:
             return (1 << 63) - 1
         return int(math.floor(m * math.log(m / zeros) + 0.5))
     return int(math.floor(est + 0.5))
+
+
+def percentile_expand(runs) -> np.ndarray:
+    """The reference's DoubleArrayList behind a PERCENTILE intermediate `(values, counts)`: every matching value, ascending."""
+    values, counts = runs
+    return np.repeat(np.asarray(values, dtype=np.float64), np.asarray(counts, dtype=np.int64))
+
+
+def percentile_final(runs, p: float) -> float:
+    """PercentileAggregationFunction#extractFinalResult (:155-171) over the runs: sorted[(int)((long) size * p / 100)], the last value for
+    p = 100, Double.NEGATIVE_INFINITY over an empty list."""
+    values, counts = runs
+    n = int(np.sum(counts))
+    if n == 0:
+        return float("-inf")
+    rank = n - 1 if p == 100.0 else int(float(n) * p / 100)
+    return float(values[int(np.searchsorted(np.cumsum(counts), rank, side="right"))])
 
 
 def hll_merge(a: bytes, b: bytes) -> bytes:

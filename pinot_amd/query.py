@@ -83,6 +83,7 @@ class AggregationSpec:
     function: str                  # COUNT / SUM / MIN / MAX / AVG / DISTINCTCOUNT / DISTINCTCOUNTHLL / MINMAXRANGE
     column: Optional[str] = None   # None for COUNT(*)
     log2m: int = 0
+    percentile: Optional[float] = None   # PERCENTILE: p in [0, 100]
 
 
 @dataclass
@@ -127,14 +128,43 @@ class QueryContext:
         out = []
         norm = lambda t: re.sub(r"\s+", "", t).upper()   # noqa: E731
         aggs = [norm(f"{a.function}({a.column or '*'}{',' + str(a.log2m) if a.log2m else ''})") for a in self.aggregations]
+        pctl = [(a.column, a.percentile) if a.function == "PERCENTILE" else None for a in self.aggregations]
         for text, asc in self.order_by:
             if text in self.group_by:
                 out.append((capi.ORDER_BY_GROUP_KEY, self.group_by.index(text), asc))
             elif norm(text) in aggs:
                 out.append((capi.ORDER_BY_AGGREGATION, aggs.index(norm(text)), asc))
+            elif _percentile_of_text(text) is not None and _percentile_of_text(text) in pctl:   # any of PERCENTILE's spellings names the same aggregation
+                out.append((capi.ORDER_BY_AGGREGATION, pctl.index(_percentile_of_text(text)), asc))
             else:
                 return None
         return out
+
+
+_PERCENTILE_LEGACY = re.compile(r"^PERCENTILE(\d+)$")
+_PERCENTILE_TEXT = re.compile(r"^PERCENTILE(\d*)\(([A-Za-z_][A-Za-z_0-9.$]*)(?:,'?([^')]+)'?)?\)$", re.I)
+
+
+def percentile_value(text) -> float:
+    """The p of PERCENTILE(col, p) / PERCENTILEp(col) (AggregationFunctionFactory: a numeric or quoted literal, 0 <= p <= 100)."""
+    try:
+        p = float(text)
+    except (TypeError, ValueError):
+        raise SqlError(f"bad percentile {text!r}")
+    if not (0.0 <= p <= 100.0):
+        raise SqlError(f"percentile {text} out of [0, 100]")
+    return p
+
+
+def _percentile_of_text(text: str):
+    """(column, p) of an ORDER BY expression text that spells a PERCENTILE, else None."""
+    m = _PERCENTILE_TEXT.match(re.sub(r"\s+", "", text))
+    if not m or bool(m.group(1)) == bool(m.group(3)):
+        return None
+    try:
+        return (m.group(2), percentile_value(m.group(1) or m.group(3)))
+    except SqlError:
+        return None
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -315,6 +345,22 @@ class _Parser:
                     raise SqlError(f"bad aggregation argument {c}")
                 col = c[1]
             log2m = 0
+            legacy = _PERCENTILE_LEGACY.match(fn)
+            if fn == "PERCENTILE" or legacy:   # PERCENTILE(col, 95) / (col, 99.9) / (col, '50') and the legacy PERCENTILE95(col)
+                if col is None:
+                    raise SqlError("PERCENTILE needs a column")
+                if legacy:
+                    p = percentile_value(legacy.group(1))
+                else:
+                    if self.peek() != ("op", ","):
+                        raise SqlError("PERCENTILE(col, p) needs its percentile")
+                    self.i += 1
+                    p = percentile_value(self.literal())
+                self.expect_op(")")
+                q.aggregations.append(AggregationSpec("PERCENTILE", col, 0, p))
+                if self.kw("AS"):
+                    self.i += 2
+                return
             if self.peek() == ("op", ","):
                 self.i += 1
                 log2m = int(self.literal())
@@ -461,6 +507,10 @@ class CQuery:
                 aggs[i].column = a.column.encode() if a.column else None
             self._keep.append(aggs)
             self.query.aggregations = aggs
+            if any(a.function == "PERCENTILE" for a in q.aggregations):
+                params = (C.c_double * na)(*[float(a.percentile) if a.percentile is not None else 0.0 for a in q.aggregations])
+                self._keep.append(params)
+                self.query.agg_params = params
         self.query.num_groups_limit = q.num_groups_limit
         self.query.max_initial_result_holder_capacity = q.max_initial_result_holder_capacity
         self.query.flags = q.flags | (capi.QUERY_FLAG_DISTINCT if q.distinct else 0) | (capi.QUERY_FLAG_SELECTION if q.selection else 0)
