@@ -190,7 +190,13 @@ typedef enum pg_agg_function {   /* AggregationFunctionType (subset named by nor
 typedef struct pg_agg_spec {
   int32_t function;       /* pg_agg_function */
   int32_t log2m;          /* DISTINCTCOUNTHLL: 0 => CommonConstants.Helix.DEFAULT_HYPERLOGLOG_LOG2M (8) */
-  const char* column;     /* NULL or "*" for COUNT(*) */
+  const char* column;     /* NULL or "*" for COUNT(*).  SUM / MIN / MAX / AVG / MINMAXRANGE also take an arithmetic expression here, as the text
+                             ExpressionContext#toString prints: fn(arg,arg,...) over add / sub / mult / div (aliases plus / minus / times /
+                             divide), single-value INT / LONG / FLOAT / DOUBLE columns and numeric literals (bare or single-quoted), e.g.
+                             "add(column1,column9)", "mult(price,'1.5')" — a column name cannot contain '(', so an argument holding one is
+                             an expression.  At most 15 operations and 8 distinct columns per expression, 4 distinct expressions per query
+                             (PG_ERR_UNSUPPORTED beyond); malformed text is PG_ERR_INVALID_ARGUMENT.  Evaluated in IEEE double, one rounded
+                             operation at a time in the reference's argument order; results that carry one are not merged in the library. */
 } pg_agg_spec;
 
 /* One ORDER BY expression of a group-by query, as TableResizer resolves it (pinot-core/.../core/data/table/TableResizer.java:129-161):

@@ -93,11 +93,18 @@ public final class NativeQuery implements AutoCloseable {
     for (AggregationFunction f : aggs) {
       int fn = function(f);
       List<ExpressionContext> args = f.getInputExpressions();
-      if (fn < 0 || args.size() > 1 || (args.size() == 1 && args.get(0).getType() != ExpressionContext.Type.IDENTIFIER)) {
+      if (fn < 0 || args.size() > 1) {
+        return null;
+      }
+      // the argument: a column, or — for SUM / MIN / MAX / AVG / MINMAXRANGE — an arithmetic expression over columns and literals, handed
+      // over as the text ExpressionContext#toString prints (pg_agg_spec.column; the library parses it, pg_expr.h)
+      String argument = args.isEmpty() ? "*" : args.get(0).getType() == ExpressionContext.Type.IDENTIFIER ? args.get(0).getIdentifier()
+          : takesExpression(fn) && isArithmetic(args.get(0)) ? args.get(0).toString() : null;
+      if (argument == null) {
         return null;
       }
       b.putInt(fn).putInt(0);   // log2m 0: DEFAULT_HYPERLOGLOG_LOG2M (a literal second argument is not expressible here)
-      putString(b, args.isEmpty() ? "*" : args.get(0).getIdentifier());
+      putString(b, argument);
       if (fn == 16) {   // PG_AGG_PERCENTILE: its p as one double right after the column (records without a PERCENTILE are unchanged)
         double p = percentileOf(f);
         if (!(p >= 0.0 && p <= 100.0)) {
@@ -370,6 +377,44 @@ public final class NativeQuery implements AutoCloseable {
     while ((b.position() & 3) != 0) {
       b.put((byte) 0);
     }
+  }
+
+  private static boolean takesExpression(int fn) {
+    return fn == 1 || fn == 2 || fn == 3 || fn == 4 || fn == 7;   // PG_AGG_SUM, _MIN, _MAX, _AVG, _MINMAXRANGE
+  }
+
+  /**
+   * A call of add / sub / mult / div or of their aliases plus / minus / times / divide (TransformFunctionType.java:47-50) whose arguments
+   * are identifiers, literals or such calls again.  Anything else — another function, a nested aggregation — stays with the Java plan.
+   */
+  static boolean isArithmetic(ExpressionContext e) {
+    if (e.getType() != ExpressionContext.Type.FUNCTION) {
+      return false;
+    }
+    FunctionContext f = e.getFunction();
+    if (f.getType() != FunctionContext.Type.TRANSFORM) {
+      return false;
+    }
+    switch (f.getFunctionName()) {
+      case "add":
+      case "plus":
+      case "sub":
+      case "minus":
+      case "mult":
+      case "times":
+      case "div":
+      case "divide":
+        break;
+      default:
+        return false;
+    }
+    for (ExpressionContext a : f.getArguments()) {
+      if (a.getType() == ExpressionContext.Type.FUNCTION ? !isArithmetic(a)
+          : a.getType() != ExpressionContext.Type.IDENTIFIER && a.getType() != ExpressionContext.Type.LITERAL) {
+        return false;
+      }
+    }
+    return true;
   }
 
   private static int estimate(QueryContext q) {

@@ -464,15 +464,16 @@ struct PgDistinctCol {
 };
 #if defined(__HIPCC__)
 // id of `doc` in a fixed-bit column (MSB-first, big-endian 32-bit words; 1 <= bits <= 31).  The second word is read only when the value
-// straddles it, so the last value of the stream never reads past it.  Shared by the DISTINCT and PERCENTILE passes.
-__device__ __forceinline__ uint32_t pg_fixed_bit_id_at(const PgDistinctCol& c, uint32_t doc) {
-  const uint64_t bit0 = (uint64_t)doc * (uint32_t)c.bits;
-  const uint32_t* w = reinterpret_cast<const uint32_t*>(c.data) + (bit0 >> 5);
+// straddles it, so the last value of the stream never reads past it.  Shared by the DISTINCT, PERCENTILE and expression passes.
+__device__ __forceinline__ uint32_t pg_fixed_bit_id(const uint8_t* data, int32_t bits, uint32_t doc) {
+  const uint64_t bit0 = (uint64_t)doc * (uint32_t)bits;
+  const uint32_t* w = reinterpret_cast<const uint32_t*>(data) + (bit0 >> 5);
   const uint32_t sh = (uint32_t)(bit0 & 31);
   uint64_t win = (uint64_t)__builtin_bswap32(w[0]) << 32;
-  if (sh + (uint32_t)c.bits > 32) win |= __builtin_bswap32(w[1]);
-  return (uint32_t)(win >> (64u - sh - (uint32_t)c.bits)) & ((1u << c.bits) - 1u);
+  if (sh + (uint32_t)bits > 32) win |= __builtin_bswap32(w[1]);
+  return (uint32_t)(win >> (64u - sh - (uint32_t)bits)) & ((1u << bits) - 1u);
 }
+__device__ __forceinline__ uint32_t pg_fixed_bit_id_at(const PgDistinctCol& c, uint32_t doc) { return pg_fixed_bit_id(c.data, c.bits, doc); }
 #endif
 struct PgDistinctArgs {
   const uint64_t* match;       // the filter's match words: bit b of word w is doc 64 w + b
@@ -568,6 +569,43 @@ struct PgSelectOutCol {
   const int64_t* vb_offsets;    // PG_SO_BYTES: numDocs + 1 offsets
   int32_t kind;                 // PgSelectOutKind
   int32_t bits;                 // PG_SO_DICT
+};
+
+// ---- arithmetic expressions inside aggregations (pg_kernels_expr.hip) ---------------------------------------------------------------------------
+// One accumulation pass for all expressions of a query: per matching doc the group key (as PgPctlArgs forms it), every operand column loaded
+// once as a double, the programs of pg_expr.h evaluated one rounded IEEE operation at a time, then the group's 64-bit slots updated — a table
+// [G][slots_per_group] of int64.  Per expression: four limbs of the exact fixed-point SUM (pg_fixed_point.h, L = 4, scale q), the MIN and the
+// MAX as order-preserving int64 keys of doubles; one doc count for AVG.  Unused slots are left out.
+#include "pg_expr_program.h"
+#define PG_EXPR_SUM_LIMBS 4
+#define PG_EXPR_MAX_SLOTS (PG_EXPR_MAX_EXPRS * (PG_EXPR_SUM_LIMBS + 2) + 1)
+#define PG_EXPR_LDS_SLOTS 16384   // 128 KiB of the CU's 160 KiB: one persistent workgroup per CU, as pg_pctl_lds
+enum PgExprAcc : int32_t { PG_EXPR_ACC_SUM = 1, PG_EXPR_ACC_MIN = 2, PG_EXPR_ACC_MAX = 4 };
+struct PgExprDesc {
+  int32_t first_step, n_steps;   // its steps in PgExprArgs::steps
+  int32_t acc;                   // PgExprAcc bits
+  int32_t q;                     // scale of the fixed-point SUM
+  int32_t sum_slot, min_slot, max_slot;   // first slot of each accumulator within the group's row (-1: none)
+  int32_t pad;
+};
+struct PgExprArgs {
+  const uint64_t* match;       // the filter's match words (bit b of word w is doc 64 w + b); NULL: every doc below n_docs matches
+  int64_t n_words;             // ceil(n_docs / 64)
+  int64_t n_docs;
+  int32_t n_gcols;
+  int32_t n_srcs;
+  int32_t n_exprs;
+  int32_t slots;               // slots per group
+  int32_t count_slot;          // the doc count's slot, -1 without an AVG
+  int32_t pad;
+  uint64_t n_groups;           // G (<= 2^32)
+  uint64_t n_slots;            // G x slots
+  int64_t* table;              // [G][slots] in HBM, every slot at its identity (pg_expr_init)
+  PgDistinctCol gcols[PG_MAX_GROUP_COLS];
+  PgValueSrc srcs[PG_EXPR_MAX_SRCS];
+  PgExprDesc exprs[PG_EXPR_MAX_EXPRS];
+  int64_t ident[PG_EXPR_MAX_SLOTS];   // per slot of a row: 0 (SUM limbs, count), INT64_MAX (MIN), INT64_MIN (MAX)
+  pg_expr_step steps[PG_EXPR_MAX_EXPRS * PG_EXPR_MAX_OPS];
 };
 
 struct PgTrimArgs {

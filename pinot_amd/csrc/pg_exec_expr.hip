@@ -1,0 +1,526 @@
+// Queries with an aggregation over an arithmetic expression — SUM / MIN / MAX / AVG / MINMAXRANGE whose pg_agg_spec.column is an expression
+// text (pg_expr.h: add / sub / mult / div over single-value numeric columns and literals): a side pass joined to the ordinary plan by group
+// key, after the PERCENTILE split (pg_exec_percentile.hip).
+//   1. The ordinary part — the query without its expression aggregations (COUNT(*) if nothing else remains) — runs through execute_query
+//      unchanged, never on a star-tree: it decides the groups, the numGroupsLimit admission and the other aggregations' results (a PERCENTILE
+//      among them takes its own side pass from there).  An ORDER BY that names an expression aggregation leaves the segment untrimmed.
+//   2. A bounds pass per (segment, expression text) over ALL docs (pg_expr_bounds): the largest finite |value| fixes the scale of the exact
+//      fixed-point SUM (pg_fixed_point.h, L = 4 limbs, q = E - 127 with every |value| < 2^E); an expression that yields a NaN / Inf anywhere in
+//      the segment is refused by pg_query_exec.  Cached in the segment (at most 256 texts, filled under its lock; the pass itself runs outside it).
+//   3. One accumulation pass for ALL expressions of the query over the filter's match words — the filter kernels and cached filter plan of the
+//      DISTINCT and PERCENTILE paths — into a table [G][slots] of int64: pg_expr_reg without GROUP BY, pg_expr_lds up to
+//      Knobs::expr_lds_max_slots slots, pg_expr_hbm up to Knobs::expr_hbm_max_bytes; beyond that the query is refused.
+//   4. The rows of the admitted groups are gathered on the device and joined to the ordinary part on the host.
+// The kernels are those of pg_kernels_expr.hip.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <limits>
+#include <set>
+#include <string>
+
+#include "pg_internal.hpp"
+#include "pg_expr.h"
+#include "pg_fixed_point.h"
+
+void pg_expr_launch_bounds(const PgExprArgs* args, unsigned long long* out, int grid, hipStream_t stream);
+void pg_expr_launch_init(const PgExprArgs* args, int grid, hipStream_t stream);
+void pg_expr_launch_pass(const PgExprArgs* args, int tier, int grid, hipStream_t stream);
+void pg_expr_launch_gather(const int64_t* table, const uint32_t* rows, int32_t n_rows, int32_t slots, uint64_t n_groups, int64_t* out, int grid, hipStream_t stream);
+
+namespace pg {
+namespace {
+
+double wall_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+const char* kWho = "expression";
+constexpr size_t kMaxCachedBounds = 256;   // Segment::expr_bounds entries per segment (some tens of bytes each)
+enum Tier { TIER_REG = 0, TIER_LDS = 1, TIER_HBM = 2 };
+const char* const kTierKernel[3] = {"pg_expr_reg", "pg_expr_lds", "pg_expr_hbm"};
+
+bool is_expression_agg(const pg_agg_spec& s) { return expr_is_expression(s.column); }
+
+const char* function_text(int32_t fn) {
+  switch (fn) {
+    case PG_AGG_COUNT: return "COUNT";
+    case PG_AGG_DISTINCTCOUNT: return "DISTINCTCOUNT";
+    case PG_AGG_DISTINCTCOUNTHLL: return "DISTINCTCOUNTHLL";
+    case PG_AGG_PERCENTILE: return "PERCENTILE";
+    case PG_AGG_COUNTMV: return "COUNTMV";
+    case PG_AGG_SUMMV: return "SUMMV";
+    case PG_AGG_MINMV: return "MINMV";
+    case PG_AGG_MAXMV: return "MAXMV";
+    case PG_AGG_AVGMV: return "AVGMV";
+    case PG_AGG_MINMAXRANGEMV: return "MINMAXRANGEMV";
+    case PG_AGG_DISTINCTCOUNTMV: return "DISTINCTCOUNTMV";
+    case PG_AGG_DISTINCTCOUNTHLLMV: return "DISTINCTCOUNTHLLMV";
+    default: return "this aggregation function";
+  }
+}
+
+struct ExprItem {
+  std::string text;
+  ExprProgram prog;
+  std::vector<int> src;     // per operand column of the program: its index among the query's sources
+  std::vector<int> aggs;    // the aggregations over it (indexes into the query's)
+  int32_t acc = 0;          // PgExprAcc bits
+  int32_t sum_slot = -1, min_slot = -1, max_slot = -1;
+  bool bounds_known = false;
+  Segment::ExprBounds bounds;
+};
+struct ExprPlan {
+  std::vector<Column*> group_cols, group_ids;
+  std::vector<uint64_t> mult;   // weight of the group column's digit (column 0 least significant)
+  uint64_t G = 1;
+  std::vector<ExprItem> exprs;
+  std::vector<Column*> srcs;    // the distinct operand columns of all expressions
+  int32_t slots = 0, count_slot = -1;
+  uint64_t n_slots = 0;
+  int tier = TIER_REG;
+  int n_columns_read = 0;       // distinct columns the query projects (ProjectOperator#getNumColumnsProjected)
+};
+
+void fill_src(PgValueSrc& S, const Column& c) {
+  S.data = c.fwd_dev.as<uint8_t>();
+  S.dict = c.has_dictionary ? c.dict_dev.ptr : nullptr;
+  S.col_kind = c.col_kind;
+  S.bits = c.bits;
+  S.val_type = c.val_type;
+  S.fx_q = 0;
+}
+
+int device_cus(int device) {
+  int cus = 0;
+  PG_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+  return std::max(cus, 1);
+}
+
+// the bounds pass of one expression over every doc of the segment (seg.mu NOT held: it only reads registered columns, which never change or
+// go away while the segment lives; the device is current)
+Segment::ExprBounds run_bounds(Segment& seg, const ExprItem& item, const std::vector<Column*>& cols) {
+  Segment::ExprBounds b;
+  if (seg.total_docs <= 0) return b;
+  PgExprArgs A;
+  memset(&A, 0, sizeof(A));
+  A.n_docs = seg.total_docs;
+  A.n_words = ((int64_t)seg.total_docs + 63) / 64;
+  A.n_srcs = (int32_t)cols.size();
+  A.n_exprs = 1;
+  A.count_slot = -1;
+  for (size_t i = 0; i < cols.size(); i++) fill_src(A.srcs[i], *cols[i]);
+  A.exprs[0].first_step = 0;
+  A.exprs[0].n_steps = item.prog.n_steps;
+  for (int k = 0; k < item.prog.n_steps; k++) A.steps[k] = item.prog.steps[k];
+  hipStream_t stream = thread_stream(seg.device);
+  DeviceBuffer out(16);
+  PG_HIP(hipMemsetAsync(out.ptr, 0, 16, stream));
+  const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)device_cus(seg.device) * 8, ((int64_t)seg.total_docs + 255) / 256));
+  pg_expr_launch_bounds(&A, out.as<unsigned long long>(), grid, stream);
+  PG_HIP(hipGetLastError());
+  unsigned long long h[2] = {0, 0};
+  PG_HIP(hipMemcpyAsync(h, out.ptr, sizeof(h), hipMemcpyDeviceToHost, stream));
+  PG_HIP(hipStreamSynchronize(stream));
+  double mx;
+  memcpy(&mx, &h[0], 8);
+  if (mx > 0) {
+    int e = 0;
+    (void)std::frexp(mx, &e);   // mx = f * 2^e, f in [0.5, 1): every finite |value| < 2^e
+    b.exp = e;
+  }
+  b.has_nonfinite = h[1] != 0;
+  return b;
+}
+
+[[noreturn]] void refuse_nonfinite(const ExprItem& item) {
+  fail(PG_ERR_UNSUPPORTED, "expression %s yields a NaN or an infinity in this segment (a division by zero, an overflow): the Java plan answers such a query", item.text.c_str());
+}
+
+ExprPlan expr_plan(Segment& seg, const pg_query& q, bool compute_bounds) {
+  if (q.n_aggregations <= 0 || !q.aggregations) fail(PG_ERR_INVALID_ARGUMENT, "query has no aggregation");
+  if (q.n_group_by < 0 || (q.n_group_by > 0 && !q.group_by_columns)) fail(PG_ERR_INVALID_ARGUMENT, "group_by_columns is null");
+  if (q.n_group_by > PG_MAX_GROUP_COLS) fail(PG_ERR_UNSUPPORTED, "an aggregation over an expression with more than %d group-by columns", PG_MAX_GROUP_COLS);
+  const bool null_handling = (q.flags & PG_QUERY_FLAG_NULL_HANDLING) != 0;
+  ExprPlan P;
+  std::set<std::string> read;
+  bool need_count = false;
+  if (compute_bounds) use_device(seg.device);
+  std::unique_lock<std::mutex> lock(seg.mu);   // virtual dictionaries and the bounds cache are filled under the segment's lock
+  for (int a = 0; a < q.n_aggregations; a++) {
+    const pg_agg_spec& s = q.aggregations[a];
+    if (!is_expression_agg(s)) {
+      if (s.column && strcmp(s.column, "*") != 0) read.insert(s.column);
+      continue;
+    }
+    int32_t acc = 0;
+    switch (s.function) {
+      case PG_AGG_SUM: acc = PG_EXPR_ACC_SUM; break;
+      case PG_AGG_MIN: acc = PG_EXPR_ACC_MIN; break;
+      case PG_AGG_MAX: acc = PG_EXPR_ACC_MAX; break;
+      case PG_AGG_AVG: acc = PG_EXPR_ACC_SUM; need_count = true; break;
+      case PG_AGG_MINMAXRANGE: acc = PG_EXPR_ACC_MIN | PG_EXPR_ACC_MAX; break;
+      default:
+        fail(PG_ERR_UNSUPPORTED, "%s over an expression (%s): SUM, MIN, MAX, AVG and MINMAXRANGE take one on the GPU path", function_text(s.function), s.column);
+    }
+    size_t k = 0;
+    while (k < P.exprs.size() && P.exprs[k].text != s.column) k++;
+    if (k == P.exprs.size()) {
+      if (k >= PG_EXPR_MAX_EXPRS) fail(PG_ERR_UNSUPPORTED, "more than %d distinct expressions in the aggregations of one query", PG_EXPR_MAX_EXPRS);
+      ExprItem item;
+      item.text = s.column;
+      std::string error;
+      const int32_t st = expr_parse(s.column, item.prog, error);
+      if (st != PG_OK) fail(st, "%s (in %s)", error.c_str(), item.text.size() > 200 ? (item.text.substr(0, 197) + "...").c_str() : item.text.c_str());
+      std::vector<Column*> cols;
+      for (const std::string& name : item.prog.columns) {
+        Column* c = seg.find(name.c_str());
+        if (!c) fail(PG_ERR_NOT_FOUND, "column not found: %s", name.size() > 200 ? (name.substr(0, 197) + "...").c_str() : name.c_str());
+        if (c->is_mv || c->raw_mv) fail(PG_ERR_UNSUPPORTED, "expression over the multi-value column %s", c->name.c_str());
+        if (c->data_type > PG_TYPE_DOUBLE) fail(PG_ERR_UNSUPPORTED, "expression over the %s column %s", c->data_type == PG_TYPE_STRING ? "STRING" : "BYTES", c->name.c_str());
+        if (null_handling && column_has_nulls(seg, c->name)) fail(PG_ERR_UNSUPPORTED, "enableNullHandling: expression over %s, which holds nulls", c->name.c_str());
+        const bool dict_ok = c->has_dictionary && c->col_kind == PG_COL_FIXED_BIT && c->bits >= 1 && c->bits <= 31 && c->cardinality >= 1 && c->dict_dev.ptr;
+        const bool raw_ok = !c->has_dictionary && (c->col_kind == PG_COL_RAW32 || c->col_kind == PG_COL_RAW64);
+        if (!dict_ok && !raw_ok) fail(PG_ERR_UNSUPPORTED, "expression: operand column %s (layout %d, %d bits)", c->name.c_str(), c->col_kind, c->bits);
+        read.insert(c->name);
+        cols.push_back(c);
+        size_t j = 0;
+        while (j < P.srcs.size() && P.srcs[j] != c) j++;
+        if (j == P.srcs.size()) {
+          if (j >= PG_EXPR_MAX_SRCS) fail(PG_ERR_UNSUPPORTED, "the expressions of one query over more than %d distinct columns", PG_EXPR_MAX_SRCS);
+          P.srcs.push_back(c);
+        }
+        item.src.push_back((int)j);
+      }
+      auto cached = seg.expr_bounds.find(item.text);
+      if (cached != seg.expr_bounds.end()) {
+        item.bounds = cached->second;
+        item.bounds_known = true;
+      } else if (compute_bounds) {
+        // the pass runs WITHOUT the segment's lock — a full-segment kernel must not stall the other planners of the segment; two threads
+        // that meet on a new text both run it and find the same answer.  The cache is bounded: texts that differ only in a literal are
+        // entries of their own, so at kMaxCachedBounds the map is emptied and fills again (a text then costs one more pass)
+        lock.unlock();
+        item.bounds = run_bounds(seg, item, cols);
+        lock.lock();
+        item.bounds_known = true;
+        if (seg.expr_bounds.size() >= kMaxCachedBounds) seg.expr_bounds.clear();
+        seg.expr_bounds.emplace(item.text, item.bounds);
+      }
+      if (item.bounds_known && item.bounds.has_nonfinite) refuse_nonfinite(item);
+      P.exprs.push_back(std::move(item));
+    }
+    P.exprs[k].acc |= acc;
+    P.exprs[k].aggs.push_back(a);
+  }
+  for (int j = 0; j < q.n_group_by; j++) {
+    const char* name = q.group_by_columns[j];
+    Column* c = name ? seg.find(name) : nullptr;
+    if (!c) fail(PG_ERR_NOT_FOUND, "column not found: %s", name ? name : "(null)");
+    if (c->is_mv || c->raw_mv) fail(PG_ERR_UNSUPPORTED, "an aggregation over an expression next to the multi-value group-by column %s", c->name.c_str());
+    if (null_handling && column_has_nulls(seg, c->name)) fail(PG_ERR_UNSUPPORTED, "enableNullHandling: an aggregation over an expression grouped by %s, which holds nulls", c->name.c_str());
+    read.insert(name);
+    Column* id = id_column(seg, *c, "group-by", kWho);
+    P.group_cols.push_back(c);
+    P.group_ids.push_back(id);
+    P.mult.push_back(P.G);
+    P.G *= (uint64_t)id->cardinality;
+    if (P.G > ((uint64_t)1 << 32)) fail(PG_ERR_UNSUPPORTED, "an aggregation over an expression: group key space over 2^32 (the product of the group-by columns' cardinalities)");
+  }
+  P.n_columns_read = (int)read.size();
+  // the group's row: per expression the SUM's limbs, the MIN, the MAX, as far as an aggregation asks for them; one doc count for AVG
+  for (ExprItem& item : P.exprs) {
+    if (item.acc & PG_EXPR_ACC_SUM) { item.sum_slot = P.slots; P.slots += PG_EXPR_SUM_LIMBS; }
+    if (item.acc & PG_EXPR_ACC_MIN) item.min_slot = P.slots++;
+    if (item.acc & PG_EXPR_ACC_MAX) item.max_slot = P.slots++;
+  }
+  if (need_count) P.count_slot = P.slots++;
+  P.n_slots = P.G * (uint64_t)P.slots;   // < 2^37
+  const Knobs& K = knobs();
+  if (q.n_group_by == 0) P.tier = TIER_REG;
+  else if (P.n_slots <= (uint64_t)std::min<int64_t>(K.expr_lds_max_slots, PG_EXPR_LDS_SLOTS)) P.tier = TIER_LDS;
+  else if (P.n_slots * 8 <= (uint64_t)K.expr_hbm_max_bytes) P.tier = TIER_HBM;
+  else
+    fail(PG_ERR_UNSUPPORTED, "aggregations over expressions: %llu groups x %d slots need a table of %llu bytes, more than PG_EXPR_HBM_MAX_BYTES (%lld)",
+         (unsigned long long)P.G, P.slots, (unsigned long long)(P.n_slots * 8), (long long)K.expr_hbm_max_bytes);
+  return P;
+}
+
+// the ordinary part: the query without its expression aggregations (COUNT(*) if nothing else remains), never on a star-tree, its ORDER BY
+// re-indexed — or dropped when it names an expression aggregation: the segment is then not trimmed
+struct BaseQuery {
+  std::vector<pg_agg_spec> aggs;
+  std::vector<double> params;
+  std::vector<pg_order_by> order;
+  std::vector<int> base_index;   // per aggregation of the query: its index in the ordinary part, -1 for one over an expression
+  pg_query q;
+};
+void base_query(const pg_query& q, BaseQuery& out) {
+  out.base_index.assign((size_t)q.n_aggregations, -1);
+  for (int a = 0; a < q.n_aggregations; a++) {
+    if (is_expression_agg(q.aggregations[a])) continue;
+    out.base_index[(size_t)a] = (int)out.aggs.size();
+    out.aggs.push_back(q.aggregations[a]);
+    out.params.push_back(q.agg_params ? q.agg_params[a] : 0.0);
+  }
+  if (out.aggs.empty()) {
+    pg_agg_spec count_star;
+    memset(&count_star, 0, sizeof(count_star));
+    count_star.function = PG_AGG_COUNT;
+    out.aggs.push_back(count_star);
+    out.params.push_back(0.0);
+  }
+  pg_query& b = out.q;
+  b = q;
+  b.aggregations = out.aggs.data();
+  b.n_aggregations = (int32_t)out.aggs.size();
+  b.agg_params = q.agg_params ? out.params.data() : nullptr;
+  b.flags = (q.flags | PG_QUERY_FLAG_SKIP_STAR_TREE) & ~PG_QUERY_FLAG_KEEP_DEVICE_TABLE;
+  if (q.n_order_by > 0 && q.order_by) {
+    bool by_expression = false;
+    for (int32_t i = 0; i < q.n_order_by; i++) {
+      pg_order_by ob = q.order_by[i];
+      if (ob.kind == PG_ORDER_BY_AGGREGATION) {
+        if (ob.index < 0 || ob.index >= q.n_aggregations) fail(PG_ERR_INVALID_ARGUMENT, "ORDER BY aggregation %d of %d", ob.index, q.n_aggregations);
+        if (out.base_index[(size_t)ob.index] < 0) by_expression = true;
+        else ob.index = out.base_index[(size_t)ob.index];
+      }
+      out.order.push_back(ob);
+    }
+    if (by_expression) { b.n_order_by = 0; b.order_by = nullptr; }
+    else b.order_by = out.order.data();
+  }
+}
+
+double order_key_to_double(int64_t k) {
+  const int64_t b = k ^ ((k >> 63) & 0x7FFFFFFFFFFFFFFFLL);
+  double d;
+  memcpy(&d, &b, 8);
+  return d;
+}
+
+}  // namespace
+
+bool has_expression(const pg_query& q) {
+  if (q.flags & (PG_QUERY_FLAG_DISTINCT | PG_QUERY_FLAG_SELECTION)) return false;
+  if (!q.aggregations) return false;
+  for (int a = 0; a < q.n_aggregations; a++) if (is_expression_agg(q.aggregations[a])) return true;
+  return false;
+}
+
+void expression_check(Segment& seg, const pg_query& q) {
+  (void)expr_plan(seg, q, false);
+  BaseQuery B;   // ... and what the ordinary part refuses
+  base_query(q, B);
+  if (has_percentile(B.q)) { percentile_check(seg, B.q); return; }
+  check_null_handling(seg, B.q);
+  (void)get_plan(seg, B.q.filter, &B.q);
+}
+
+std::unique_ptr<Result> execute_expression(Segment& seg, const pg_query& q, const CancelToken* cancel) {
+  const double t0 = wall_ms();
+  use_device(seg.device);
+  const ExprPlan P = expr_plan(seg, q, true);
+  const double t_plan = wall_ms();
+  // ---- the ordinary part ------------------------------------------------------------------------------------------------------------------
+  BaseQuery B;
+  base_query(q, B);
+  std::unique_ptr<Result> res = execute_query(seg, B.q, cancel);
+  use_device(seg.device);
+  hipStream_t stream = thread_stream(seg.device);
+  const int32_t n_rows = q.n_group_by > 0 ? res->num_groups : 1;
+  // ---- the filter's match words (none without a filter and without an upsert snapshot) ---------------------------------------------------
+  bool snapshot = false;
+  {
+    std::lock_guard<std::mutex> lock(seg.mu);
+    snapshot = seg.queryable_doc_ids != nullptr;
+  }
+  std::unique_ptr<DocIdSet> ds;
+  int64_t M = seg.total_docs;
+  if (q.filter || snapshot) {
+    ds = execute_filter(seg, q.filter, q.flags & PG_QUERY_FLAG_NULL_HANDLING);
+    M = ds->cardinality;
+  }
+  if (cancel && cancel->requested.load(std::memory_order_acquire)) fail(PG_ERR_CANCELLED, "query cancelled (EarlyTerminationException)");
+  // ---- the admitted groups' keys -------------------------------------------------------------------------------------------------------------
+  std::vector<uint32_t> rows((size_t)n_rows, 0);
+  for (int j = 0; j < q.n_group_by; j++) {
+    const std::vector<uint32_t> ids = group_ids_of(*res, j, *P.group_cols[(size_t)j], *P.group_ids[(size_t)j], n_rows, kWho);
+    for (int32_t i = 0; i < n_rows; i++) {
+      if (ids[(size_t)i] >= (uint32_t)P.group_ids[(size_t)j]->cardinality) fail(PG_ERR_INTERNAL, "expression: group key id %u of %s out of range", ids[(size_t)i], P.group_cols[(size_t)j]->name.c_str());
+      rows[(size_t)i] += (uint32_t)(ids[(size_t)i] * P.mult[(size_t)j]);
+    }
+  }
+  const int cus = device_cus(seg.device);
+  const int64_t n_words = ((int64_t)seg.total_docs + 63) / 64;
+  // ---- the accumulation pass -------------------------------------------------------------------------------------------------------------------
+  PgExprArgs A;
+  memset(&A, 0, sizeof(A));
+  A.match = ds ? ds->words.as<uint64_t>() : nullptr;
+  A.n_words = n_words;
+  A.n_docs = seg.total_docs;
+  A.n_gcols = q.n_group_by;
+  A.n_srcs = (int32_t)P.srcs.size();
+  A.n_exprs = (int32_t)P.exprs.size();
+  A.slots = P.slots;
+  A.count_slot = P.count_slot;
+  A.n_groups = P.G;
+  A.n_slots = P.n_slots;
+  int64_t doc_bits = 0;
+  for (int j = 0; j < q.n_group_by; j++) {
+    A.gcols[j].data = P.group_ids[(size_t)j]->fwd_dev.as<uint8_t>();
+    A.gcols[j].bits = P.group_ids[(size_t)j]->bits;
+    A.gcols[j].card = P.group_ids[(size_t)j]->cardinality;
+    A.gcols[j].mult = P.mult[(size_t)j];
+    doc_bits += P.group_ids[(size_t)j]->bits;
+  }
+  for (size_t i = 0; i < P.srcs.size(); i++) {
+    fill_src(A.srcs[i], *P.srcs[i]);
+    doc_bits += P.srcs[i]->col_kind == PG_COL_FIXED_BIT ? P.srcs[i]->bits : (P.srcs[i]->col_kind == PG_COL_RAW32 ? 32 : 64);
+  }
+  int32_t n_steps = 0;
+  for (size_t e = 0; e < P.exprs.size(); e++) {
+    const ExprItem& item = P.exprs[e];
+    PgExprDesc& X = A.exprs[e];
+    X.first_step = n_steps;
+    X.n_steps = item.prog.n_steps;
+    X.acc = item.acc;
+    X.q = item.bounds.exp - (32 * PG_EXPR_SUM_LIMBS - 1);
+    X.sum_slot = item.sum_slot;
+    X.min_slot = item.min_slot;
+    X.max_slot = item.max_slot;
+    for (int k = 0; k < item.prog.n_steps; k++) {
+      pg_expr_step st = item.prog.steps[k];   // the program's column indexes -> the query's sources
+      if (st.a >= 0 && st.a < PG_EXPR_MAX_SRCS) st.a = item.src[(size_t)st.a];
+      if (st.b >= 0 && st.b < PG_EXPR_MAX_SRCS) st.b = item.src[(size_t)st.b];
+      A.steps[n_steps++] = st;
+    }
+    if (item.min_slot >= 0) A.ident[item.min_slot] = INT64_MAX;
+    if (item.max_slot >= 0) A.ident[item.max_slot] = INT64_MIN;
+  }
+  DeviceBuffer table((size_t)P.n_slots * 8);
+  A.table = table.as<int64_t>();
+  // PG_QUERY_FLAG_PROFILE: the pass (initialisation, accumulation, gather and its copy) between two events of its own
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  struct EventGuard {
+    hipEvent_t* e;
+    ~EventGuard() { for (int i = 0; i < 2; i++) if (e[i]) (void)hipEventDestroy(e[i]); }
+  } ev_guard{ev};
+  if (q.flags & PG_QUERY_FLAG_PROFILE) {
+    PG_HIP(hipEventCreate(&ev[0]));
+    PG_HIP(hipEventCreate(&ev[1]));
+    PG_HIP(hipEventRecord(ev[0], stream));
+  }
+  pg_expr_launch_init(&A, (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)cus * 8, ((int64_t)P.n_slots + 255) / 256)), stream);
+  PG_HIP(hipGetLastError());
+  if (M > 0 && n_words > 0) {
+    const int64_t words_per_wg = P.tier == TIER_LDS ? 32 : 16;
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(P.tier == TIER_LDS ? cus : cus * 8, (n_words + words_per_wg - 1) / words_per_wg));
+    pg_expr_launch_pass(&A, P.tier, grid, stream);
+    PG_HIP(hipGetLastError());
+  }
+  std::vector<int64_t> got((size_t)n_rows * (size_t)P.slots);
+  if (n_rows > 0) {
+    DeviceBuffer d_rows((size_t)n_rows * 4), d_out(got.size() * 8);
+    PG_HIP(hipMemcpyAsync(d_rows.ptr, rows.data(), (size_t)n_rows * 4, hipMemcpyHostToDevice, stream));
+    pg_expr_launch_gather(table.as<int64_t>(), d_rows.as<uint32_t>(), n_rows, P.slots, P.G, d_out.as<int64_t>(),
+                          (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)cus * 8, ((int64_t)got.size() + 255) / 256)), stream);
+    PG_HIP(hipGetLastError());
+    PG_HIP(hipMemcpyAsync(got.data(), d_out.ptr, got.size() * 8, hipMemcpyDeviceToHost, stream));
+    wait_stream(stream, cancel);   // d_rows and d_out go out of scope
+  } else {
+    wait_stream(stream, cancel);
+  }
+  float pass_ms = 0;
+  if (ev[0]) {
+    PG_HIP(hipEventRecord(ev[1], stream));
+    PG_HIP(hipEventSynchronize(ev[1]));
+    PG_HIP(hipEventElapsedTime(&pass_ms, ev[0], ev[1]));
+  }
+  // ---- the expression aggregations' results: the reference's defaults over no doc fall out of the identities -----------------------------------
+  std::vector<AggResult> out((size_t)q.n_aggregations);
+  for (const ExprItem& item : P.exprs) {
+    const int fx_q = item.bounds.exp - (32 * PG_EXPR_SUM_LIMBS - 1);
+    auto sum_of = [&](int32_t i) { return pg_limbs_to_double(&got[(size_t)i * (size_t)P.slots + (size_t)item.sum_slot], PG_EXPR_SUM_LIMBS, fx_q); };
+    auto min_of = [&](int32_t i) {
+      const int64_t k = got[(size_t)i * (size_t)P.slots + (size_t)item.min_slot];
+      return k == INT64_MAX ? std::numeric_limits<double>::infinity() : order_key_to_double(k);   // MinAggregationFunction's default
+    };
+    auto max_of = [&](int32_t i) {
+      const int64_t k = got[(size_t)i * (size_t)P.slots + (size_t)item.max_slot];
+      return k == INT64_MIN ? -std::numeric_limits<double>::infinity() : order_key_to_double(k);
+    };
+    for (int a : item.aggs) {
+      AggResult& r = out[(size_t)a];
+      switch (q.aggregations[a].function) {
+        case PG_AGG_SUM:
+          r.kind = PG_RESULT_DOUBLE;
+          r.d[0].resize((size_t)n_rows);
+          for (int32_t i = 0; i < n_rows; i++) r.d[0][(size_t)i] = sum_of(i);
+          break;
+        case PG_AGG_MIN:
+          r.kind = PG_RESULT_DOUBLE;
+          r.d[0].resize((size_t)n_rows);
+          for (int32_t i = 0; i < n_rows; i++) r.d[0][(size_t)i] = min_of(i);
+          break;
+        case PG_AGG_MAX:
+          r.kind = PG_RESULT_DOUBLE;
+          r.d[0].resize((size_t)n_rows);
+          for (int32_t i = 0; i < n_rows; i++) r.d[0][(size_t)i] = max_of(i);
+          break;
+        case PG_AGG_AVG:
+          r.kind = PG_RESULT_AVG_PAIR;
+          r.d[0].resize((size_t)n_rows);
+          r.l[0].resize((size_t)n_rows);
+          for (int32_t i = 0; i < n_rows; i++) { r.d[0][(size_t)i] = sum_of(i); r.l[0][(size_t)i] = got[(size_t)i * (size_t)P.slots + (size_t)P.count_slot]; }
+          break;
+        default:   // PG_AGG_MINMAXRANGE
+          r.kind = PG_RESULT_MINMAX_PAIR;
+          r.d[0].resize((size_t)n_rows);
+          r.d[1].resize((size_t)n_rows);
+          for (int32_t i = 0; i < n_rows; i++) { r.d[0][(size_t)i] = min_of(i); r.d[1][(size_t)i] = max_of(i); }
+          break;
+      }
+    }
+  }
+  if (q.n_group_by == 0 && P.count_slot >= 0 && got[(size_t)P.count_slot] != M)
+    fail(PG_ERR_INTERNAL, "expression: %lld docs counted for %lld matching docs", (long long)got[(size_t)P.count_slot], (long long)M);
+  // ---- the joined result ------------------------------------------------------------------------------------------------------------------------
+  std::vector<std::vector<uint8_t>> nulls;
+  if (!res->agg_nulls.empty()) nulls.assign((size_t)q.n_aggregations, {});
+  for (int a = 0; a < q.n_aggregations; a++) {
+    const int bi = B.base_index[(size_t)a];
+    if (bi < 0) continue;
+    out[(size_t)a] = std::move(res->aggs[(size_t)bi]);
+    if (!nulls.empty() && (size_t)bi < res->agg_nulls.size()) nulls[(size_t)a] = std::move(res->agg_nulls[(size_t)bi]);
+  }
+  res->aggs = std::move(out);
+  res->agg_nulls = std::move(nulls);
+  res->dev.reset();
+  res->expression = true;
+  pg_exec_stats& st = res->stats;
+  st.num_docs_scanned = M;
+  st.num_entries_scanned_post_filter = M * P.n_columns_read;
+  if (ds) {
+    st.num_entries_scanned_in_filter = ds->stats.num_entries_scanned_in_filter;
+    st.stats_exact = ds->stats.stats_exact;
+    st.filter_stats_path = ds->stats.filter_stats_path;
+    st.device_ms_filter += ds->stats.device_ms_filter;
+  } else {
+    st.num_entries_scanned_in_filter = 0;
+    st.stats_exact = 1;
+  }
+  st.device_ms_aggregate += pass_ms;
+  st.device_ms_total += pass_ms + (ds ? ds->stats.device_ms_filter : 0.0f);
+  st.num_total_docs = seg.total_docs;
+  st.star_tree_index = -1;
+  st.algorithmic_bytes += ((int64_t)seg.total_docs * doc_bits + 7) / 8 + (ds ? n_words * 8 : 0);
+  snprintf(st.kernel, sizeof(st.kernel), "%s", kTierKernel[P.tier]);
+  fill_result_schema(seg, q, *res);
+  res->null_handling = (q.flags & PG_QUERY_FLAG_NULL_HANDLING) != 0;
+  st.host_ms_plan += (float)(t_plan - t0);
+  st.host_ms_total = (float)(wall_ms() - t0);
+  return res;
+}
+
+}  // namespace pg

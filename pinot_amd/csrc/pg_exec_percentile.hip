@@ -32,9 +32,6 @@ void pg_pctl_launch_sort_runs(const uint64_t* run_keys, const uint32_t* run_coun
                               uint32_t card, const int64_t* offsets, uint32_t* out_ids, uint32_t* out_counts, int grid, hipStream_t stream);
 
 namespace pg {
-namespace {
-
-double wall_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 bool column_has_nulls(Segment& seg, const std::string& name) {   // seg.mu held
   auto it = seg.null_vectors.find(name);
@@ -42,18 +39,37 @@ bool column_has_nulls(Segment& seg, const std::string& name) {   // seg.mu held
 }
 
 // the column of fixed-bit, value-ordered ids behind `c`: its own dictIds, or its virtual dictionary's (seg.mu held)
-Column* id_column(Segment& seg, Column& c, const char* what) {
+Column* id_column(Segment& seg, Column& c, const char* what, const char* who) {
   Column* id = &c;
   if (!c.has_dictionary) {
     if (c.col_kind != PG_COL_RAW32 && c.col_kind != PG_COL_RAW64 && c.col_kind != PG_COL_VAR_BYTES)
-      fail(PG_ERR_UNSUPPORTED, "PERCENTILE: %s column %s (layout %d)", what, c.name.c_str(), c.col_kind);
+      fail(PG_ERR_UNSUPPORTED, "%s: %s column %s (layout %d)", who, what, c.name.c_str(), c.col_kind);
     ensure_virtual_dictionary(seg, c);
     id = c.vdict.get();
   }
   if (id->cardinality < 1 || id->bits < 1 || id->bits > 31)
-    fail(PG_ERR_UNSUPPORTED, "PERCENTILE: %s column %s has %d values in %d bits", what, c.name.c_str(), id->cardinality, id->bits);
+    fail(PG_ERR_UNSUPPORTED, "%s: %s column %s has %d values in %d bits", who, what, c.name.c_str(), id->cardinality, id->bits);
   return id;
 }
+
+void wait_stream(hipStream_t stream, const CancelToken* cancel) {
+  if (cancel) {
+    for (;;) {
+      const hipError_t e = hipStreamQuery(stream);
+      if (e == hipSuccess) return;
+      if (e != hipErrorNotReady) PG_HIP(e);
+      if (cancel->requested.load(std::memory_order_acquire)) {
+        (void)hipStreamSynchronize(stream);   // let what was launched finish
+        fail(PG_ERR_CANCELLED, "query cancelled (EarlyTerminationException)");
+      }
+    }
+  }
+  PG_HIP(hipStreamSynchronize(stream));
+}
+
+namespace {
+
+double wall_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 struct PctlColumn {
   Column* col = nullptr;    // the column the segment knows by name
@@ -133,31 +149,18 @@ double value_of_id(const Column& col, const Column& ids, int32_t id) {   // Dict
   return d;
 }
 
-void wait_stream(hipStream_t stream, const CancelToken* cancel) {
-  if (cancel) {
-    for (;;) {
-      const hipError_t e = hipStreamQuery(stream);
-      if (e == hipSuccess) return;
-      if (e != hipErrorNotReady) PG_HIP(e);
-      if (cancel->requested.load(std::memory_order_acquire)) {
-        (void)hipStreamSynchronize(stream);   // let what was launched finish
-        fail(PG_ERR_CANCELLED, "query cancelled (EarlyTerminationException)");
-      }
-    }
-  }
-  PG_HIP(hipStreamSynchronize(stream));
-}
+}  // namespace
 
-// the id of every admitted group's key in group-by column j of the percentile pass
-std::vector<uint32_t> group_ids_of(const Result& r, int j, const Column& col, const Column& ids, int32_t n_rows) {
+// the id of every admitted group's key in group-by column j of a side pass
+std::vector<uint32_t> group_ids_of(const Result& r, int j, const Column& col, const Column& ids, int32_t n_rows, const char* who) {
   std::vector<uint32_t> out((size_t)n_rows);
   const int32_t kt = r.group_key_type.empty() ? PG_GROUP_KEY_DICT_IDS : r.group_key_type[(size_t)j];
   if (kt == PG_GROUP_KEY_DICT_IDS) {
-    if (!col.has_dictionary) fail(PG_ERR_INTERNAL, "PERCENTILE: dictIds for the raw group-by column %s", col.name.c_str());
+    if (!col.has_dictionary) fail(PG_ERR_INTERNAL, "%s: dictIds for the raw group-by column %s", who, col.name.c_str());
     for (int32_t i = 0; i < n_rows; i++) out[(size_t)i] = (uint32_t)r.group_dict_ids[(size_t)j][(size_t)i];
     return out;
   }
-  if (col.has_dictionary) fail(PG_ERR_INTERNAL, "PERCENTILE: values for the dictionary group-by column %s", col.name.c_str());
+  if (col.has_dictionary) fail(PG_ERR_INTERNAL, "%s: values for the dictionary group-by column %s", who, col.name.c_str());
   const size_t card = (size_t)ids.cardinality;
   if (kt == PG_GROUP_KEY_BYTES_VALUES) {
     std::unordered_map<std::string, uint32_t> by_value;
@@ -166,7 +169,7 @@ std::vector<uint32_t> group_ids_of(const Result& r, int j, const Column& col, co
     const auto& off = r.group_bytes_off[(size_t)j];
     for (int32_t i = 0; i < n_rows; i++) {
       auto it = by_value.find(std::string(reinterpret_cast<const char*>(r.group_bytes[(size_t)j].data()) + off[(size_t)i], (size_t)(off[(size_t)i + 1] - off[(size_t)i])));
-      if (it == by_value.end()) fail(PG_ERR_INTERNAL, "PERCENTILE: a group key of %s is not in its virtual dictionary", col.name.c_str());
+      if (it == by_value.end()) fail(PG_ERR_INTERNAL, "%s: a group key of %s is not in its virtual dictionary", who, col.name.c_str());
       out[(size_t)i] = it->second;
     }
     return out;
@@ -176,11 +179,13 @@ std::vector<uint32_t> group_ids_of(const Result& r, int j, const Column& col, co
   for (size_t v = 0; v < card; v++) by_value.emplace(vdict_value_of_key(ids.vdict_keys[v], ids.vdict_kind, nullptr), (uint32_t)v);
   for (int32_t i = 0; i < n_rows; i++) {
     auto it = by_value.find(r.group_values[(size_t)j][(size_t)i]);
-    if (it == by_value.end()) fail(PG_ERR_INTERNAL, "PERCENTILE: a group key of %s is not in its virtual dictionary", col.name.c_str());
+    if (it == by_value.end()) fail(PG_ERR_INTERNAL, "%s: a group key of %s is not in its virtual dictionary", who, col.name.c_str());
     out[(size_t)i] = it->second;
   }
   return out;
 }
+
+namespace {
 
 // the ordinary part of a percentile query: the query without its PERCENTILEs (COUNT(*) if nothing else remains), never on a star-tree, its
 // ORDER BY re-indexed — or dropped when it names a PERCENTILE: the segment is then not trimmed

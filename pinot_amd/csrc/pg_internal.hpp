@@ -161,6 +161,13 @@ struct Segment {
   // doc-id bitmaps handed over as portable RoaringBitmaps, kept as one-posting inverted indexes (the kernels' posting leaf):
   std::map<std::string, std::shared_ptr<Column>> null_vectors;   // NullValueVectorReader#getNullBitmap per column
   std::shared_ptr<Column> queryable_doc_ids;                     // SegmentContext#getQueryableDocIdsSnapshot
+  // per expression text of an aggregation (pg_exec_expr.hip): the bounds pass's answer over ALL docs, filled under `mu`
+  // (the pass itself runs outside it); at most 256 entries, emptied when full
+  struct ExprBounds {
+    int32_t exp = 0;             // every finite |value| < 2^exp
+    bool has_nonfinite = false;  // a NaN / Inf occurs (division by zero, overflow): such a query stays with the Java plan
+  };
+  std::map<std::string, ExprBounds> expr_bounds;
   Column* find(const char* name);
   Segment();
   ~Segment();
@@ -449,6 +456,7 @@ struct Result {
   bool distinct = false;        // PG_QUERY_FLAG_DISTINCT: the groups are the distinct tuples, no aggregation (never merged in the library)
   bool selection = false;       // PG_QUERY_FLAG_SELECTION: the groups are the selected rows (never merged in the library)
   bool percentile = false;      // the query carried a PERCENTILE: its lists merge by value on the Java side (never merged in the library)
+  bool expression = false;      // the query carried an aggregation over an expression: the scale of its sums differs per segment (never merged in the library)
   pg_exec_stats stats{};
 };
 struct DocIdSet {
@@ -487,6 +495,18 @@ void pctl_sort_build(const PgPctlArgs& A, int64_t n_matches, int key_bits, hipSt
 bool has_percentile(const pg_query& q);
 void percentile_check(Segment& seg, const pg_query& q);
 std::unique_ptr<Result> execute_percentile(Segment& seg, const pg_query& q, const CancelToken* cancel);
+// shared by the side passes that join the ordinary plan by group key (pg_exec_percentile.hip; `who` names the path in messages)
+bool column_has_nulls(Segment& seg, const std::string& name);   // seg.mu held
+Column* id_column(Segment& seg, Column& c, const char* what, const char* who = "PERCENTILE");   // seg.mu held
+std::vector<uint32_t> group_ids_of(const Result& r, int j, const Column& col, const Column& ids, int32_t n_rows, const char* who = "PERCENTILE");
+void wait_stream(hipStream_t stream, const CancelToken* cancel);
+// queries with an aggregation over an arithmetic expression (pg_exec_expr.hip): SUM / MIN / MAX / AVG / MINMAXRANGE whose pg_agg_spec.column
+// is an expression text (pg_expr.h).  The ordinary part through execute_query, a bounds pass per (segment, expression), one accumulation
+// pass for all expressions of the query joined to the ordinary part's groups by key.  expression_check: the checks of the path
+// (pg_query_supported); the bounds are answered from the segment's cache when it is filled, else the shape is let through.
+bool has_expression(const pg_query& q);
+void expression_check(Segment& seg, const pg_query& q);
+std::unique_ptr<Result> execute_expression(Segment& seg, const pg_query& q, const CancelToken* cancel);
 std::unique_ptr<Result> execute_query_plain(Segment& seg, const pg_query& q, const CancelToken* cancel);   // ... the executor proper (pg_exec.hip)
 void fill_result_schema(Segment& seg, const pg_query& q, Result& r);
 int64_t hll_cardinality(const uint8_t* regs, int log2m);   // HyperLogLog#cardinality of one register row (pg_exec.hip)
@@ -555,6 +575,10 @@ struct Knobs {
   int64_t pctl_lds_max_keys = 32768;          // PG_PCTL_LDS_MAX_KEYS
   int64_t pctl_hbm_max_bytes = (int64_t)256 << 20;   // PG_PCTL_HBM_MAX_BYTES
   int64_t pctl_sort_max_bytes = (int64_t)8 << 30;    // PG_PCTL_SORT_MAX_BYTES: work area of the sort tier (larger ones are refused by pg_query_exec, which alone knows the matches)
+  // expressions inside aggregations (pg_exec_expr.hip): tables of up to expr_lds_max_slots 64-bit slots (groups x slots per group) live in the
+  // workgroups' LDS (default and ceiling PG_EXPR_LDS_SLOTS = 16 384: 128 KiB), up to expr_hbm_max_bytes in HBM; beyond that the query is refused.
+  int64_t expr_lds_max_slots = 16384;                // PG_EXPR_LDS_MAX_SLOTS
+  int64_t expr_hbm_max_bytes = (int64_t)256 << 20;   // PG_EXPR_HBM_MAX_BYTES
   int64_t limit_prefix_min_docs = (int64_t)1 << 20;   // PG_LIMIT_PREFIX_MIN_DOCS: smallest doc prefix of the numGroupsLimit admission pass (tests lower it)
   std::string oct_passes;      // PG_OCT_PASSES: cumulative fractions, e.g. "0.02,0.08,0.3,1"
   // pg_comm.cpp

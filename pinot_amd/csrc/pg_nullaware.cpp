@@ -491,6 +491,9 @@ std::unique_ptr<Result> execute_query(Segment& seg, const pg_query& q_in, const 
   q.flags &= ~kQueryFlagNullPartition;   // internal
   if (q.flags & PG_QUERY_FLAG_SELECTION) return execute_selection(seg, q, cancel);   // its columns' nulls are refused (selection_shape)
   if (q.flags & PG_QUERY_FLAG_DISTINCT) return execute_distinct(seg, q, cancel);   // its columns' nulls are refused (distinct_shape)
+  // aggregations over expressions: before the PERCENTILE check, so that the expression pass is the outer one of a query that carries both —
+  // its statistics count the operand columns, and its ordinary part (PERCENTILEs included) comes back through here
+  if (has_expression(q)) return execute_expression(seg, q, cancel);
   if (has_percentile(q)) return execute_percentile(seg, q, cancel);   // its ordinary part comes back through here; nulls in its columns are refused (percentile_check)
   if (!(q.flags & PG_QUERY_FLAG_NULL_HANDLING)) return execute_query_plain(seg, q, cancel);
   if (q.n_aggregations <= 0 || !q.aggregations) fail(PG_ERR_INVALID_ARGUMENT, "query has no aggregation");

@@ -13,6 +13,7 @@ RANGE.  The broker-side QueryOptimizer (range merging etc.) is *not* applied, ex
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import re
 from dataclasses import dataclass, field
 from typing import List, Optional, Sequence, Tuple
@@ -81,7 +82,7 @@ def range_(col, lower=UNBOUNDED, upper=UNBOUNDED, lower_inclusive=True, upper_in
 @dataclass
 class AggregationSpec:
     function: str                  # COUNT / SUM / MIN / MAX / AVG / DISTINCTCOUNT / DISTINCTCOUNTHLL / MINMAXRANGE
-    column: Optional[str] = None   # None for COUNT(*)
+    column: Optional[str] = None   # None for COUNT(*); an arithmetic expression as its canonical text, e.g. "plus(a,times(b,'2'))"
     log2m: int = 0
     percentile: Optional[float] = None   # PERCENTILE: p in [0, 100]
 
@@ -129,6 +130,10 @@ class QueryContext:
         norm = lambda t: re.sub(r"\s+", "", t).upper()   # noqa: E731
         aggs = [norm(f"{a.function}({a.column or '*'}{',' + str(a.log2m) if a.log2m else ''})") for a in self.aggregations]
         pctl = [(a.column, a.percentile) if a.function == "PERCENTILE" else None for a in self.aggregations]
+        expr_aggs = {}   # (function, canonical text) of the aggregations over expressions -> the first one's index
+        for i, a in enumerate(self.aggregations):
+            if "(" in (a.column or ""):
+                expr_aggs.setdefault((a.function, a.column), i)
         for text, asc in self.order_by:
             if text in self.group_by:
                 out.append((capi.ORDER_BY_GROUP_KEY, self.group_by.index(text), asc))
@@ -136,6 +141,9 @@ class QueryContext:
                 out.append((capi.ORDER_BY_AGGREGATION, aggs.index(norm(text)), asc))
             elif _percentile_of_text(text) is not None and _percentile_of_text(text) in pctl:   # any of PERCENTILE's spellings names the same aggregation
                 out.append((capi.ORDER_BY_AGGREGATION, pctl.index(_percentile_of_text(text)), asc))
+            elif expr_aggs and _expression_aggregation_of_text(text) in expr_aggs:
+                # an aggregation over an expression, whatever its spelling (infix or function form): by its canonical text
+                out.append((capi.ORDER_BY_AGGREGATION, expr_aggs[_expression_aggregation_of_text(text)], asc))
             else:
                 return None
         return out
@@ -167,11 +175,26 @@ def _percentile_of_text(text: str):
         return None
 
 
+@functools.lru_cache(maxsize=256)
+def _expression_aggregation_of_text(text: str):
+    """(function, canonical expression text) of an ORDER BY expression that spells an aggregation over an arithmetic expression, else None
+    (parsed once per text)."""
+    try:
+        p = _Parser(text)
+        q = QueryContext()
+        p.select_item(q)
+    except SqlError:
+        return None
+    if p.peek()[0] != "eof" or len(q.aggregations) != 1 or "(" not in (q.aggregations[0].column or ""):
+        return None
+    return (q.aggregations[0].function, q.aggregations[0].column)
+
+
 # ----------------------------------------------------------------------------------------------------------------------
 # SQL subset parser
 # ----------------------------------------------------------------------------------------------------------------------
 _TOKEN = re.compile(r"\s*(?:(?P<num>-?\d+(?:\.\d+)?(?:[eE][-+]?\d+)?)|(?P<str>'(?:[^']|'')*')|(?P<id>[A-Za-z_][A-Za-z_0-9.$]*)"
-                    r"|(?P<op><=|>=|<>|!=|=|<|>|\(|\)|,|\*))")
+                    r"|(?P<op><=|>=|<>|!=|=|<|>|\(|\)|,|\*|\+|-|/))")
 
 
 class SqlError(ValueError):
@@ -325,6 +348,68 @@ class _Parser:
             return FilterContext.pred(Predicate("RANGE", col, [], UNBOUNDED, v, False, True))
         raise SqlError(f"unsupported operator {o}")
 
+    # --- arithmetic expressions inside aggregations -----------------------------------------------------------------
+    # The canonical text is what ExpressionContext#toString prints: fn(arg,arg,...) with the function name in lower case, literals quoted.
+    # Infix + - * / become plus / minus / times / divide, as the reference's compiler names them (CalciteSqlParser: SqlKind -> function name);
+    # the function forms ADD / SUB / MULT / DIV keep their names.  A lone column stays a plain column name.
+    _INFIX = {"+": "plus", "-": "minus", "*": "times", "/": "divide"}
+
+    def expression(self) -> str:
+        """the canonical text of an additive expression (a lone column: its name)"""
+        left = self.term()
+        while True:
+            t = self.peek()
+            if t in (("op", "+"), ("op", "-")):
+                self.i += 1
+                name = self._INFIX[t[1]]
+            elif t[0] == "num" and t[1].startswith("-"):   # after an operand, a number with a leading '-' is a subtraction
+                self.toks[self.i] = ("num", t[1][1:])
+                name = "minus"
+            else:
+                return left
+            right = self.term()
+            left = f"{name}({left},{right})"
+
+    def term(self) -> str:
+        left = self.factor()
+        while self.peek() in (("op", "*"), ("op", "/")):
+            name = self._INFIX[self.take()[1]]
+            right = self.factor()
+            left = f"{name}({left},{right})"
+        return left
+
+    def factor(self) -> str:
+        t = self.take()
+        if t == ("op", "("):
+            e = self.expression()
+            self.expect_op(")")
+            return e
+        if t[0] == "num":
+            return f"'{t[1]}'"
+        if t[0] == "str":
+            try:
+                float(t[1])
+            except ValueError:
+                raise SqlError(f"the literal {t[1]!r} in an arithmetic expression is not a number")
+            return f"'{t[1]}'"
+        if t[0] != "id":
+            raise SqlError(f"bad aggregation argument {t}")
+        if self.peek() == ("op", "("):   # a function call: its name in lower case, without underscores (FunctionContext's canonical name)
+            self.i += 1
+            args = [self.expression()]
+            while self.peek() == ("op", ","):
+                self.i += 1
+                args.append(self.expression())
+            self.expect_op(")")
+            return f"{t[1].lower().replace('_', '')}({','.join(args)})"
+        return t[1]
+
+    def aggregation_argument(self) -> str:
+        e = self.expression()
+        if e.startswith("'"):
+            raise SqlError(f"bad aggregation argument {e}: a literal")
+        return e
+
     # --- select -------------------------------------------------------------------------------------------------
     def select_item(self, q: QueryContext):
         t = self.take()
@@ -336,14 +421,11 @@ class _Parser:
         if self.peek() == ("op", "("):
             fn = t[1].upper()
             self.i += 1
-            if self.peek() == ("op", "*"):
+            if self.peek() == ("op", "*") and self.peek(1) == ("op", ")"):
                 self.i += 1
                 col = None
             else:
-                c = self.take()
-                if c[0] != "id":
-                    raise SqlError(f"bad aggregation argument {c}")
-                col = c[1]
+                col = self.aggregation_argument()   # a column, or the canonical text of an arithmetic expression
             log2m = 0
             legacy = _PERCENTILE_LEGACY.match(fn)
             if fn == "PERCENTILE" or legacy:   # PERCENTILE(col, 95) / (col, 99.9) / (col, '50') and the legacy PERCENTILE95(col)
