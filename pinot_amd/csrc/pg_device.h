@@ -475,6 +475,31 @@ __device__ __forceinline__ uint32_t pg_fixed_bit_id(const uint8_t* data, int32_t
 }
 __device__ __forceinline__ uint32_t pg_fixed_bit_id_at(const PgDistinctCol& c, uint32_t doc) { return pg_fixed_bit_id(c.data, c.bits, doc); }
 #endif
+// What the side passes' kernels (PERCENTILE, expressions) scan: the filter's match words and the group columns whose ids form the group key.
+// The first member of their arguments; the host fills it in one place (side_scan_fill, pg_exec_sidepass.hip).
+struct PgGroupScan {
+  const uint64_t* match;       // the filter's match words (bit b of word w is doc 64 w + b); NULL: every doc below n_docs matches
+  int64_t n_words;             // ceil(n_docs / 64)
+  int64_t n_docs;
+  int32_t n_gcols;
+  int32_t pad;
+  PgDistinctCol gcols[PG_MAX_GROUP_COLS];   // group columns (mult: weight of the digit in the group key)
+};
+#if defined(__HIPCC__)
+// the match word `w` with the bits of docs that do not exist cleared (w < n_words)
+__device__ __forceinline__ uint64_t pg_scan_match_word(const PgGroupScan& s, int64_t w) {
+  uint64_t v = s.match ? s.match[w] : ~0ULL;
+  const int64_t rem = s.n_docs - w * 64;
+  if (rem < 64) v &= ~0ULL >> (64 - rem);
+  return v;
+}
+// the mixed-radix group key of `doc` (0 without group columns)
+__device__ __forceinline__ uint64_t pg_scan_group_key(const PgGroupScan& s, uint32_t doc) {
+  uint64_t g = 0;
+  for (int j = 0; j < s.n_gcols; j++) g += (uint64_t)pg_fixed_bit_id_at(s.gcols[j], doc) * s.gcols[j].mult;
+  return g;
+}
+#endif
 struct PgDistinctArgs {
   const uint64_t* match;       // the filter's match words: bit b of word w is doc 64 w + b
   int64_t w_begin, w_end;      // the match words this pass reads
@@ -495,12 +520,7 @@ struct PgDistinctArgs {
 #define PG_PCTL_LDS_KEYS 32768   // 128 KiB of the CU's 160 KiB: one persistent workgroup per CU
 #define PG_PCTL_MAX_P 16         // percentiles of one column selected per launch
 struct PgPctlArgs {
-  const uint64_t* match;       // the filter's match words (bit b of word w is doc 64 w + b); NULL: every doc below n_docs matches
-  int64_t n_words;             // ceil(n_docs / 64)
-  int64_t n_docs;
-  int32_t n_gcols;
-  int32_t pad;
-  PgDistinctCol gcols[PG_MAX_GROUP_COLS];   // group columns (mult: weight of the digit in groupKey)
+  PgGroupScan scan;            // match words and group columns (groupKey)
   PgDistinctCol vcol;          // the value column's ids
   uint32_t card;               // C
   uint32_t n_keys;             // G x C (< 2^32)
@@ -589,19 +609,14 @@ struct PgExprDesc {
   int32_t pad;
 };
 struct PgExprArgs {
-  const uint64_t* match;       // the filter's match words (bit b of word w is doc 64 w + b); NULL: every doc below n_docs matches
-  int64_t n_words;             // ceil(n_docs / 64)
-  int64_t n_docs;
-  int32_t n_gcols;
+  PgGroupScan scan;            // match words and group columns
   int32_t n_srcs;
   int32_t n_exprs;
   int32_t slots;               // slots per group
   int32_t count_slot;          // the doc count's slot, -1 without an AVG
-  int32_t pad;
-  uint64_t n_groups;           // G (<= 2^32)
+  uint64_t n_groups;          // G (<= 2^32)
   uint64_t n_slots;            // G x slots
   int64_t* table;              // [G][slots] in HBM, every slot at its identity (pg_expr_init)
-  PgDistinctCol gcols[PG_MAX_GROUP_COLS];
   PgValueSrc srcs[PG_EXPR_MAX_SRCS];
   PgExprDesc exprs[PG_EXPR_MAX_EXPRS];
   int64_t ident[PG_EXPR_MAX_SLOTS];   // per slot of a row: 0 (SUM limbs, count), INT64_MAX (MIN), INT64_MIN (MAX)

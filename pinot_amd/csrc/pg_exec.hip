@@ -365,6 +365,7 @@ int default_device() {
   const int d = g_default_device.load();
   return d < 0 ? 0 : d;
 }
+int device_cus(int ordinal) { return g_devices[ordinal].num_cus; }
 static int num_cus() { return g_devices[t_device].num_cus; }
 static size_t lds_per_cu() { return g_devices[t_device].lds_per_cu; }
 
@@ -552,7 +553,7 @@ static ThreadCtx& ctx_on(int device) {
 }
 hipStream_t thread_stream(int device) { return ctx_on(device).stream; }
 
-static double now_ms() {
+double now_ms() {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 

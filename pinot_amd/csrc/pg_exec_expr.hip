@@ -1,21 +1,19 @@
 // Queries with an aggregation over an arithmetic expression — SUM / MIN / MAX / AVG / MINMAXRANGE whose pg_agg_spec.column is an expression
 // text (pg_expr.h: add / sub / mult / div over single-value numeric columns and literals): a side pass joined to the ordinary plan by group
-// key, after the PERCENTILE split (pg_exec_percentile.hip).
+// key, in the frame of pg_exec_sidepass.hip (which runs step 1 and the filter, maps the admitted groups to rows and joins the result, step 4).
 //   1. The ordinary part — the query without its expression aggregations (COUNT(*) if nothing else remains) — runs through execute_query
 //      unchanged, never on a star-tree: it decides the groups, the numGroupsLimit admission and the other aggregations' results (a PERCENTILE
 //      among them takes its own side pass from there).  An ORDER BY that names an expression aggregation leaves the segment untrimmed.
 //   2. A bounds pass per (segment, expression text) over ALL docs (pg_expr_bounds): the largest finite |value| fixes the scale of the exact
 //      fixed-point SUM (pg_fixed_point.h, L = 4 limbs, q = E - 127 with every |value| < 2^E); an expression that yields a NaN / Inf anywhere in
 //      the segment is refused by pg_query_exec.  Cached in the segment (at most 256 texts, filled under its lock; the pass itself runs outside it).
-//   3. One accumulation pass for ALL expressions of the query over the filter's match words — the filter kernels and cached filter plan of the
-//      DISTINCT and PERCENTILE paths — into a table [G][slots] of int64: pg_expr_reg without GROUP BY, pg_expr_lds up to
+//   3. One accumulation pass for ALL expressions of the query over the filter's match words into a table [G][slots] of int64: pg_expr_reg without GROUP BY, pg_expr_lds up to
 //      Knobs::expr_lds_max_slots slots, pg_expr_hbm up to Knobs::expr_hbm_max_bytes; beyond that the query is refused.
 //   4. The rows of the admitted groups are gathered on the device and joined to the ordinary part on the host.
 // The kernels are those of pg_kernels_expr.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <limits>
 #include <set>
@@ -33,9 +31,8 @@ void pg_expr_launch_gather(const int64_t* table, const uint32_t* rows, int32_t n
 namespace pg {
 namespace {
 
-double wall_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
 const char* kWho = "expression";
+const char* kSubject = "an aggregation over an expression";
 constexpr size_t kMaxCachedBounds = 256;   // Segment::expr_bounds entries per segment (some tens of bytes each)
 enum Tier { TIER_REG = 0, TIER_LDS = 1, TIER_HBM = 2 };
 const char* const kTierKernel[3] = {"pg_expr_reg", "pg_expr_lds", "pg_expr_hbm"};
@@ -71,9 +68,7 @@ struct ExprItem {
   Segment::ExprBounds bounds;
 };
 struct ExprPlan {
-  std::vector<Column*> group_cols, group_ids;
-  std::vector<uint64_t> mult;   // weight of the group column's digit (column 0 least significant)
-  uint64_t G = 1;
+  SideGroups groups;
   std::vector<ExprItem> exprs;
   std::vector<Column*> srcs;    // the distinct operand columns of all expressions
   int32_t slots = 0, count_slot = -1;
@@ -91,12 +86,6 @@ void fill_src(PgValueSrc& S, const Column& c) {
   S.fx_q = 0;
 }
 
-int device_cus(int device) {
-  int cus = 0;
-  PG_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-  return std::max(cus, 1);
-}
-
 // the bounds pass of one expression over every doc of the segment (seg.mu NOT held: it only reads registered columns, which never change or
 // go away while the segment lives; the device is current)
 Segment::ExprBounds run_bounds(Segment& seg, const ExprItem& item, const std::vector<Column*>& cols) {
@@ -104,8 +93,8 @@ Segment::ExprBounds run_bounds(Segment& seg, const ExprItem& item, const std::ve
   if (seg.total_docs <= 0) return b;
   PgExprArgs A;
   memset(&A, 0, sizeof(A));
-  A.n_docs = seg.total_docs;
-  A.n_words = ((int64_t)seg.total_docs + 63) / 64;
+  A.scan.n_docs = seg.total_docs;
+  A.scan.n_words = ((int64_t)seg.total_docs + 63) / 64;
   A.n_srcs = (int32_t)cols.size();
   A.n_exprs = 1;
   A.count_slot = -1;
@@ -138,9 +127,7 @@ Segment::ExprBounds run_bounds(Segment& seg, const ExprItem& item, const std::ve
 }
 
 ExprPlan expr_plan(Segment& seg, const pg_query& q, bool compute_bounds) {
-  if (q.n_aggregations <= 0 || !q.aggregations) fail(PG_ERR_INVALID_ARGUMENT, "query has no aggregation");
-  if (q.n_group_by < 0 || (q.n_group_by > 0 && !q.group_by_columns)) fail(PG_ERR_INVALID_ARGUMENT, "group_by_columns is null");
-  if (q.n_group_by > PG_MAX_GROUP_COLS) fail(PG_ERR_UNSUPPORTED, "an aggregation over an expression with more than %d group-by columns", PG_MAX_GROUP_COLS);
+  side_query_check(q, kSubject);
   const bool null_handling = (q.flags & PG_QUERY_FLAG_NULL_HANDLING) != 0;
   ExprPlan P;
   std::set<std::string> read;
@@ -213,20 +200,7 @@ ExprPlan expr_plan(Segment& seg, const pg_query& q, bool compute_bounds) {
     P.exprs[k].acc |= acc;
     P.exprs[k].aggs.push_back(a);
   }
-  for (int j = 0; j < q.n_group_by; j++) {
-    const char* name = q.group_by_columns[j];
-    Column* c = name ? seg.find(name) : nullptr;
-    if (!c) fail(PG_ERR_NOT_FOUND, "column not found: %s", name ? name : "(null)");
-    if (c->is_mv || c->raw_mv) fail(PG_ERR_UNSUPPORTED, "an aggregation over an expression next to the multi-value group-by column %s", c->name.c_str());
-    if (null_handling && column_has_nulls(seg, c->name)) fail(PG_ERR_UNSUPPORTED, "enableNullHandling: an aggregation over an expression grouped by %s, which holds nulls", c->name.c_str());
-    read.insert(name);
-    Column* id = id_column(seg, *c, "group-by", kWho);
-    P.group_cols.push_back(c);
-    P.group_ids.push_back(id);
-    P.mult.push_back(P.G);
-    P.G *= (uint64_t)id->cardinality;
-    if (P.G > ((uint64_t)1 << 32)) fail(PG_ERR_UNSUPPORTED, "an aggregation over an expression: group key space over 2^32 (the product of the group-by columns' cardinalities)");
-  }
+  P.groups = side_groups(seg, q, kSubject, kWho, read);
   P.n_columns_read = (int)read.size();
   // the group's row: per expression the SUM's limbs, the MIN, the MAX, as far as an aggregation asks for them; one doc count for AVG
   for (ExprItem& item : P.exprs) {
@@ -235,62 +209,19 @@ ExprPlan expr_plan(Segment& seg, const pg_query& q, bool compute_bounds) {
     if (item.acc & PG_EXPR_ACC_MAX) item.max_slot = P.slots++;
   }
   if (need_count) P.count_slot = P.slots++;
-  P.n_slots = P.G * (uint64_t)P.slots;   // < 2^37
+  P.n_slots = P.groups.G * (uint64_t)P.slots;   // < 2^37
   const Knobs& K = knobs();
   if (q.n_group_by == 0) P.tier = TIER_REG;
   else if (P.n_slots <= (uint64_t)std::min<int64_t>(K.expr_lds_max_slots, PG_EXPR_LDS_SLOTS)) P.tier = TIER_LDS;
   else if (P.n_slots * 8 <= (uint64_t)K.expr_hbm_max_bytes) P.tier = TIER_HBM;
   else
     fail(PG_ERR_UNSUPPORTED, "aggregations over expressions: %llu groups x %d slots need a table of %llu bytes, more than PG_EXPR_HBM_MAX_BYTES (%lld)",
-         (unsigned long long)P.G, P.slots, (unsigned long long)(P.n_slots * 8), (long long)K.expr_hbm_max_bytes);
+         (unsigned long long)P.groups.G, P.slots, (unsigned long long)(P.n_slots * 8), (long long)K.expr_hbm_max_bytes);
   return P;
 }
 
-// the ordinary part: the query without its expression aggregations (COUNT(*) if nothing else remains), never on a star-tree, its ORDER BY
-// re-indexed — or dropped when it names an expression aggregation: the segment is then not trimmed
-struct BaseQuery {
-  std::vector<pg_agg_spec> aggs;
-  std::vector<double> params;
-  std::vector<pg_order_by> order;
-  std::vector<int> base_index;   // per aggregation of the query: its index in the ordinary part, -1 for one over an expression
-  pg_query q;
-};
-void base_query(const pg_query& q, BaseQuery& out) {
-  out.base_index.assign((size_t)q.n_aggregations, -1);
-  for (int a = 0; a < q.n_aggregations; a++) {
-    if (is_expression_agg(q.aggregations[a])) continue;
-    out.base_index[(size_t)a] = (int)out.aggs.size();
-    out.aggs.push_back(q.aggregations[a]);
-    out.params.push_back(q.agg_params ? q.agg_params[a] : 0.0);
-  }
-  if (out.aggs.empty()) {
-    pg_agg_spec count_star;
-    memset(&count_star, 0, sizeof(count_star));
-    count_star.function = PG_AGG_COUNT;
-    out.aggs.push_back(count_star);
-    out.params.push_back(0.0);
-  }
-  pg_query& b = out.q;
-  b = q;
-  b.aggregations = out.aggs.data();
-  b.n_aggregations = (int32_t)out.aggs.size();
-  b.agg_params = q.agg_params ? out.params.data() : nullptr;
-  b.flags = (q.flags | PG_QUERY_FLAG_SKIP_STAR_TREE) & ~PG_QUERY_FLAG_KEEP_DEVICE_TABLE;
-  if (q.n_order_by > 0 && q.order_by) {
-    bool by_expression = false;
-    for (int32_t i = 0; i < q.n_order_by; i++) {
-      pg_order_by ob = q.order_by[i];
-      if (ob.kind == PG_ORDER_BY_AGGREGATION) {
-        if (ob.index < 0 || ob.index >= q.n_aggregations) fail(PG_ERR_INVALID_ARGUMENT, "ORDER BY aggregation %d of %d", ob.index, q.n_aggregations);
-        if (out.base_index[(size_t)ob.index] < 0) by_expression = true;
-        else ob.index = out.base_index[(size_t)ob.index];
-      }
-      out.order.push_back(ob);
-    }
-    if (by_expression) { b.n_order_by = 0; b.order_by = nullptr; }
-    else b.order_by = out.order.data();
-  }
-}
+// the ordinary part may hold a PERCENTILE, which reads PG_QUERY_FLAG_FINAL_PERCENTILE; it does not keep its table (the result is not merged in the library)
+constexpr int32_t kBaseClears = PG_QUERY_FLAG_KEEP_DEVICE_TABLE;
 
 double order_key_to_double(int64_t k) {
   const int64_t b = k ^ ((k >> 63) & 0x7FFFFFFFFFFFFFFFLL);
@@ -310,70 +241,35 @@ bool has_expression(const pg_query& q) {
 
 void expression_check(Segment& seg, const pg_query& q) {
   (void)expr_plan(seg, q, false);
-  BaseQuery B;   // ... and what the ordinary part refuses
-  base_query(q, B);
+  SideBaseQuery B;   // ... and what the ordinary part refuses
+  side_base_query(q, is_expression_agg, kBaseClears, B);
   if (has_percentile(B.q)) { percentile_check(seg, B.q); return; }
   check_null_handling(seg, B.q);
   (void)get_plan(seg, B.q.filter, &B.q);
 }
 
 std::unique_ptr<Result> execute_expression(Segment& seg, const pg_query& q, const CancelToken* cancel) {
-  const double t0 = wall_ms();
+  const double t0 = now_ms();
   use_device(seg.device);
   const ExprPlan P = expr_plan(seg, q, true);
-  const double t_plan = wall_ms();
-  // ---- the ordinary part ------------------------------------------------------------------------------------------------------------------
-  BaseQuery B;
-  base_query(q, B);
-  std::unique_ptr<Result> res = execute_query(seg, B.q, cancel);
-  use_device(seg.device);
-  hipStream_t stream = thread_stream(seg.device);
-  const int32_t n_rows = q.n_group_by > 0 ? res->num_groups : 1;
-  // ---- the filter's match words (none without a filter and without an upsert snapshot) ---------------------------------------------------
-  bool snapshot = false;
-  {
-    std::lock_guard<std::mutex> lock(seg.mu);
-    snapshot = seg.queryable_doc_ids != nullptr;
-  }
-  std::unique_ptr<DocIdSet> ds;
-  int64_t M = seg.total_docs;
-  if (q.filter || snapshot) {
-    ds = execute_filter(seg, q.filter, q.flags & PG_QUERY_FLAG_NULL_HANDLING);
-    M = ds->cardinality;
-  }
-  if (cancel && cancel->requested.load(std::memory_order_acquire)) fail(PG_ERR_CANCELLED, "query cancelled (EarlyTerminationException)");
-  // ---- the admitted groups' keys -------------------------------------------------------------------------------------------------------------
-  std::vector<uint32_t> rows((size_t)n_rows, 0);
-  for (int j = 0; j < q.n_group_by; j++) {
-    const std::vector<uint32_t> ids = group_ids_of(*res, j, *P.group_cols[(size_t)j], *P.group_ids[(size_t)j], n_rows, kWho);
-    for (int32_t i = 0; i < n_rows; i++) {
-      if (ids[(size_t)i] >= (uint32_t)P.group_ids[(size_t)j]->cardinality) fail(PG_ERR_INTERNAL, "expression: group key id %u of %s out of range", ids[(size_t)i], P.group_cols[(size_t)j]->name.c_str());
-      rows[(size_t)i] += (uint32_t)(ids[(size_t)i] * P.mult[(size_t)j]);
-    }
-  }
-  const int cus = device_cus(seg.device);
-  const int64_t n_words = ((int64_t)seg.total_docs + 63) / 64;
+  const double t_plan = now_ms();
+  SideBaseQuery B;
+  side_base_query(q, is_expression_agg, kBaseClears, B);
+  SidePass S = side_pass_begin(seg, q, B, P.groups, kWho, cancel);
+  const int32_t n_rows = S.n_rows;
+  const int64_t M = S.M, n_words = S.n_words;
+  const int cus = S.cus;
+  hipStream_t stream = S.stream;
   // ---- the accumulation pass -------------------------------------------------------------------------------------------------------------------
   PgExprArgs A;
   memset(&A, 0, sizeof(A));
-  A.match = ds ? ds->words.as<uint64_t>() : nullptr;
-  A.n_words = n_words;
-  A.n_docs = seg.total_docs;
-  A.n_gcols = q.n_group_by;
+  int64_t doc_bits = side_scan_fill(A.scan, seg, S, P.groups);
   A.n_srcs = (int32_t)P.srcs.size();
   A.n_exprs = (int32_t)P.exprs.size();
   A.slots = P.slots;
   A.count_slot = P.count_slot;
-  A.n_groups = P.G;
+  A.n_groups = P.groups.G;
   A.n_slots = P.n_slots;
-  int64_t doc_bits = 0;
-  for (int j = 0; j < q.n_group_by; j++) {
-    A.gcols[j].data = P.group_ids[(size_t)j]->fwd_dev.as<uint8_t>();
-    A.gcols[j].bits = P.group_ids[(size_t)j]->bits;
-    A.gcols[j].card = P.group_ids[(size_t)j]->cardinality;
-    A.gcols[j].mult = P.mult[(size_t)j];
-    doc_bits += P.group_ids[(size_t)j]->bits;
-  }
   for (size_t i = 0; i < P.srcs.size(); i++) {
     fill_src(A.srcs[i], *P.srcs[i]);
     doc_bits += P.srcs[i]->col_kind == PG_COL_FIXED_BIT ? P.srcs[i]->bits : (P.srcs[i]->col_kind == PG_COL_RAW32 ? 32 : 64);
@@ -401,16 +297,8 @@ std::unique_ptr<Result> execute_expression(Segment& seg, const pg_query& q, cons
   DeviceBuffer table((size_t)P.n_slots * 8);
   A.table = table.as<int64_t>();
   // PG_QUERY_FLAG_PROFILE: the pass (initialisation, accumulation, gather and its copy) between two events of its own
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  struct EventGuard {
-    hipEvent_t* e;
-    ~EventGuard() { for (int i = 0; i < 2; i++) if (e[i]) (void)hipEventDestroy(e[i]); }
-  } ev_guard{ev};
-  if (q.flags & PG_QUERY_FLAG_PROFILE) {
-    PG_HIP(hipEventCreate(&ev[0]));
-    PG_HIP(hipEventCreate(&ev[1]));
-    PG_HIP(hipEventRecord(ev[0], stream));
-  }
+  ProfileTimer timer(q.flags);
+  timer.start(stream);
   pg_expr_launch_init(&A, (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)cus * 8, ((int64_t)P.n_slots + 255) / 256)), stream);
   PG_HIP(hipGetLastError());
   if (M > 0 && n_words > 0) {
@@ -422,8 +310,8 @@ std::unique_ptr<Result> execute_expression(Segment& seg, const pg_query& q, cons
   std::vector<int64_t> got((size_t)n_rows * (size_t)P.slots);
   if (n_rows > 0) {
     DeviceBuffer d_rows((size_t)n_rows * 4), d_out(got.size() * 8);
-    PG_HIP(hipMemcpyAsync(d_rows.ptr, rows.data(), (size_t)n_rows * 4, hipMemcpyHostToDevice, stream));
-    pg_expr_launch_gather(table.as<int64_t>(), d_rows.as<uint32_t>(), n_rows, P.slots, P.G, d_out.as<int64_t>(),
+    PG_HIP(hipMemcpyAsync(d_rows.ptr, S.rows.data(), (size_t)n_rows * 4, hipMemcpyHostToDevice, stream));
+    pg_expr_launch_gather(table.as<int64_t>(), d_rows.as<uint32_t>(), n_rows, P.slots, P.groups.G, d_out.as<int64_t>(),
                           (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)cus * 8, ((int64_t)got.size() + 255) / 256)), stream);
     PG_HIP(hipGetLastError());
     PG_HIP(hipMemcpyAsync(got.data(), d_out.ptr, got.size() * 8, hipMemcpyDeviceToHost, stream));
@@ -431,12 +319,7 @@ std::unique_ptr<Result> execute_expression(Segment& seg, const pg_query& q, cons
   } else {
     wait_stream(stream, cancel);
   }
-  float pass_ms = 0;
-  if (ev[0]) {
-    PG_HIP(hipEventRecord(ev[1], stream));
-    PG_HIP(hipEventSynchronize(ev[1]));
-    PG_HIP(hipEventElapsedTime(&pass_ms, ev[0], ev[1]));
-  }
+  const float pass_ms = timer.stop_ms();
   // ---- the expression aggregations' results: the reference's defaults over no doc fall out of the identities -----------------------------------
   std::vector<AggResult> out((size_t)q.n_aggregations);
   for (const ExprItem& item : P.exprs) {
@@ -485,41 +368,9 @@ std::unique_ptr<Result> execute_expression(Segment& seg, const pg_query& q, cons
   }
   if (q.n_group_by == 0 && P.count_slot >= 0 && got[(size_t)P.count_slot] != M)
     fail(PG_ERR_INTERNAL, "expression: %lld docs counted for %lld matching docs", (long long)got[(size_t)P.count_slot], (long long)M);
-  // ---- the joined result ------------------------------------------------------------------------------------------------------------------------
-  std::vector<std::vector<uint8_t>> nulls;
-  if (!res->agg_nulls.empty()) nulls.assign((size_t)q.n_aggregations, {});
-  for (int a = 0; a < q.n_aggregations; a++) {
-    const int bi = B.base_index[(size_t)a];
-    if (bi < 0) continue;
-    out[(size_t)a] = std::move(res->aggs[(size_t)bi]);
-    if (!nulls.empty() && (size_t)bi < res->agg_nulls.size()) nulls[(size_t)a] = std::move(res->agg_nulls[(size_t)bi]);
-  }
-  res->aggs = std::move(out);
-  res->agg_nulls = std::move(nulls);
-  res->dev.reset();
+  const int64_t pass_bytes = ((int64_t)seg.total_docs * doc_bits + 7) / 8 + (S.ds ? n_words * 8 : 0);
+  std::unique_ptr<Result> res = side_pass_finish(seg, q, B, S, out, {kTierKernel[P.tier], pass_bytes, P.n_columns_read, pass_ms, t0, t_plan});
   res->expression = true;
-  pg_exec_stats& st = res->stats;
-  st.num_docs_scanned = M;
-  st.num_entries_scanned_post_filter = M * P.n_columns_read;
-  if (ds) {
-    st.num_entries_scanned_in_filter = ds->stats.num_entries_scanned_in_filter;
-    st.stats_exact = ds->stats.stats_exact;
-    st.filter_stats_path = ds->stats.filter_stats_path;
-    st.device_ms_filter += ds->stats.device_ms_filter;
-  } else {
-    st.num_entries_scanned_in_filter = 0;
-    st.stats_exact = 1;
-  }
-  st.device_ms_aggregate += pass_ms;
-  st.device_ms_total += pass_ms + (ds ? ds->stats.device_ms_filter : 0.0f);
-  st.num_total_docs = seg.total_docs;
-  st.star_tree_index = -1;
-  st.algorithmic_bytes += ((int64_t)seg.total_docs * doc_bits + 7) / 8 + (ds ? n_words * 8 : 0);
-  snprintf(st.kernel, sizeof(st.kernel), "%s", kTierKernel[P.tier]);
-  fill_result_schema(seg, q, *res);
-  res->null_handling = (q.flags & PG_QUERY_FLAG_NULL_HANDLING) != 0;
-  st.host_ms_plan += (float)(t_plan - t0);
-  st.host_ms_total = (float)(wall_ms() - t0);
   return res;
 }
 

@@ -1,11 +1,11 @@
-// Queries with an exact PERCENTILE aggregation (PG_AGG_PERCENTILE): a side pass joined to the ordinary plan by group key.
+// Queries with an exact PERCENTILE aggregation (PG_AGG_PERCENTILE): a side pass joined to the ordinary plan by group key, in the frame of
+// pg_exec_sidepass.hip (which runs step 1 and the filter, maps the admitted groups to rows and joins the result).
 //   1. The ordinary part — the query without its PERCENTILEs (COUNT(*) if nothing else remains) — runs through execute_query unchanged: it
 //      decides the groups, the numGroupsLimit admission and the other aggregations' results.
-//   2. One counting pass per distinct percentile COLUMN (p50 / p95 / p99 of one column share it) over the filter's match words — the filter
-//      kernels and cached filter plan of the DISTINCT path — into a dense table of 32-bit counters [G][C]: pg_pctl_lds up to
-//      Knobs::pctl_lds_max_keys counters, pg_pctl_hbm up to Knobs::pctl_hbm_max_bytes; beyond that the sort tier (pg_pctl_sort: the matching
-//      docs' 64-bit keys written compacted, a radix sort over their significant bits, a run-length encode), refused when its work area would
-//      exceed Knobs::pctl_sort_max_bytes.
+//   2. One counting pass per distinct percentile COLUMN (p50 / p95 / p99 of one column share it) over the filter's match words into a dense
+//      table of 32-bit counters [G][C]: pg_pctl_lds up to Knobs::pctl_lds_max_keys counters, pg_pctl_hbm up to Knobs::pctl_hbm_max_bytes;
+//      beyond that the sort tier (pg_pctl_sort: the matching docs' 64-bit keys written compacted, a radix sort over their significant bits, a
+//      run-length encode), refused when its work area would exceed Knobs::pctl_sort_max_bytes.
 //   3. Rank selection on the device over the rows of the admitted groups (pg_pctl_select; pg_pctl_sort_select over the sort tier's runs); the
 //      intermediate form is the rows' non-zero (value, count) runs (pg_pctl_runs / pg_pctl_sort_runs), the final form
 //      (PG_QUERY_FLAG_FINAL_PERCENTILE) one double per group and aggregation.
@@ -13,12 +13,10 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <limits>
 #include <set>
 #include <string>
-#include <unordered_map>
 
 #include "pg_internal.hpp"
 
@@ -33,43 +31,9 @@ void pg_pctl_launch_sort_runs(const uint64_t* run_keys, const uint32_t* run_coun
 
 namespace pg {
 
-bool column_has_nulls(Segment& seg, const std::string& name) {   // seg.mu held
-  auto it = seg.null_vectors.find(name);
-  return it != seg.null_vectors.end() && it->second && !it->second->posting_card.empty() && it->second->posting_card[0] > 0;
-}
-
-// the column of fixed-bit, value-ordered ids behind `c`: its own dictIds, or its virtual dictionary's (seg.mu held)
-Column* id_column(Segment& seg, Column& c, const char* what, const char* who) {
-  Column* id = &c;
-  if (!c.has_dictionary) {
-    if (c.col_kind != PG_COL_RAW32 && c.col_kind != PG_COL_RAW64 && c.col_kind != PG_COL_VAR_BYTES)
-      fail(PG_ERR_UNSUPPORTED, "%s: %s column %s (layout %d)", who, what, c.name.c_str(), c.col_kind);
-    ensure_virtual_dictionary(seg, c);
-    id = c.vdict.get();
-  }
-  if (id->cardinality < 1 || id->bits < 1 || id->bits > 31)
-    fail(PG_ERR_UNSUPPORTED, "%s: %s column %s has %d values in %d bits", who, what, c.name.c_str(), id->cardinality, id->bits);
-  return id;
-}
-
-void wait_stream(hipStream_t stream, const CancelToken* cancel) {
-  if (cancel) {
-    for (;;) {
-      const hipError_t e = hipStreamQuery(stream);
-      if (e == hipSuccess) return;
-      if (e != hipErrorNotReady) PG_HIP(e);
-      if (cancel->requested.load(std::memory_order_acquire)) {
-        (void)hipStreamSynchronize(stream);   // let what was launched finish
-        fail(PG_ERR_CANCELLED, "query cancelled (EarlyTerminationException)");
-      }
-    }
-  }
-  PG_HIP(hipStreamSynchronize(stream));
-}
-
 namespace {
 
-double wall_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+const char* kWho = "PERCENTILE";
 
 struct PctlColumn {
   Column* col = nullptr;    // the column the segment knows by name
@@ -79,17 +43,13 @@ struct PctlColumn {
   uint64_t n_keys = 0;
 };
 struct PctlPlan {
-  std::vector<Column*> group_cols, group_ids;
-  std::vector<uint64_t> mult;   // weight of the group column's digit (column 0 least significant)
-  uint64_t G = 1;
+  SideGroups groups;
   std::vector<PctlColumn> cols;
   int n_columns_read = 0;       // distinct columns the query projects (ProjectOperator#getNumColumnsProjected)
 };
 
 PctlPlan pctl_plan(Segment& seg, const pg_query& q) {
-  if (q.n_aggregations <= 0 || !q.aggregations) fail(PG_ERR_INVALID_ARGUMENT, "query has no aggregation");
-  if (q.n_group_by < 0 || (q.n_group_by > 0 && !q.group_by_columns)) fail(PG_ERR_INVALID_ARGUMENT, "group_by_columns is null");
-  if (q.n_group_by > PG_MAX_GROUP_COLS) fail(PG_ERR_UNSUPPORTED, "PERCENTILE with more than %d group-by columns", PG_MAX_GROUP_COLS);
+  side_query_check(q, kWho);
   const bool null_handling = (q.flags & PG_QUERY_FLAG_NULL_HANDLING) != 0;
   PctlPlan P;
   std::set<std::string> read;
@@ -116,26 +76,13 @@ PctlPlan pctl_plan(Segment& seg, const pg_query& q) {
     }
     P.cols[k].aggs.push_back(a);
   }
-  for (int j = 0; j < q.n_group_by; j++) {
-    const char* name = q.group_by_columns[j];
-    Column* c = name ? seg.find(name) : nullptr;
-    if (!c) fail(PG_ERR_NOT_FOUND, "column not found: %s", name ? name : "(null)");
-    if (c->is_mv || c->raw_mv) fail(PG_ERR_UNSUPPORTED, "PERCENTILE next to the multi-value group-by column %s", c->name.c_str());
-    if (null_handling && column_has_nulls(seg, c->name)) fail(PG_ERR_UNSUPPORTED, "enableNullHandling: PERCENTILE grouped by %s, which holds nulls", c->name.c_str());
-    read.insert(name);
-    Column* id = id_column(seg, *c, "group-by");
-    P.group_cols.push_back(c);
-    P.group_ids.push_back(id);
-    P.mult.push_back(P.G);
-    P.G *= (uint64_t)id->cardinality;
-    if (P.G > ((uint64_t)1 << 32)) fail(PG_ERR_UNSUPPORTED, "PERCENTILE: group key space over 2^32 (the product of the group-by columns' cardinalities)");
-  }
+  P.groups = side_groups(seg, q, kWho, kWho, read);
   P.n_columns_read = (int)read.size();
   const Knobs& K = knobs();
   for (PctlColumn& pc : P.cols) {
-    pc.ids = id_column(seg, *pc.col, "aggregated");
+    pc.ids = id_column(seg, *pc.col, "aggregated", kWho);
     const uint64_t C = (uint64_t)pc.ids->cardinality;
-    pc.n_keys = P.G * C;   // < 2^63
+    pc.n_keys = P.groups.G * C;   // < 2^63
     pc.sort = pc.n_keys >= 0xFFFFFFFFull || pc.n_keys * 4 > (uint64_t)K.pctl_hbm_max_bytes;   // no dense table: the sort tier
     pc.lds = !pc.sort && pc.n_keys <= (uint64_t)std::min<int64_t>(K.pctl_lds_max_keys, PG_PCTL_LDS_KEYS);
   }
@@ -149,90 +96,9 @@ double value_of_id(const Column& col, const Column& ids, int32_t id) {   // Dict
   return d;
 }
 
-}  // namespace
-
-// the id of every admitted group's key in group-by column j of a side pass
-std::vector<uint32_t> group_ids_of(const Result& r, int j, const Column& col, const Column& ids, int32_t n_rows, const char* who) {
-  std::vector<uint32_t> out((size_t)n_rows);
-  const int32_t kt = r.group_key_type.empty() ? PG_GROUP_KEY_DICT_IDS : r.group_key_type[(size_t)j];
-  if (kt == PG_GROUP_KEY_DICT_IDS) {
-    if (!col.has_dictionary) fail(PG_ERR_INTERNAL, "%s: dictIds for the raw group-by column %s", who, col.name.c_str());
-    for (int32_t i = 0; i < n_rows; i++) out[(size_t)i] = (uint32_t)r.group_dict_ids[(size_t)j][(size_t)i];
-    return out;
-  }
-  if (col.has_dictionary) fail(PG_ERR_INTERNAL, "%s: values for the dictionary group-by column %s", who, col.name.c_str());
-  const size_t card = (size_t)ids.cardinality;
-  if (kt == PG_GROUP_KEY_BYTES_VALUES) {
-    std::unordered_map<std::string, uint32_t> by_value;
-    for (size_t v = 0; v < card; v++)
-      by_value.emplace(std::string(reinterpret_cast<const char*>(ids.vdict_bytes.data()) + ids.vdict_bytes_off[v], (size_t)(ids.vdict_bytes_off[v + 1] - ids.vdict_bytes_off[v])), (uint32_t)v);
-    const auto& off = r.group_bytes_off[(size_t)j];
-    for (int32_t i = 0; i < n_rows; i++) {
-      auto it = by_value.find(std::string(reinterpret_cast<const char*>(r.group_bytes[(size_t)j].data()) + off[(size_t)i], (size_t)(off[(size_t)i + 1] - off[(size_t)i])));
-      if (it == by_value.end()) fail(PG_ERR_INTERNAL, "%s: a group key of %s is not in its virtual dictionary", who, col.name.c_str());
-      out[(size_t)i] = it->second;
-    }
-    return out;
-  }
-  std::unordered_map<int64_t, uint32_t> by_value;   // LONG values, or the IEEE bits of DOUBLE values: what the ordinary part hands back
-  by_value.reserve(card * 2);
-  for (size_t v = 0; v < card; v++) by_value.emplace(vdict_value_of_key(ids.vdict_keys[v], ids.vdict_kind, nullptr), (uint32_t)v);
-  for (int32_t i = 0; i < n_rows; i++) {
-    auto it = by_value.find(r.group_values[(size_t)j][(size_t)i]);
-    if (it == by_value.end()) fail(PG_ERR_INTERNAL, "%s: a group key of %s is not in its virtual dictionary", who, col.name.c_str());
-    out[(size_t)i] = it->second;
-  }
-  return out;
-}
-
-namespace {
-
-// the ordinary part of a percentile query: the query without its PERCENTILEs (COUNT(*) if nothing else remains), never on a star-tree, its
-// ORDER BY re-indexed — or dropped when it names a PERCENTILE: the segment is then not trimmed
-struct BaseQuery {
-  std::vector<pg_agg_spec> aggs;
-  std::vector<pg_order_by> order;
-  std::vector<int> base_index;   // per aggregation of the query: its index in the ordinary part, -1 for a PERCENTILE
-  pg_query q;
-};
-void base_query(const pg_query& q, BaseQuery& out) {
-  std::vector<pg_agg_spec>& aggs = out.aggs;
-  std::vector<pg_order_by>& order = out.order;
-  std::vector<int>& base_index = out.base_index;
-  pg_query& b = out.q;
-  base_index.assign((size_t)q.n_aggregations, -1);
-  for (int a = 0; a < q.n_aggregations; a++) {
-    if (q.aggregations[a].function == PG_AGG_PERCENTILE) continue;
-    base_index[(size_t)a] = (int)aggs.size();
-    aggs.push_back(q.aggregations[a]);
-  }
-  if (aggs.empty()) {
-    pg_agg_spec count_star;
-    memset(&count_star, 0, sizeof(count_star));
-    count_star.function = PG_AGG_COUNT;
-    aggs.push_back(count_star);
-  }
-  b = q;
-  b.aggregations = aggs.data();
-  b.n_aggregations = (int32_t)aggs.size();
-  b.agg_params = nullptr;
-  b.flags = (q.flags | PG_QUERY_FLAG_SKIP_STAR_TREE) & ~(PG_QUERY_FLAG_FINAL_PERCENTILE | PG_QUERY_FLAG_KEEP_DEVICE_TABLE);
-  // segment trim: an ORDER BY that names a PERCENTILE leaves the segment untrimmed; others keep their aggregation by its new index
-  if (q.n_order_by > 0 && q.order_by) {
-    bool by_percentile = false;
-    for (int32_t i = 0; i < q.n_order_by; i++) {
-      pg_order_by ob = q.order_by[i];
-      if (ob.kind == PG_ORDER_BY_AGGREGATION) {
-        if (ob.index < 0 || ob.index >= q.n_aggregations) fail(PG_ERR_INVALID_ARGUMENT, "ORDER BY aggregation %d of %d", ob.index, q.n_aggregations);
-        if (base_index[(size_t)ob.index] < 0) by_percentile = true;
-        else ob.index = base_index[(size_t)ob.index];
-      }
-      order.push_back(ob);
-    }
-    if (by_percentile) { b.n_order_by = 0; b.order_by = nullptr; }
-    else b.order_by = order.data();
-  }
-}
+bool is_percentile_agg(const pg_agg_spec& s) { return s.function == PG_AGG_PERCENTILE; }
+// the ordinary part holds no PERCENTILE: it neither keeps its table (the result is not merged in the library) nor reads the final-form flag
+constexpr int32_t kBaseClears = PG_QUERY_FLAG_FINAL_PERCENTILE | PG_QUERY_FLAG_KEEP_DEVICE_TABLE;
 
 }  // namespace
 
@@ -245,70 +111,34 @@ bool has_percentile(const pg_query& q) {
 
 void percentile_check(Segment& seg, const pg_query& q) {
   (void)pctl_plan(seg, q);
-  BaseQuery B;   // ... and what the ordinary part's plan refuses; compiled and cached for the execution that follows
-  base_query(q, B);
+  SideBaseQuery B;   // ... and what the ordinary part's plan refuses; compiled and cached for the execution that follows
+  side_base_query(q, is_percentile_agg, kBaseClears, B);
   check_null_handling(seg, B.q);
   (void)get_plan(seg, B.q.filter, &B.q);
 }
 
 std::unique_ptr<Result> execute_percentile(Segment& seg, const pg_query& q, const CancelToken* cancel) {
-  const double t0 = wall_ms();
+  const double t0 = now_ms();
   use_device(seg.device);
   const PctlPlan P = pctl_plan(seg, q);
-  const double t_plan = wall_ms();
+  const double t_plan = now_ms();
   const bool final_values = (q.flags & PG_QUERY_FLAG_FINAL_PERCENTILE) != 0;
-  // ---- the ordinary part ------------------------------------------------------------------------------------------------------------------
-  BaseQuery B;
-  base_query(q, B);
-  const std::vector<int>& base_index = B.base_index;
-  const pg_query& b = B.q;
-  std::unique_ptr<Result> res = execute_query(seg, b, cancel);
-  use_device(seg.device);
-  hipStream_t stream = thread_stream(seg.device);
-  const int32_t n_rows = q.n_group_by > 0 ? res->num_groups : 1;
-  // ---- the filter's match words (none without a filter and without an upsert snapshot) ---------------------------------------------------
-  bool snapshot = false;
-  {
-    std::lock_guard<std::mutex> lock(seg.mu);
-    snapshot = seg.queryable_doc_ids != nullptr;
-  }
-  std::unique_ptr<DocIdSet> ds;
-  int64_t M = seg.total_docs;
-  if (q.filter || snapshot) {
-    ds = execute_filter(seg, q.filter, q.flags & PG_QUERY_FLAG_NULL_HANDLING);
-    M = ds->cardinality;
-  }
-  if (cancel && cancel->requested.load(std::memory_order_acquire)) fail(PG_ERR_CANCELLED, "query cancelled (EarlyTerminationException)");
-  // ---- the admitted groups' keys -------------------------------------------------------------------------------------------------------------
-  std::vector<uint32_t> rows((size_t)n_rows, 0);
-  for (int j = 0; j < q.n_group_by; j++) {
-    const std::vector<uint32_t> ids = group_ids_of(*res, j, *P.group_cols[(size_t)j], *P.group_ids[(size_t)j], n_rows);
-    for (int32_t i = 0; i < n_rows; i++) {
-      if (ids[(size_t)i] >= (uint32_t)P.group_ids[(size_t)j]->cardinality) fail(PG_ERR_INTERNAL, "PERCENTILE: group key id %u of %s out of range", ids[(size_t)i], P.group_cols[(size_t)j]->name.c_str());
-      rows[(size_t)i] += (uint32_t)(ids[(size_t)i] * P.mult[(size_t)j]);
-    }
-  }
-  int cus = 0;
-  PG_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, seg.device));
-  cus = std::max(cus, 1);
+  SideBaseQuery B;
+  side_base_query(q, is_percentile_agg, kBaseClears, B);
+  SidePass S = side_pass_begin(seg, q, B, P.groups, kWho, cancel);
+  const int32_t n_rows = S.n_rows;
+  const int64_t M = S.M, n_words = S.n_words;
+  const int cus = S.cus;
+  hipStream_t stream = S.stream;
   DeviceBuffer d_rows((size_t)std::max(n_rows, 1) * 4);
-  if (n_rows > 0) PG_HIP(hipMemcpyAsync(d_rows.ptr, rows.data(), (size_t)n_rows * 4, hipMemcpyHostToDevice, stream));
-  const int64_t n_words = ((int64_t)seg.total_docs + 63) / 64;
+  if (n_rows > 0) PG_HIP(hipMemcpyAsync(d_rows.ptr, S.rows.data(), (size_t)n_rows * 4, hipMemcpyHostToDevice, stream));
   std::vector<AggResult> out((size_t)q.n_aggregations);
   const char* kernel = "";
   int64_t pass_bytes = 0;
   int32_t passes = 0;
   // PG_QUERY_FLAG_PROFILE: the percentile passes (counting, selection, runs and their copies) between two events of their own
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  struct EventGuard {
-    hipEvent_t* e;
-    ~EventGuard() { for (int i = 0; i < 2; i++) if (e[i]) (void)hipEventDestroy(e[i]); }
-  } ev_guard{ev};
-  if (q.flags & PG_QUERY_FLAG_PROFILE) {
-    PG_HIP(hipEventCreate(&ev[0]));
-    PG_HIP(hipEventCreate(&ev[1]));
-    PG_HIP(hipEventRecord(ev[0], stream));
-  }
+  ProfileTimer timer(q.flags);
+  timer.start(stream);
   for (const PctlColumn& pc : P.cols) {
     // ---- the counting pass ---------------------------------------------------------------------------------------------------------------
     const uint32_t C = (uint32_t)pc.ids->cardinality;
@@ -319,18 +149,7 @@ std::unique_ptr<Result> execute_percentile(Segment& seg, const pg_query& q, cons
     }
     PgPctlArgs A;
     memset(&A, 0, sizeof(A));
-    A.match = ds ? ds->words.as<uint64_t>() : nullptr;
-    A.n_words = n_words;
-    A.n_docs = seg.total_docs;
-    A.n_gcols = q.n_group_by;
-    int64_t id_bits = pc.ids->bits;
-    for (int j = 0; j < q.n_group_by; j++) {
-      A.gcols[j].data = P.group_ids[(size_t)j]->fwd_dev.as<uint8_t>();
-      A.gcols[j].bits = P.group_ids[(size_t)j]->bits;
-      A.gcols[j].card = P.group_ids[(size_t)j]->cardinality;
-      A.gcols[j].mult = P.mult[(size_t)j];
-      id_bits += P.group_ids[(size_t)j]->bits;
-    }
+    const int64_t id_bits = pc.ids->bits + side_scan_fill(A.scan, seg, S, P.groups);
     A.vcol.data = pc.ids->fwd_dev.as<uint8_t>();
     A.vcol.bits = pc.ids->bits;
     A.vcol.card = pc.ids->cardinality;
@@ -355,7 +174,7 @@ std::unique_ptr<Result> execute_percentile(Segment& seg, const pg_query& q, cons
     }
     kernel = pc.sort ? "pg_pctl_sort" : pc.lds ? "pg_pctl_lds" : "pg_pctl_hbm";
     passes++;
-    pass_bytes += ((int64_t)seg.total_docs * id_bits + 7) / 8 + (ds ? n_words * 8 : 0);
+    pass_bytes += ((int64_t)seg.total_docs * id_bits + 7) / 8 + (S.ds ? n_words * 8 : 0);
     if (n_rows == 0) {
       for (int a : pc.aggs) { out[(size_t)a].kind = final_values ? PG_RESULT_DOUBLE : PG_RESULT_VALUE_COUNTS; out[(size_t)a].param = q.agg_params[a]; }
       wait_stream(stream, cancel);
@@ -459,48 +278,10 @@ std::unique_ptr<Result> execute_percentile(Segment& seg, const pg_query& q, cons
       out[(size_t)a].param = q.agg_params[a];
     }
   }
-  float pass_ms = 0;
-  if (ev[0]) {
-    PG_HIP(hipEventRecord(ev[1], stream));
-    PG_HIP(hipEventSynchronize(ev[1]));
-    PG_HIP(hipEventElapsedTime(&pass_ms, ev[0], ev[1]));
-  }
-  // ---- the joined result ------------------------------------------------------------------------------------------------------------------------
-  std::vector<std::vector<uint8_t>> nulls;
-  if (!res->agg_nulls.empty()) nulls.assign((size_t)q.n_aggregations, {});
-  for (int a = 0; a < q.n_aggregations; a++) {
-    const int bi = base_index[(size_t)a];
-    if (bi < 0) continue;
-    out[(size_t)a] = std::move(res->aggs[(size_t)bi]);
-    if (!nulls.empty() && (size_t)bi < res->agg_nulls.size()) nulls[(size_t)a] = std::move(res->agg_nulls[(size_t)bi]);
-  }
-  res->aggs = std::move(out);
-  res->agg_nulls = std::move(nulls);
-  res->dev.reset();
+  const float pass_ms = timer.stop_ms();
+  std::unique_ptr<Result> res = side_pass_finish(seg, q, B, S, out, {kernel, pass_bytes, P.n_columns_read, pass_ms, t0, t_plan});
   res->percentile = true;
-  pg_exec_stats& st = res->stats;
-  st.num_docs_scanned = M;
-  st.num_entries_scanned_post_filter = M * P.n_columns_read;
-  if (ds) {
-    st.num_entries_scanned_in_filter = ds->stats.num_entries_scanned_in_filter;
-    st.stats_exact = ds->stats.stats_exact;
-    st.filter_stats_path = ds->stats.filter_stats_path;
-    st.device_ms_filter += ds->stats.device_ms_filter;
-  } else {
-    st.num_entries_scanned_in_filter = 0;
-    st.stats_exact = 1;
-  }
-  st.device_ms_aggregate += pass_ms;
-  st.device_ms_total += pass_ms + (ds ? ds->stats.device_ms_filter : 0.0f);
-  st.num_total_docs = seg.total_docs;
-  st.star_tree_index = -1;
-  st.algorithmic_bytes += pass_bytes;
-  st.percentile_passes = passes;
-  snprintf(st.kernel, sizeof(st.kernel), "%s", kernel);
-  fill_result_schema(seg, q, *res);
-  res->null_handling = (q.flags & PG_QUERY_FLAG_NULL_HANDLING) != 0;
-  st.host_ms_plan += (float)(t_plan - t0);
-  st.host_ms_total = (float)(wall_ms() - t0);
+  res->stats.percentile_passes = passes;
   return res;
 }
 

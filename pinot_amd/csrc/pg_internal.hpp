@@ -10,6 +10,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <set>
 #include <stdexcept>
 #include <string>
 #include <unordered_map>
@@ -17,6 +18,7 @@
 
 #include "../../include/pinot_gpu.h"
 #include "pg_device.h"
+#include "pg_side_query.h"
 
 namespace pg {
 
@@ -475,16 +477,72 @@ struct CancelToken { std::atomic<int> requested{0}; };
 void device_init(int ordinal);          // pg_init: validates + selects the default device
 int default_device();                   // the device pg_segment_create pins on (0 unless pg_init chose another)
 void use_device(int ordinal);           // makes `ordinal` current on the calling thread, initialising it on first use
+int device_cus(int ordinal);            // its compute units (after use_device(ordinal))
+double now_ms();                        // the host clock of host_ms_plan / host_ms_total
 std::unique_ptr<Result> execute_query(Segment& seg, const pg_query& q, const CancelToken* cancel);         // pg_nullaware.cpp: query-level null handling above ...
 // internal query flag (never set by callers: pg_query_exec masks it): the query is a part of a null-partitioned one — its filter is evaluated in
 // three-valued logic even where the reference's FastFilteredCountOperator would not (a lone COUNT(*) over an index-only filter)
 constexpr int32_t kQueryFlagNullPartition = 0x40000000;
 std::unique_ptr<Result> execute_distinct(Segment& seg, const pg_query& q, const CancelToken* cancel);   // PG_QUERY_FLAG_DISTINCT (pg_exec.hip)
 std::unique_ptr<Result> execute_selection(Segment& seg, const pg_query& q, const CancelToken* cancel);  // PG_QUERY_FLAG_SELECTION (pg_exec.hip)
-// queries with a PERCENTILE aggregation (pg_exec_percentile.hip): the checks of the path (pg_query_supported), and the query itself — the
-// ordinary part through execute_query, one counting pass per distinct percentile column joined to its groups by key
-// the sort tier's runs (pg_kernels_percentile.hip): the matching docs' keys written compacted, sorted over their significant bits and run-length
-// encoded on `stream`; returns after the stream drained (the number of runs is read back)
+// ---- side passes: aggregations answered by a pass of their own and joined to the ordinary plan by group key -------------------------------
+// The frame they share (pg_exec_sidepass.hip; `who` names the path in messages — "PERCENTILE" / "expression" —, `subject` is how a refusal
+// names its aggregation: "PERCENTILE" / "an aggregation over an expression").
+bool column_has_nulls(Segment& seg, const std::string& name);   // seg.mu held
+Column* id_column(Segment& seg, Column& c, const char* what, const char* who);   // seg.mu held
+std::vector<uint32_t> group_ids_of(const Result& r, int j, const Column& col, const Column& ids, int32_t n_rows, const char* who);
+void wait_stream(hipStream_t stream, const CancelToken* cancel);   // polls the token while the stream drains (no spin limiter)
+void side_query_check(const pg_query& q, const char* subject);     // the query's aggregation and group-by lists, before the path plans them
+struct SideGroups {
+  std::vector<Column*> group_cols, group_ids;   // the group-by columns and their fixed-bit ids
+  std::vector<uint64_t> mult;                   // weight of the group column's digit (column 0 least significant)
+  uint64_t G = 1;
+};
+SideGroups side_groups(Segment& seg, const pg_query& q, const char* subject, const char* who, std::set<std::string>& read);   // seg.mu held; adds the columns' names to `read`
+void side_base_query(const pg_query& q, bool (*is_side)(const pg_agg_spec&), int32_t clear_flags, SideBaseQuery& out);   // pg_side_query.h, failing through fail()
+// the ordinary part's result, the filter's match words and the admitted groups' rows (rows[i]: the mixed-radix key of group i)
+struct SidePass {
+  std::unique_ptr<Result> res;
+  std::unique_ptr<DocIdSet> ds;   // null: no filter and no upsert snapshot, every doc matches
+  int64_t M = 0;                  // matching docs
+  int32_t n_rows = 0;
+  std::vector<uint32_t> rows;
+  int64_t n_words = 0;            // ceil(total_docs / 64)
+  hipStream_t stream = nullptr;
+  int cus = 1;
+};
+SidePass side_pass_begin(Segment& seg, const pg_query& q, const SideBaseQuery& B, const SideGroups& G, const char* who, const CancelToken* cancel);
+int64_t side_scan_fill(PgGroupScan& scan, const Segment& seg, const SidePass& S, const SideGroups& G);   // returns the group columns' bits per doc
+// PG_QUERY_FLAG_PROFILE: a pass between two events of its own (without the flag there are none and stop_ms() is 0)
+class ProfileTimer {
+ public:
+  explicit ProfileTimer(int32_t query_flags);
+  ~ProfileTimer();
+  ProfileTimer(const ProfileTimer&) = delete;
+  ProfileTimer& operator=(const ProfileTimer&) = delete;
+  void start(hipStream_t stream);
+  float stop_ms();   // waits for the stream under the flag
+ private:
+  hipEvent_t ev_[2] = {nullptr, nullptr};
+  hipStream_t stream_ = nullptr;
+};
+struct SidePassStats {
+  const char* kernel;
+  int64_t pass_bytes;     // the pass's algorithmic bytes
+  int n_columns_read;     // distinct columns the query projects (ProjectOperator#getNumColumnsProjected)
+  float pass_ms;
+  double t0, t_plan;      // now_ms() at the start of the query and after its planning
+};
+// the ordinary part's columns and null vectors moved to their places in `out` (through B.base_index), `out` made the result's aggregations,
+// every statistic of the query written, the schema filled
+std::unique_ptr<Result> side_pass_finish(Segment& seg, const pg_query& q, const SideBaseQuery& B, SidePass& S, std::vector<AggResult>& out, const SidePassStats& P);
+// Queries with a PERCENTILE aggregation (pg_exec_percentile.hip): percentile_check are the checks of the path (pg_query_supported);
+// execute_percentile runs the ordinary part and one counting pass per distinct percentile column.
+bool has_percentile(const pg_query& q);
+void percentile_check(Segment& seg, const pg_query& q);
+std::unique_ptr<Result> execute_percentile(Segment& seg, const pg_query& q, const CancelToken* cancel);
+// ... its sort tier's runs (pg_kernels_percentile.hip): the matching docs' keys written compacted, sorted over their significant bits and
+// run-length encoded on `stream`; returns after the stream drained (the number of runs is read back)
 struct PctlSortRuns {
   DeviceBuffer keys, cum;       // [n_runs] distinct keys ascending, inclusive prefix sums of their counts
   DeviceBuffer counts;          // [n_runs] uint32
@@ -492,18 +550,10 @@ struct PctlSortRuns {
 };
 size_t pctl_sort_bytes(int64_t n_matches);   // bytes of the work area (keys in and out, runs, rocprim's temporaries)
 void pctl_sort_build(const PgPctlArgs& A, int64_t n_matches, int key_bits, hipStream_t stream, PctlSortRuns& out);
-bool has_percentile(const pg_query& q);
-void percentile_check(Segment& seg, const pg_query& q);
-std::unique_ptr<Result> execute_percentile(Segment& seg, const pg_query& q, const CancelToken* cancel);
-// shared by the side passes that join the ordinary plan by group key (pg_exec_percentile.hip; `who` names the path in messages)
-bool column_has_nulls(Segment& seg, const std::string& name);   // seg.mu held
-Column* id_column(Segment& seg, Column& c, const char* what, const char* who = "PERCENTILE");   // seg.mu held
-std::vector<uint32_t> group_ids_of(const Result& r, int j, const Column& col, const Column& ids, int32_t n_rows, const char* who = "PERCENTILE");
-void wait_stream(hipStream_t stream, const CancelToken* cancel);
-// queries with an aggregation over an arithmetic expression (pg_exec_expr.hip): SUM / MIN / MAX / AVG / MINMAXRANGE whose pg_agg_spec.column
-// is an expression text (pg_expr.h).  The ordinary part through execute_query, a bounds pass per (segment, expression), one accumulation
-// pass for all expressions of the query joined to the ordinary part's groups by key.  expression_check: the checks of the path
-// (pg_query_supported); the bounds are answered from the segment's cache when it is filled, else the shape is let through.
+// Queries with an aggregation over an arithmetic expression (pg_exec_expr.hip): SUM / MIN / MAX / AVG / MINMAXRANGE whose pg_agg_spec.column
+// is an expression text (pg_expr.h).  A bounds pass per (segment, expression), one accumulation pass for all expressions of the query.
+// expression_check: the checks of the path (pg_query_supported); the bounds are answered from the segment's cache when it is filled, else
+// the shape is let through.
 bool has_expression(const pg_query& q);
 void expression_check(Segment& seg, const pg_query& q);
 std::unique_ptr<Result> execute_expression(Segment& seg, const pg_query& q, const CancelToken* cancel);

@@ -82,20 +82,6 @@ DEVFN int64_t expr_order_key(double v) {   // order-preserving map double -> int
   return b ^ ((b >> 63) & 0x7FFFFFFFFFFFFFFFLL);
 }
 
-DEVFN uint64_t expr_group_of(const PgExprArgs& a, uint32_t doc) {
-  uint64_t g = 0;
-  for (int j = 0; j < a.n_gcols; j++) g += (uint64_t)pg_fixed_bit_id_at(a.gcols[j], doc) * a.gcols[j].mult;
-  return g;
-}
-
-// the match word `w` with the bits of docs that do not exist cleared (w < n_words)
-DEVFN uint64_t expr_match_word(const PgExprArgs& a, int64_t w) {
-  uint64_t v = a.match ? a.match[w] : ~0ULL;
-  const int64_t rem = a.n_docs - w * 64;
-  if (rem < 64) v &= ~0ULL >> (64 - rem);
-  return v;
-}
-
 DEVFN int64_t wave_sum_i64(int64_t v) {
   for (int off = 32; off > 0; off >>= 1) v += (int64_t)__shfl_xor((long long)v, off);
   return v;
@@ -114,7 +100,7 @@ constexpr int kWordsPerWave = 4;
 // the tiers with a table: `row0` is the table's first slot — the workgroup's copy in LDS, or the table in HBM
 template <typename Ptr>
 DEVFN void expr_update(const PgExprArgs& a, Ptr row0, uint32_t doc) {
-  const uint64_t g = expr_group_of(a, doc);
+  const uint64_t g = pg_scan_group_key(a.scan, doc);
   if (g >= a.n_groups) return;   // (ids below their cardinalities never are)
   Ptr row = row0 + g * (uint64_t)a.slots;
   const d8 s = expr_load_all(a, doc);
@@ -149,12 +135,12 @@ DEVFN void expr_table_body(const PgExprArgs& a) {
     __syncthreads();
   }
   const int64_t stride = (int64_t)gridDim.x * waves * kWordsPerWave;
-  for (int64_t w0 = ((int64_t)blockIdx.x * waves + wave) * kWordsPerWave; w0 < a.n_words; w0 += stride) {
+  for (int64_t w0 = ((int64_t)blockIdx.x * waves + wave) * kWordsPerWave; w0 < a.scan.n_words; w0 += stride) {
 #pragma unroll 1
     for (int u = 0; u < kWordsPerWave; u++) {
       const int64_t w = w0 + u;
-      if (w >= a.n_words) break;
-      const uint64_t m = expr_match_word(a, w);
+      if (w >= a.scan.n_words) break;
+      const uint64_t m = pg_scan_match_word(a.scan, w);
       if (m == 0) continue;   // a word without a match costs one scalar load
       if ((m >> lane) & 1) {
         if (LDS) expr_update(a, s_tab, (uint32_t)(w * 64 + lane));
@@ -194,12 +180,12 @@ extern "C" __global__ void __launch_bounds__(256) pg_expr_reg(const PgExprArgs a
     for (int l = 0; l < PG_EXPR_SUM_LIMBS; l++) sum[e][l] = 0;
   }
   const int64_t stride = (int64_t)gridDim.x * waves * kWordsPerWave;
-  for (int64_t w0 = ((int64_t)blockIdx.x * waves + wave) * kWordsPerWave; w0 < a.n_words; w0 += stride) {
+  for (int64_t w0 = ((int64_t)blockIdx.x * waves + wave) * kWordsPerWave; w0 < a.scan.n_words; w0 += stride) {
 #pragma unroll 1
     for (int u = 0; u < kWordsPerWave; u++) {
       const int64_t w = w0 + u;
-      if (w >= a.n_words) break;
-      const uint64_t m = expr_match_word(a, w);
+      if (w >= a.scan.n_words) break;
+      const uint64_t m = pg_scan_match_word(a.scan, w);
       if (m == 0) continue;
       if (!((m >> lane) & 1)) continue;
       const d8 s = expr_load_all(a, (uint32_t)(w * 64 + lane));
@@ -253,7 +239,7 @@ extern "C" __global__ void __launch_bounds__(256) pg_expr_reg(const PgExprArgs a
 // Expression 0 of `a` over ALL docs: out[0] = the bits of the largest finite |value|, out[1] = 1 when a NaN / Inf occurs
 extern "C" __global__ void __launch_bounds__(256) pg_expr_bounds(const PgExprArgs a, unsigned long long* __restrict__ out) {
   unsigned long long mx = 0, bad = 0;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n_docs; i += (int64_t)gridDim.x * blockDim.x) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.scan.n_docs; i += (int64_t)gridDim.x * blockDim.x) {
     const d8 s = expr_load_all(a, (uint32_t)i);
     const double v = expr_eval(a, 0, s);
     unsigned long long b = (unsigned long long)__double_as_longlong(v) & 0x7FFFFFFFFFFFFFFFULL;

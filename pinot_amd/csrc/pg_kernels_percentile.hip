@@ -27,24 +27,10 @@
 
 namespace {
 
-// id of `doc` in a fixed-bit column: a per-doc gather of one or two dwords (pg_fixed_bit_id_at, pg_device.h), as the DISTINCT path reads them
-DEVFN uint32_t pctl_id_at(const PgDistinctCol& c, uint32_t doc) { return pg_fixed_bit_id_at(c, doc); }
-
 constexpr uint32_t kNoKey = 0xFFFFFFFFu;   // n_keys < 2^32: never a key
 
-DEVFN uint64_t pctl_key64_of(const PgPctlArgs& a, uint32_t doc) {
-  uint64_t g = 0;
-  for (int j = 0; j < a.n_gcols; j++) g += (uint64_t)pctl_id_at(a.gcols[j], doc) * a.gcols[j].mult;
-  return g * a.card + pctl_id_at(a.vcol, doc);
-}
-
-// the match word `w` with the bits of docs that do not exist cleared (w < n_words)
-DEVFN uint64_t pctl_match_word(const PgPctlArgs& a, int64_t w) {
-  uint64_t v = a.match ? a.match[w] : ~0ULL;
-  const int64_t rem = a.n_docs - w * 64;
-  if (rem < 64) v &= ~0ULL >> (64 - rem);
-  return v;
-}
+// key = groupKey x C + valueId: the ids are per-doc gathers of one or two dwords (pg_fixed_bit_id_at, pg_device.h), as the DISTINCT path reads them
+DEVFN uint64_t pctl_key64_of(const PgPctlArgs& a, uint32_t doc) { return pg_scan_group_key(a.scan, doc) * a.card + pg_fixed_bit_id_at(a.vcol, doc); }
 
 DEVFN uint32_t pctl_key_of(const PgPctlArgs& a, uint32_t doc) {   // the dense tiers' key: below n_keys < 2^32
   const uint64_t key = pctl_key64_of(a, doc);
@@ -65,12 +51,12 @@ DEVFN void pctl_count_body(const PgPctlArgs& a) {
     __syncthreads();
   }
   const int64_t stride = (int64_t)gridDim.x * waves * kWordsPerWave;
-  for (int64_t w0 = ((int64_t)blockIdx.x * waves + wave) * kWordsPerWave; w0 < a.n_words; w0 += stride) {
+  for (int64_t w0 = ((int64_t)blockIdx.x * waves + wave) * kWordsPerWave; w0 < a.scan.n_words; w0 += stride) {
     uint64_t m[kWordsPerWave];
 #pragma unroll
     for (int u = 0; u < kWordsPerWave; u++) {
       const int64_t w = w0 + u;
-      m[u] = w < a.n_words ? pctl_match_word(a, w) : 0;
+      m[u] = w < a.scan.n_words ? pg_scan_match_word(a.scan, w) : 0;
     }
     if ((m[0] | m[1] | m[2] | m[3]) == 0) continue;
     uint32_t key[kWordsPerWave];
@@ -184,7 +170,7 @@ extern "C" __global__ void __launch_bounds__(256) pg_pctl_runs(const uint32_t* _
 extern "C" __global__ void __launch_bounds__(PG_TILE_WORDS) pg_pctl_tile_counts(const PgPctlArgs a, int64_t* __restrict__ counts) {
   __shared__ uint32_t s[PG_TILE_WORDS];
   const int64_t w = (int64_t)blockIdx.x * PG_TILE_WORDS + threadIdx.x;
-  s[threadIdx.x] = w < a.n_words ? (uint32_t)__popcll(pctl_match_word(a, w)) : 0u;
+  s[threadIdx.x] = w < a.scan.n_words ? (uint32_t)__popcll(pg_scan_match_word(a.scan, w)) : 0u;
   __syncthreads();
   for (int off = PG_TILE_WORDS / 2; off > 0; off >>= 1) {
     if ((int)threadIdx.x < off) s[threadIdx.x] += s[threadIdx.x + off];
@@ -200,7 +186,7 @@ extern "C" __global__ void __launch_bounds__(PG_TILE_WORDS) pg_pctl_sort(const P
   __shared__ uint32_t s[PG_TILE_WORDS];
   const int t = threadIdx.x;
   const int64_t w_t = (int64_t)blockIdx.x * PG_TILE_WORDS + t;
-  const uint32_t pc = w_t < a.n_words ? (uint32_t)__popcll(pctl_match_word(a, w_t)) : 0u;
+  const uint32_t pc = w_t < a.scan.n_words ? (uint32_t)__popcll(pg_scan_match_word(a.scan, w_t)) : 0u;
   s[t] = pc;
   for (int off = 1; off < PG_TILE_WORDS; off <<= 1) {
     __syncthreads();
@@ -214,8 +200,8 @@ extern "C" __global__ void __launch_bounds__(PG_TILE_WORDS) pg_pctl_sort(const P
   const int64_t base = tile_offsets[blockIdx.x];
   for (int i = wave; i < PG_TILE_WORDS; i += PG_TILE_WORDS / 64) {
     const int64_t w = (int64_t)blockIdx.x * PG_TILE_WORDS + i;
-    if (w >= a.n_words) break;
-    const uint64_t m = pctl_match_word(a, w);
+    if (w >= a.scan.n_words) break;
+    const uint64_t m = pg_scan_match_word(a.scan, w);
     if (m == 0) continue;
     if ((m >> lane) & 1) {
       const int64_t pos = base + (i ? s[i - 1] : 0u) + __popcll(m & ((1ULL << lane) - 1ULL));
@@ -298,7 +284,7 @@ void pctl_sort_build(const PgPctlArgs& A, int64_t n_matches, int key_bits, hipSt
   out.n_runs = 0;
   if (n_matches <= 0) return;
   const size_t n = (size_t)n_matches;
-  const int64_t n_tiles = (A.n_words + PG_TILE_WORDS - 1) / PG_TILE_WORDS;
+  const int64_t n_tiles = (A.scan.n_words + PG_TILE_WORDS - 1) / PG_TILE_WORDS;
   // offsets from the tiles' match counts
   DeviceBuffer counts((size_t)(n_tiles + 1) * 8), offsets((size_t)(n_tiles + 1) * 8);
   PG_HIP(hipMemsetAsync(counts.ptr, 0, (size_t)(n_tiles + 1) * 8, stream));

@@ -1,0 +1,27 @@
+// The ordinary part of a query that carries side aggregations — aggregations answered by a pass of their own and joined to the ordinary plan
+// by group key (exact PERCENTILE: pg_exec_percentile.hip; aggregations over an expression: pg_exec_expr.hip; the frame they share:
+// pg_exec_sidepass.hip).  Plain C++ over include/pinot_gpu.h without HIP types: it compiles stand-alone (tests/side_query_main.cpp).
+#pragma once
+#include "../../include/pinot_gpu.h"
+
+#include <string>
+#include <vector>
+
+namespace pg {
+// The query without its side aggregations (COUNT(*) if nothing else remains), never on a star-tree (PG_QUERY_FLAG_SKIP_STAR_TREE), its
+// ORDER BY re-indexed — or dropped when it names a side aggregation: the segment is then not trimmed (LIMIT stays).  `q` points into the
+// vectors: the struct is filled in place and not copied.
+struct SideBaseQuery {
+  std::vector<pg_agg_spec> aggs;
+  std::vector<double> params;    // the kept aggregations' agg_params (q.agg_params is null when the query had none)
+  std::vector<pg_order_by> order;
+  std::vector<int> base_index;   // per aggregation of the query: its index in the ordinary part, -1 for a side aggregation
+  pg_query q;
+  SideBaseQuery() = default;
+  SideBaseQuery(const SideBaseQuery&) = delete;
+  SideBaseQuery& operator=(const SideBaseQuery&) = delete;
+};
+// `is_side`: is this aggregation answered by the side pass?  `clear_flags`: PG_QUERY_FLAG_* bits the ordinary part must not see.
+// PG_OK, or PG_ERR_INVALID_ARGUMENT (an ORDER BY aggregation index out of range) with the reason in `error`.
+int32_t side_base_query(const pg_query& q, bool (*is_side)(const pg_agg_spec&), int32_t clear_flags, SideBaseQuery& out, std::string& error);
+}  // namespace pg
