@@ -140,6 +140,28 @@ typedef enum pg_predicate_type {  /* Predicate.Type (subset on the path) */
 
 #define PG_RANGE_UNBOUNDED "*"    /* RangePredicate.UNBOUNDED */
 
+/* A predicate's `column` is the left-hand side: a column name, or — ExpressionFilterOperator — an ARITHMETIC EXPRESSION, under exactly the rules
+ * of pg_agg_spec.column: the text ExpressionContext#toString prints, fn(arg,arg,...) over add / sub / mult / div (aliases plus / minus / times /
+ * divide), single-value INT / LONG / FLOAT / DOUBLE columns (dictionary-encoded or raw) and numeric literals (bare or single-quoted); a name
+ * containing '(' is an expression; at most 15 operations and 8 distinct columns.  "WHERE a > b" arrives so, as minus(a,b) > 0
+ * (PredicateComparisonRewriter).  The expression's type is DOUBLE (the four transform functions' getResultMetadata); it is evaluated in IEEE
+ * double, one rounded operation at a time in the reference's argument order, and EQ / NOT_EQ / IN / NOT_IN / RANGE apply with the reference's
+ * raw DOUBLE evaluators:
+ *   RANGE        v >= lower && v <= upper, an exclusive bound moved by nextUp / nextDown first (one at its infinity: PG_ERR_INVALID_ARGUMENT,
+ *                "Invalid range")
+ *   EQ / NOT_EQ  numeric == / !=: -0.0 equals 0.0, NaN equals nothing
+ *   IN / NOT_IN  membership in a DoubleOpenHashSet, i.e. by Double.doubleToLongBits: -0.0 is NOT in {0.0}, NaN IS in a set that holds NaN
+ *                (predicates over a raw DOUBLE column compare numerically here; the two differ for these values only)
+ * A NaN or an infinity among the values is not refused: a division by zero simply matches or does not, as Java's comparisons say.
+ * The leaf's doc set is computed once, when the query's plan is compiled — one pass over all docs per leaf — and kept with the cached plan
+ * (numDocs / 8 bytes per leaf).  numEntriesScannedInFilter counts the docs the reference's ExpressionScanDocIdIterator evaluates (blocks of
+ * 10 000), not operand columns; numEntriesScannedPostFilter does not count the filter's operands.  A star-tree never answers such a query.
+ * Refused, each with its own pg_last_error text, alike by pg_query_supported, pg_filter_exec and pg_query_exec:
+ *   PG_ERR_UNSUPPORTED       IS_NULL / IS_NOT_NULL over an expression; a multi-value, STRING or BYTES operand; mod or any other function;
+ *                            more than 4 expression predicates in one filter; under PG_QUERY_FLAG_NULL_HANDLING an operand column that
+ *                            holds nulls (columns without nulls run); more than 15 operations or 8 columns
+ *   PG_ERR_INVALID_ARGUMENT  malformed text, a literal that is no number
+ *   PG_ERR_NOT_FOUND         an unknown column */
 typedef struct pg_filter_node {
   int32_t type;                          /* pg_filter_type */
   int32_t n_children;                    /* AND / OR: >=1; NOT: 1 */
@@ -147,7 +169,7 @@ typedef struct pg_filter_node {
   /* PG_FILTER_PREDICATE only */
   int32_t predicate_type;                /* pg_predicate_type */
   int32_t n_values;                      /* EQ / NOT_EQ: 1; IN / NOT_IN: >=1 */
-  const char* column;                    /* lhs identifier */
+  const char* column;                    /* lhs identifier, or an arithmetic expression's text (see above) */
   const char* const* values;             /* literal strings */
   const char* lower;                     /* RANGE: lower bound or "*" */
   const char* upper;                     /* RANGE: upper bound or "*" */

@@ -314,10 +314,14 @@ public final class NativeQuery implements AutoCloseable {
   }
 
   private static boolean putPredicate(ByteBuffer b, Predicate p) {
-    if (p.getLhs().getType() != ExpressionContext.Type.IDENTIFIER) {
-      return false;
+    // the left-hand side: a column, or an arithmetic expression over columns and literals (ExpressionFilterOperator: WHERE a * b > 10, and
+    // every column-to-column comparison, which PredicateComparisonRewriter turns into minus(a,b) > 0) handed over as the text
+    // ExpressionContext#toString prints (pg_filter_node.column; the library parses it, as it does an aggregation's argument)
+    ExpressionContext lhs = p.getLhs();
+    String column = lhs.getType() == ExpressionContext.Type.IDENTIFIER ? lhs.getIdentifier() : isArithmetic(lhs) ? lhs.toString() : null;
+    if (column == null) {
+      return false;   // another function on the left: the default plan
     }
-    String column = p.getLhs().getIdentifier();
     b.putInt(F_PREDICATE).putInt(0);
     switch (p.getType()) {
       case EQ:

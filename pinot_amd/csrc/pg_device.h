@@ -622,6 +622,25 @@ struct PgExprArgs {
   int64_t ident[PG_EXPR_MAX_SLOTS];   // per slot of a row: 0 (SUM limbs, count), INT64_MAX (MIN), INT64_MIN (MAX)
   pg_expr_step steps[PG_EXPR_MAX_EXPRS * PG_EXPR_MAX_OPS];
 };
+// ---- an arithmetic expression as a filter leaf (pg_kernels_exprpred.hip) -----------------------------------------------------------------------
+// The reference's ExpressionFilterOperator: expression 0 of a PgExprArgs evaluated over ALL docs and compared by the raw DOUBLE predicate
+// evaluators; the leaf's doc set is written as match words in the layout PG_F_PUSH_WORDS reads.
+#define PG_EXPR_PRED_WORDS 4   // 64-doc words a wavefront of pg_expr_pred takes per iteration
+enum PgExprPredKind : int32_t {
+  PG_XP_RANGE = 0,    // lo <= v && v <= hi   (exclusive bounds already moved by nextafter)
+  PG_XP_EQ = 1,       // v == lo              (numeric: -0.0 equals 0.0, NaN equals nothing)
+  PG_XP_NOT_EQ = 2,   // v != lo
+  PG_XP_IN = 3,       // doubleToLongBits(v) among `set` (DoubleOpenHashSet: -0.0 is not 0.0, every NaN is the one NaN)
+  PG_XP_NOT_IN = 4
+};
+struct PgExprPred {
+  int32_t kind;           // PgExprPredKind
+  int32_t n_set;
+  double lo, hi;
+  const uint64_t* set;    // IN / NOT_IN: the values' canonical bit patterns
+  uint64_t* out;          // bit b of word w is doc 64 w + b; the kernel writes words [0, n_words), bits at and beyond n_docs clear
+  int64_t n_words;        // ceil(n_docs / 64)
+};
 
 struct PgTrimArgs {
   const int64_t* table;     // [n_ops][G]

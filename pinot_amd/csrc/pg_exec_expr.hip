@@ -77,14 +77,7 @@ struct ExprPlan {
   int n_columns_read = 0;       // distinct columns the query projects (ProjectOperator#getNumColumnsProjected)
 };
 
-void fill_src(PgValueSrc& S, const Column& c) {
-  S.data = c.fwd_dev.as<uint8_t>();
-  S.dict = c.has_dictionary ? c.dict_dev.ptr : nullptr;
-  S.col_kind = c.col_kind;
-  S.bits = c.bits;
-  S.val_type = c.val_type;
-  S.fx_q = 0;
-}
+void fill_src(PgValueSrc& S, const Column& c) { expr_fill_src(S, c); }
 
 // the bounds pass of one expression over every doc of the segment (seg.mu NOT held: it only reads registered columns, which never change or
 // go away while the segment lives; the device is current)
@@ -161,14 +154,7 @@ ExprPlan expr_plan(Segment& seg, const pg_query& q, bool compute_bounds) {
       if (st != PG_OK) fail(st, "%s (in %s)", error.c_str(), item.text.size() > 200 ? (item.text.substr(0, 197) + "...").c_str() : item.text.c_str());
       std::vector<Column*> cols;
       for (const std::string& name : item.prog.columns) {
-        Column* c = seg.find(name.c_str());
-        if (!c) fail(PG_ERR_NOT_FOUND, "column not found: %s", name.size() > 200 ? (name.substr(0, 197) + "...").c_str() : name.c_str());
-        if (c->is_mv || c->raw_mv) fail(PG_ERR_UNSUPPORTED, "expression over the multi-value column %s", c->name.c_str());
-        if (c->data_type > PG_TYPE_DOUBLE) fail(PG_ERR_UNSUPPORTED, "expression over the %s column %s", c->data_type == PG_TYPE_STRING ? "STRING" : "BYTES", c->name.c_str());
-        if (null_handling && column_has_nulls(seg, c->name)) fail(PG_ERR_UNSUPPORTED, "enableNullHandling: expression over %s, which holds nulls", c->name.c_str());
-        const bool dict_ok = c->has_dictionary && c->col_kind == PG_COL_FIXED_BIT && c->bits >= 1 && c->bits <= 31 && c->cardinality >= 1 && c->dict_dev.ptr;
-        const bool raw_ok = !c->has_dictionary && (c->col_kind == PG_COL_RAW32 || c->col_kind == PG_COL_RAW64);
-        if (!dict_ok && !raw_ok) fail(PG_ERR_UNSUPPORTED, "expression: operand column %s (layout %d, %d bits)", c->name.c_str(), c->col_kind, c->bits);
+        Column* c = expr_operand_column(seg, name, null_handling);   // the rules expression predicates share (pg_plan.cpp)
         read.insert(c->name);
         cols.push_back(c);
         size_t j = 0;

@@ -27,6 +27,7 @@ namespace pg {
 
 static const int32_t kEof = -1;   // Constants.EOF
 static const int kScanBatch = 256;   // BlockDocIdIterator.OPTIMAL_ITERATOR_BATCH_SIZE
+static const int kExprBlock = 10000; // DocIdSetPlanNode.MAX_DOC_PER_CALL
 
 int64_t HostBits::next_set(int64_t from) const {
   if (from < 0) from = 0;
@@ -69,6 +70,7 @@ struct It {
   virtual int32_t advance(int32_t target) = 0;
   virtual const HostBits* doc_ids() const { return nullptr; }                 // BitmapBasedDocIdIterator#getDocIds
   virtual const std::vector<std::pair<int32_t, int32_t>>* ranges() const { return nullptr; }   // SortedDocIdIterator#getDocIdRanges
+  virtual void apply_and(HostBits&) {}                                        // ScanBasedDocIdIterator#applyAnd (ItKind::Scan)
 };
 using ItPtr = std::unique_ptr<It>;
 
@@ -134,7 +136,7 @@ struct ScanIt : It {
     next_doc = p + 1;
     return (int32_t)p;
   }
-  void apply_and(HostBits& doc_ids_io) {   // :115-142 — every candidate is evaluated once
+  void apply_and(HostBits& doc_ids_io) override {   // :115-142 — every candidate is evaluated once
     if (mv_off) {
       for (size_t i = 0; i < doc_ids_io.w.size(); i++)
         for (uint64_t x = doc_ids_io.w[i]; x; x &= x - 1) {
@@ -145,6 +147,66 @@ struct ScanIt : It {
       c.entries += doc_ids_io.cardinality();
     }
     for (size_t i = 0; i < doc_ids_io.w.size(); i++) doc_ids_io.w[i] &= m.w[i];
+  }
+};
+
+// ExpressionScanDocIdIterator (ExpressionScanDocIdIterator.java:81-145) over the leaf's match bitmap.  It is a ScanBasedDocIdIterator that
+// evaluates whole blocks of MAX_DOC_PER_CALL docs and counts every doc of a block it evaluates (_numEntriesScanned += numDocs, :151): docs,
+// not operand columns.
+struct ExprIt : It {
+  const HostBits& m;
+  Counter& c;
+  int64_t block_end = 0;            // _blockEndDocId
+  int64_t cur = -1, cur_end = 0;    // _docIdIterator: the matches of [.., cur_end) from `cur` on; cur < 0: null
+  ExprIt(const HostBits& bits, Counter& counter) : m(bits), c(counter) { kind = ItKind::Scan; }
+  int32_t in_block(int64_t from) {
+    const int64_t p = m.next_set(from);
+    if (p < 0 || p >= cur_end) { cur = cur_end; return kEof; }
+    cur = p + 1;
+    return (int32_t)p;
+  }
+  int32_t next() override {   // :81-102
+    if (cur >= 0) {           // the rest of the current block first
+      const int32_t d = in_block(cur);
+      if (d != kEof) return d;
+    }
+    const int64_t n = m.n_docs;
+    while (block_end < n) {   // whole blocks from _blockEndDocId until one holds a match
+      const int64_t start = block_end;
+      block_end = std::min<int64_t>(start + kExprBlock, n);
+      c.entries += block_end - start;
+      const int64_t p = m.next_set(start);
+      if (p >= 0 && p < block_end) {
+        cur = p + 1;
+        cur_end = block_end;
+        return (int32_t)p;
+      }
+      if (p < 0) {            // no match left: every remaining block is evaluated
+        c.entries += n - block_end;
+        block_end = n;
+      } else {                // the empty blocks before the one that holds p
+        const int64_t skipped = (p - block_end) / kExprBlock;
+        c.entries += skipped * kExprBlock;
+        block_end += skipped * kExprBlock;
+      }
+    }
+    return kEof;
+  }
+  int32_t advance(int32_t target) override {   // :104-120
+    if (target < block_end) {
+      if (cur >= 0) {          // advanceIfNeeded never moves backwards
+        const int32_t d = in_block(std::max<int64_t>(cur, target));
+        if (d != kEof) return d;
+      }
+    } else {
+      block_end = target;      // the blocks before the target are skipped: the next one STARTS at the target
+    }
+    cur = -1;
+    return next();
+  }
+  void apply_and(HostBits& doc_ids_io) override {   // :135-145 — a projection over exactly the candidates
+    c.entries += doc_ids_io.cardinality();
+    for (size_t i = 0; i < doc_ids_io.w.size(); i++) doc_ids_io.w[i] &= i < m.w.size() ? m.w[i] : 0;
   }
 };
 
@@ -309,7 +371,7 @@ struct NotIt : It {   // NotDocIdIterator.java:28-70
 };
 
 // ---- doc-id SETS (BlockDocIdSet): what getTrues / getFalses return; iterator() builds the automaton ------------------------------
-enum class SetKind { Empty, MatchAll, Scan, Bitmap, Sorted, And, Or, Not };
+enum class SetKind { Empty, MatchAll, Scan, Bitmap, Sorted, And, Or, Not, Expr };
 struct Set {
   SetKind kind = SetKind::Empty;
   const HostBits* leaf_bits = nullptr;                       // Scan: match bitmap; Bitmap: the doc set
@@ -363,6 +425,11 @@ struct Emu {
         auto s = mk(SetKind::Scan);
         bind_leaf(*s, op);
         if (op.col && op.col->is_mv) { s->mv_off = op.col->mv_offsets_host.data(); s->mv_off_dev = op.col->mv_offsets_dev.as<int32_t>(); }
+        return s;
+      }
+      case OpKind::Expr: {   // ExpressionFilterOperator#getTrues: an ExpressionDocIdSet
+        auto s = mk(SetKind::Expr);
+        if (!dev_leaves) s->leaf_bits = &leaves.at(&op);   // (the device evaluation declines trees that hold the leaf)
         return s;
       }
       case OpKind::Inverted: {
@@ -441,6 +508,20 @@ struct Emu {
         o->children = std::move(sets);
         return not_of(std::move(o));
       }
+      case OpKind::Expr: {   // ExpressionFilterOperator#getFalses (:100-110) overrides the default: a second ExpressionDocIdSet, with
+        // PredicateEvaluationResult.FALSE — NOT(leaf) is itself a scan-based ExpressionScanDocIdIterator over the docs the predicate
+        // rejects (no nulls: operand columns that hold nulls are refused), taking applyAnd inside an AND and walking blocks of the complement
+        auto s = mk(SetKind::Expr);
+        if (!dev_leaves) {
+          const HostBits& m = leaves.at(&op);
+          s->owned = std::make_shared<HostBits>();
+          s->owned->resize_for(n_docs);
+          s->owned->add_range(0, (int64_t)n_docs - 1);
+          for (size_t i = 0; i < s->owned->w.size(); i++) s->owned->w[i] &= ~(i < m.w.size() ? m.w[i] : 0);
+          s->leaf_bits = s->owned.get();
+        }
+        return s;
+      }
       default: {            // BaseFilterOperator#getFalses
         SetPtr t = trues(op);
         if (t->kind == SetKind::MatchAll) return mk(SetKind::Empty);
@@ -471,6 +552,9 @@ struct Emu {
       case SetKind::Scan:
         counters.push_back(std::make_unique<Counter>());
         return std::make_unique<ScanIt>(*s.leaf_bits, *counters.back(), s.mv_off);
+      case SetKind::Expr:
+        counters.push_back(std::make_unique<Counter>());
+        return std::make_unique<ExprIt>(*s.leaf_bits, *counters.back());
       case SetKind::Bitmap: return std::make_unique<BitmapIt>(s.owned ? s.owned : clone_bits(*s.leaf_bits));
       case SetKind::Sorted: return std::make_unique<SortedIt>(s.ranges);
       case SetKind::Not: return std::make_unique<NotIt>(iterator(*s.children[0]), n_docs);
@@ -495,7 +579,7 @@ struct Emu {
               else for (size_t i = 0; i < docs->w.size(); i++) docs->w[i] &= i < it->doc_ids()->w.size() ? it->doc_ids()->w[i] : 0;
             }
           for (auto& it : all)
-            if (it->kind == ItKind::Scan && docs->next_set(0) >= 0) static_cast<ScanIt*>(it.get())->apply_and(*docs);   // applyAnd: an empty candidate set is not scanned
+            if (it->kind == ItKind::Scan && docs->next_set(0) >= 0) it->apply_and(*docs);   // applyAnd: an empty candidate set is not scanned
             else if (it->kind == ItKind::Scan) std::fill(docs->w.begin(), docs->w.end(), 0);
           auto merged = std::make_unique<BitmapIt>(docs);
           std::vector<ItPtr> remaining;
@@ -1190,8 +1274,14 @@ int64_t emulate_entries_scanned_in_filter(const FilterOp& root, const StatLeafBi
   return total;
 }
 
+static bool holds_expr_leaf(const FilterOp& op) {
+  if (op.kind == OpKind::Expr) return true;
+  for (auto& c : op.children) if (holds_expr_leaf(*c)) return true;
+  return false;
+}
 bool filter_stats_on_device(const FilterOp& root, int32_t n_docs) {
   if (n_docs <= 0) return false;
+  if (holds_expr_leaf(root)) return false;   // ExpressionScanDocIdIterator's 10 000-doc blocks are not in the tile automaton: the host walk
   static const StatLeafBits no_host_bits;
   StatLeafWords none;
   Emu emu{no_host_bits, n_docs, {}};

@@ -252,7 +252,8 @@ bool filter_stats_on_device(const FilterOp& root, int32_t n_docs);
 int64_t entries_scanned_on_device(const FilterOp& root, const StatLeafWords& leaves, int32_t n_docs, DeviceBuffer& arena, void* hip_stream);
 
 // ---- compiled plan ------------------------------------------------------------------------------------------------------------
-enum class OpKind { Empty, MatchAll, Scan, Inverted, Sorted, And, Or, Not, Bitmap, RangeIdx };
+// Expr: ExpressionFilterOperator — a predicate over an arithmetic expression (pg_expr.h); its doc set is computed when the plan is compiled
+enum class OpKind { Empty, MatchAll, Scan, Inverted, Sorted, And, Or, Not, Bitmap, RangeIdx, Expr };
 
 struct FilterOp {
   OpKind kind = OpKind::Empty;
@@ -261,6 +262,10 @@ struct FilterOp {
   std::shared_ptr<Column> bitmap_col;        // Inverted over a docId bitmap of the segment (null vector, queryableDocIds): keeps it alive
   std::vector<std::unique_ptr<FilterOp>> children;
   std::vector<int32_t> range_lo, range_hi;   // Bitmap (BitmapBasedFilterOperator): ascending disjoint inclusive docId ranges
+  // Expr: the leaf's doc set as match words in HBM (the layout PG_F_PUSH_WORDS reads: one dword per 32 docs, whole wave tiles), computed once
+  // by pg_expr_pred and kept with the plan through its operator tree (CompiledPlan::root_op); its distinct operand columns
+  std::shared_ptr<DeviceBuffer> expr_words;
+  std::vector<Column*> expr_cols;
 };
 using OpPtr = std::unique_ptr<FilterOp>;
 OpPtr make_filter_op(OpKind k);
@@ -351,7 +356,26 @@ struct CompiledPlan {
 
 void hll_registers_of_dictionary(Column& c, int log2m, uint8_t* regs);
 double dictionary_value_as_double(const Column& c, int32_t dict_id);
-std::shared_ptr<CompiledPlan> compile_plan(Segment& seg, const pg_filter_node* filter, const pg_query* query, int32_t flags = 0);   // flags: of a filter-only plan (query == nullptr)
+// Expression leaves of a filter (a pg_filter_node whose column spells an expression): expr_leaf_specs checks and resolves them under seg.mu
+// (every refusal of the leaf comes from here), expr_leaf_run is the pass over all docs that produces a leaf's match words — get_plan runs it
+// WITHOUT the segment's lock, as the bounds pass of expressions inside aggregations does, and hands the words to compile_plan.
+#define PG_MAX_EXPR_LEAVES 4   // per filter: each costs numDocs / 8 bytes of HBM per cached plan
+struct ExprLeafSpec {
+  const pg_filter_node* node = nullptr;
+  PgExprArgs args;     // expression 0: the program; srcs: the operand columns
+  PgExprPred pred;     // kind, bounds (set / out: filled by the pass)
+  std::vector<uint64_t> set_bits;   // IN / NOT_IN: Double.doubleToLongBits of the values
+  std::vector<Column*> cols;
+  std::shared_ptr<DeviceBuffer> words;   // after expr_leaf_run
+};
+bool filter_has_expression(const pg_filter_node* filter);
+Column* expr_operand_column(Segment& seg, const std::string& name, bool null_handling);   // an expression's operand, checked (seg.mu held)
+void expr_fill_src(PgValueSrc& S, const Column& c);
+std::vector<ExprLeafSpec> expr_leaf_specs(Segment& seg, const pg_filter_node* filter, int32_t flags);   // seg.mu held
+void expr_leaf_run(Segment& seg, ExprLeafSpec& leaf);                                                    // seg.mu not needed
+// `expr_leaves`: the filter's expression leaves with their words (a filter that holds one and finds no words is PG_ERR_INTERNAL)
+std::shared_ptr<CompiledPlan> compile_plan(Segment& seg, const pg_filter_node* filter, const pg_query* query, int32_t flags = 0,
+                                           const std::vector<ExprLeafSpec>* expr_leaves = nullptr);   // flags: of a filter-only plan (query == nullptr)
 // SELECT DISTINCT (PG_QUERY_FLAG_DISTINCT): the checked query and its key space (pg_plan.cpp); execute_distinct runs it (pg_exec.hip)
 struct DistinctShape {
   std::vector<Column*> cols;       // per DISTINCT column: the column of fixed-bit ids (its own dictIds, or its virtual dictionary's ids)

@@ -16,7 +16,10 @@
 #include <sstream>
 
 #include "pg_internal.hpp"
+#include "pg_expr.h"
 #include "pg_fixed_point.h"
+
+void pg_expr_launch_pred(const PgExprArgs* args, const PgExprPred* pred, int grid, hipStream_t stream);   // pg_kernels_exprpred.hip
 
 extern "C" const int pg_specd_waves_per_block;   // pg_kernels_specd.hip
 extern "C" int pg_specw_stage_bytes(int scan_bits, int value_bits, int bits0, int bits1, int n_bitmaps);   // pg_kernels_specw.hip
@@ -318,6 +321,7 @@ static int priority(const FilterOp& op) {   // PrioritizedFilterOperator.java:31
     case OpKind::Or: return 400;
     case OpKind::Not: return priority(*op.children[0]);
     case OpKind::Scan: return op.col && op.col->is_mv ? 550 : 500;   // getScanBasedFilterPriority (FilterOperatorUtils.java:253-265): multi-value scans last
+    case OpKind::Expr: return 1000;    // ExpressionFilterOperator: PrioritizedFilterOperator.EXPRESSION_PRIORITY — after every scan
     default: return 10000;
   }
 }
@@ -394,19 +398,162 @@ static std::shared_ptr<Column> null_vector_of(Segment& seg, const Column* col) {
   return !nv.posting_card.empty() && nv.posting_card[0] > 0 ? it->second : nullptr;
 }
 
-static OpPtr construct(Segment& seg, const pg_filter_node& f, bool nh) {   // FilterPlanNode#constructPhysicalOperator
+// =====================================================================================================================
+// expression leaves (ExpressionFilterOperator)
+// =====================================================================================================================
+bool filter_has_expression(const pg_filter_node* f) {
+  if (!f) return false;
+  if (f->type == PG_FILTER_PREDICATE) return expr_is_expression(f->column);
+  for (int i = 0; i < f->n_children && f->children; i++) if (filter_has_expression(&f->children[i])) return true;
+  return false;
+}
+static std::string short_text(const std::string& t) { return t.size() > 200 ? t.substr(0, 197) + "..." : t; }
+static uint64_t double_to_long_bits(double v) {   // Double.doubleToLongBits
+  if (v != v) return 0x7FF8000000000000ULL;
+  uint64_t b;
+  memcpy(&b, &v, 8);
+  return b;
+}
+// An operand column of an expression, checked: the rules and the refusal texts that expressions inside aggregations (pg_exec_expr.hip) and
+// in filters share.  seg.mu held.
+Column* expr_operand_column(Segment& seg, const std::string& name, bool null_handling) {
+  Column* c = seg.find(name.c_str());
+  if (!c) fail(PG_ERR_NOT_FOUND, "column not found: %s", short_text(name).c_str());
+  if (c->is_mv || c->raw_mv) fail(PG_ERR_UNSUPPORTED, "expression over the multi-value column %s", c->name.c_str());
+  if (c->data_type > PG_TYPE_DOUBLE) fail(PG_ERR_UNSUPPORTED, "expression over the %s column %s", c->data_type == PG_TYPE_STRING ? "STRING" : "BYTES", c->name.c_str());
+  if (null_handling && column_has_nulls(seg, c->name)) fail(PG_ERR_UNSUPPORTED, "enableNullHandling: expression over %s, which holds nulls", c->name.c_str());
+  const bool dict_ok = c->has_dictionary && c->col_kind == PG_COL_FIXED_BIT && c->bits >= 1 && c->bits <= 31 && c->cardinality >= 1 && c->dict_dev.ptr;
+  const bool raw_ok = !c->has_dictionary && (c->col_kind == PG_COL_RAW32 || c->col_kind == PG_COL_RAW64);
+  if (!dict_ok && !raw_ok) fail(PG_ERR_UNSUPPORTED, "expression: operand column %s (layout %d, %d bits)", c->name.c_str(), c->col_kind, c->bits);
+  return c;
+}
+void expr_fill_src(PgValueSrc& S, const Column& c) {
+  S.data = c.fwd_dev.as<uint8_t>();
+  S.dict = c.has_dictionary ? c.dict_dev.ptr : nullptr;
+  S.col_kind = c.col_kind;
+  S.bits = c.bits;
+  S.val_type = c.val_type;
+  S.fx_q = 0;
+}
+// One expression predicate, checked and resolved: the program, the operand columns, the raw DOUBLE predicate (the four transform functions'
+// getResultMetadata says DOUBLE, so the reference builds the raw DOUBLE evaluators of the predicate's type).  seg.mu held.
+static ExprLeafSpec expr_leaf_spec(Segment& seg, const pg_filter_node& f, bool nh) {
+  ExprLeafSpec L;
+  L.node = &f;
+  const std::string text = f.column;
+  if (f.predicate_type == PG_PRED_IS_NULL || f.predicate_type == PG_PRED_IS_NOT_NULL)
+    fail(PG_ERR_UNSUPPORTED, "IS [NOT] NULL over the expression %s: the Java plan answers such a query", short_text(text).c_str());
+  ExprProgram prog;
+  std::string error;
+  const int32_t st = expr_parse(f.column, prog, error);
+  if (st != PG_OK) fail(st, "%s (in %s)", error.c_str(), short_text(text).c_str());
+  memset(&L.args, 0, sizeof(L.args));
+  memset(&L.pred, 0, sizeof(L.pred));
+  for (const std::string& name : prog.columns) {
+    Column* c = expr_operand_column(seg, name, nh);
+    expr_fill_src(L.args.srcs[L.cols.size()], *c);   // (expr_parse admits at most PG_EXPR_MAX_SRCS columns)
+    L.cols.push_back(c);
+  }
+  L.args.scan.n_docs = seg.total_docs;
+  L.args.scan.n_words = ((int64_t)seg.total_docs + 63) / 64;
+  L.args.n_srcs = (int32_t)L.cols.size();
+  L.args.n_exprs = 1;
+  L.args.count_slot = -1;
+  L.args.exprs[0].first_step = 0;
+  L.args.exprs[0].n_steps = prog.n_steps;
+  for (int k = 0; k < prog.n_steps; k++) L.args.steps[k] = prog.steps[k];
+  // the predicate, as the raw evaluators over a DOUBLE "column" named by the expression build it: bounds moved by nextafter, "Invalid range"
+  Column as_double;
+  as_double.name = short_text(text);
+  as_double.data_type = PG_TYPE_DOUBLE;
+  as_double.has_dictionary = false;
+  const PredEval e = make_pred_eval(f, as_double);
+  switch (f.predicate_type) {
+    case PG_PRED_RANGE: L.pred.kind = PG_XP_RANGE; L.pred.lo = e.lo_d; L.pred.hi = e.hi_d; break;
+    case PG_PRED_EQ: L.pred.kind = PG_XP_EQ; L.pred.lo = e.set_d[0]; break;
+    case PG_PRED_NOT_EQ: L.pred.kind = PG_XP_NOT_EQ; L.pred.lo = e.set_d[0]; break;
+    case PG_PRED_IN:
+    case PG_PRED_NOT_IN:
+      L.pred.kind = f.predicate_type == PG_PRED_IN ? PG_XP_IN : PG_XP_NOT_IN;
+      for (double v : e.set_d) L.set_bits.push_back(double_to_long_bits(v));
+      L.pred.n_set = (int32_t)L.set_bits.size();
+      break;
+    default: fail(PG_ERR_UNSUPPORTED, "predicate type %d over the expression %s", f.predicate_type, short_text(text).c_str());
+  }
+  return L;
+}
+static void collect_expr_leaves(Segment& seg, const pg_filter_node& f, bool nh, std::vector<ExprLeafSpec>& out) {
+  if (f.type == PG_FILTER_PREDICATE) {
+    if (!expr_is_expression(f.column)) return;
+    if (out.size() >= PG_MAX_EXPR_LEAVES)
+      fail(PG_ERR_UNSUPPORTED, "more than %d predicates over expressions in one filter (each keeps numDocs / 8 bytes of match words with the plan)", PG_MAX_EXPR_LEAVES);
+    out.push_back(expr_leaf_spec(seg, f, nh));
+    return;
+  }
+  for (int i = 0; i < f.n_children && f.children; i++) collect_expr_leaves(seg, f.children[i], nh, out);
+}
+std::vector<ExprLeafSpec> expr_leaf_specs(Segment& seg, const pg_filter_node* filter, int32_t flags) {
+  std::vector<ExprLeafSpec> out;
+  if (filter) collect_expr_leaves(seg, *filter, (flags & PG_QUERY_FLAG_NULL_HANDLING) != 0, out);
+  return out;
+}
+// The leaf's doc set: one pass of pg_expr_pred over ALL docs.  It only reads registered columns, which never change or go away while the
+// segment lives, so it needs no lock; the words are whole wave tiles (plan_wtiles * 64 + 64 dwords, as Emitter::emit_ranges builds them),
+// zero beyond the last doc.
+void expr_leaf_run(Segment& seg, ExprLeafSpec& L) {
+  use_device(seg.device);
+  const int64_t wtiles = ((int64_t)seg.total_docs + PG_WAVE_DOCS - 1) / PG_WAVE_DOCS;
+  const size_t bytes = (size_t)(wtiles * 64 + 64) * 4;
+  auto words = std::make_shared<DeviceBuffer>(bytes);
+  hipStream_t stream = thread_stream(seg.device);
+  PG_HIP(hipMemsetAsync(words->ptr, 0, words->size, stream));
+  DeviceBuffer set;
+  if (seg.total_docs > 0) {
+    if (!L.set_bits.empty()) {
+      set.alloc(L.set_bits.size() * 8);
+      PG_HIP(hipMemcpyAsync(set.ptr, L.set_bits.data(), L.set_bits.size() * 8, hipMemcpyHostToDevice, stream));
+    }
+    PgExprPred P = L.pred;
+    P.set = set.as<uint64_t>();
+    P.out = words->as<uint64_t>();
+    P.n_words = L.args.scan.n_words;   // <= wtiles * 32: inside the buffer
+    const int64_t per_wg = 4 * PG_EXPR_PRED_WORDS;   // 64-doc words per workgroup and iteration (4 wavefronts of 256 threads)
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)device_cus(seg.device) * 8, (P.n_words + per_wg - 1) / per_wg));
+    pg_expr_launch_pred(&L.args, &P, grid, stream);
+    PG_HIP(hipGetLastError());
+  }
+  PG_HIP(hipStreamSynchronize(stream));   // `set` goes out of scope; the plan's executions may run on other threads' streams
+  L.words = std::move(words);
+}
+// `leaves`: the filter's expression leaves with the words get_plan prepared (no pass runs here: compilation holds the segment's lock)
+static OpPtr expr_operator(const pg_filter_node& f, const std::vector<ExprLeafSpec>* leaves) {
+  if (leaves)
+    for (const ExprLeafSpec& L : *leaves)
+      if (L.node == &f && L.words) {
+        auto op = make_op(OpKind::Expr);
+        op->expr_words = L.words;
+        op->expr_cols = L.cols;
+        return op;
+      }
+  fail(PG_ERR_INTERNAL, "the match words of the expression predicate over %s were not prepared before the plan was compiled", short_text(f.column).c_str());
+}
+
+static OpPtr construct(Segment& seg, const pg_filter_node& f, bool nh, const std::vector<ExprLeafSpec>* leaves) {   // FilterPlanNode#constructPhysicalOperator
   switch (f.type) {
     case PG_FILTER_AND:
     case PG_FILTER_OR: {
       if (f.n_children < 1 || !f.children) fail(PG_ERR_INVALID_ARGUMENT, "AND/OR without children");
       std::vector<OpPtr> ch;
-      for (int i = 0; i < f.n_children; i++) ch.push_back(construct(seg, f.children[i], nh));
+      for (int i = 0; i < f.n_children; i++) ch.push_back(construct(seg, f.children[i], nh, leaves));
       return f.type == PG_FILTER_AND ? and_operator(std::move(ch)) : or_operator(std::move(ch));
     }
     case PG_FILTER_NOT:
       if (f.n_children != 1 || !f.children) fail(PG_ERR_INVALID_ARGUMENT, "NOT needs exactly one child");
-      return not_operator(construct(seg, f.children[0], nh));
+      return not_operator(construct(seg, f.children[0], nh, leaves));
     case PG_FILTER_PREDICATE: {
+      // an expression on the left-hand side: ExpressionFilterOperator (FilterPlanNode.java:266-272).  No always-true / always-false folding:
+      // its evaluator has no dictionary to tell; under null handling it has no nulls of its own (operand columns with nulls are refused)
+      if (expr_is_expression(f.column)) return expr_operator(f, leaves);
       Column* col = seg.find(f.column);
       if (!col) fail(PG_ERR_NOT_FOUND, "column not found: %s", f.column ? f.column : "(null)");
       if (f.predicate_type == PG_PRED_IS_NULL || f.predicate_type == PG_PRED_IS_NOT_NULL) {   // FilterPlanNode.java:298-312
@@ -567,6 +714,29 @@ struct Emitter {
     L.hi = keep(hi);
     ranges.push_back(L);
     instrs.push_back({L.words ? PG_F_PUSH_WORDS : PG_F_PUSH_RANGES, (int32_t)ranges.size() - 1});
+    push();
+  }
+
+  // ExpressionFilterOperator: the doc set pg_expr_pred left with the operator, read as match words.  Bytes: the words, and the operand
+  // columns once (what the pass at compilation read).  Its statistic depends on how the reference's iterators drive each other (blocks of
+  // 10 000 docs: ExpressionScanDocIdIterator): the host walk of pg_filter_stats.cpp counts it; full_scan_entries carries the lone leaf's
+  // numDocs as the stand-in where the walk is not taken.
+  // (has_scan, index_child and yields_bitmap below — the bookkeeping of which shapes the kernels' own counters count exactly — are
+  // deliberately not taught that this leaf is scan-based: a plan holding it is never stats_exact, so they are not asked about it.)
+  void emit_expr(const FilterOp& op) {
+    PgRangeLeaf L{};
+    L.words = op.expr_words->as<uint32_t>();
+    L.lo = L.hi = nullptr;
+    ranges.push_back(L);
+    alg_bytes += ((int64_t)seg.total_docs + 7) / 8;
+    for (Column* c : op.expr_cols)
+      if (std::find(scanned_cols.begin(), scanned_cols.end(), c) == scanned_cols.end()) {
+        scanned_cols.push_back(c);
+        alg_bytes += (int64_t)c->fwd_bytes_logical;
+      }
+    plan.full_scan_entries += seg.total_docs;
+    plan.stats_exact = false;
+    instrs.push_back({PG_F_PUSH_WORDS, (int32_t)ranges.size() - 1});
     push();
   }
 
@@ -778,6 +948,7 @@ struct Emitter {
       case OpKind::Inverted: emit_inverted(op); break;
       case OpKind::RangeIdx: emit_rangeidx(op); break;
       case OpKind::Scan: emit_scan(op, false); break;
+      case OpKind::Expr: emit_expr(op); break;
       case OpKind::Not:
         emit(*op.children[0], false);
         instrs.push_back({PG_F_NOT, 0});
@@ -1063,6 +1234,7 @@ static double estimate_selectivity(const FilterOp& op, double n_docs) {
     case OpKind::Scan:
       if (op.eval.dictionary_based && op.col->cardinality > 0) return (double)op.eval.matching.size() / op.col->cardinality;   // uniform dictIds
       return 0.2;   // a raw-value predicate without column statistics: assume it is selective (the dense HBM table is the safe side)
+    case OpKind::Expr: return 0.2;   // unknown at plan time, as a raw-value scan
     case OpKind::And: { double s = 1; for (auto& c : op.children) s *= estimate_selectivity(*c, n_docs); return s; }
     case OpKind::Or: { double s = 1; for (auto& c : op.children) s *= 1 - estimate_selectivity(*c, n_docs); return 1 - s; }
     case OpKind::Not: return 1 - estimate_selectivity(*op.children[0], n_docs);
@@ -1074,6 +1246,7 @@ static double estimate_selectivity(const FilterOp& op, double n_docs) {
 static bool can_optimize_count(const FilterOp& op) {
   switch (op.kind) {
     case OpKind::Scan: return false;
+    case OpKind::Expr: return false;   // ExpressionFilterOperator keeps BaseFilterOperator's canOptimizeCount: never FastFilteredCountOperator's
     case OpKind::And: case OpKind::Or: case OpKind::Not:
       for (auto& c : op.children) if (!can_optimize_count(*c)) return false;
       return true;
@@ -1087,9 +1260,9 @@ static std::shared_ptr<CompiledPlan> compile_in_space(Segment& seg, OpPtr root, 
 // regular filter is planned first; FastFilteredCountOperator takes a lone COUNT(*) over an index-only filter; otherwise, when the
 // filter result is not empty, the first star-tree the query fits answers it (AggregationFunctionUtils#buildAggregationInfo
 // :285-307) and the operators run over that star-tree's doc space.
-std::shared_ptr<CompiledPlan> compile_plan(Segment& seg, const pg_filter_node* filter, const pg_query* q, int32_t flags) {
+std::shared_ptr<CompiledPlan> compile_plan(Segment& seg, const pg_filter_node* filter, const pg_query* q, int32_t flags, const std::vector<ExprLeafSpec>* expr_leaves) {
   const bool nh = ((q ? q->flags : flags) & PG_QUERY_FLAG_NULL_HANDLING) != 0;
-  OpPtr root = filter ? construct(seg, *filter, nh) : make_op(OpKind::MatchAll);
+  OpPtr root = filter ? construct(seg, *filter, nh, expr_leaves) : make_op(OpKind::MatchAll);
   if (seg.queryable_doc_ids) {   // FilterPlanNode.run (:88-106): AND(filter, BitmapBasedFilterOperator(queryableDocIds))
     std::vector<OpPtr> both;
     both.push_back(std::move(root));

@@ -312,6 +312,7 @@ struct PredMap {
 
 // StarTreeUtils#getPredicateEvaluator: false when the predicate cannot be solved with the star-tree (no dictionary)
 static bool star_pred_eval(Segment& seg, const pg_filter_node& p, PredEval* out) {
+  if (filter_has_expression(&p)) return false;   // StarTreeUtils takes identifier predicates only (:112-115): an expression leaf is never fit
   Column* col = seg.find(p.column);
   if (!col) fail(PG_ERR_NOT_FOUND, "column not found: %s", p.column ? p.column : "(null)");
   if (!col->has_dictionary) return false;

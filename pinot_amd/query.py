@@ -285,16 +285,34 @@ class _Parser:
             return FilterContext.not_(self.not_expr())
         return self.primary()
 
+    _OPPOSITE = {"=": "=", "!=": "!=", "<>": "<>", "<": ">", "<=": ">=", ">": "<", ">=": "<="}
+
     def primary(self) -> FilterContext:
         if self.peek() == ("op", "("):
-            self.i += 1
-            e = self.or_expr()
-            self.expect_op(")")
-            return e
-        t = self.take()
-        if t[0] != "id":
-            raise SqlError(f"expected column, got {t}")
-        col = t[1]
+            # a leading '(' opens either a predicate group or an arithmetic expression: try the group, fall back to the expression
+            mark, toks = self.i, list(self.toks)
+            try:
+                self.i += 1
+                e = self.or_expr()
+                self.expect_op(")")
+                t = self.peek()
+                if (t[0] == "op" and t[1] != ")") or (t[0] == "num" and t[1].startswith("-")) or any(self.kw(w) for w in ("BETWEEN", "IN", "IS")) \
+                        or (self.kw("NOT") and (self.kw("IN", 1) or self.kw("BETWEEN", 1))):
+                    raise SqlError("a parenthesised expression, not a predicate group")
+                return e
+            except SqlError:
+                self.i, self.toks = mark, toks
+        # the left-hand side: a column, or an arithmetic expression in its canonical text (the function forms and infix + - * /)
+        col = self.expression()
+        if col.startswith("'"):
+            # PredicateComparisonRewriter.java:108-115: '10 < a' becomes 'a > 10'
+            op = self.take()
+            if op[0] != "op" or op[1] not in self._OPPOSITE:
+                raise SqlError(f"expected comparison after the literal {col}, got {op}")
+            lit, col = col[1:-1], self.expression()
+            if col.startswith("'"):
+                raise SqlError("a comparison of two literals")
+            return self._comparison(col, self._OPPOSITE[op[1]], lit)
         if self.kw("BETWEEN"):
             self.i += 1
             lo = self.literal()
@@ -332,8 +350,14 @@ class _Parser:
         op = self.take()
         if op[0] != "op":
             raise SqlError(f"expected comparison, got {op}")
-        v = self.literal()
-        o = op[1]
+        if self.peek()[0] in ("num", "str"):
+            return self._comparison(col, op[1], self.literal())
+        # PredicateComparisonRewriter.java:117-124: a right-hand side that is no literal — 'a > b' becomes 'minus(a,b) > 0'
+        rhs = self.expression()
+        return self._comparison(f"minus({col},{rhs})", op[1], "0")
+
+    @staticmethod
+    def _comparison(col: str, o: str, v: str) -> FilterContext:
         if o == "=":
             return FilterContext.pred(Predicate("EQ", col, [v]))
         if o in ("!=", "<>"):
