@@ -241,7 +241,15 @@ typedef struct pg_query {
   const pg_filter_node* filter;          /* NULL => MatchAllFilterOperator */
   int32_t n_group_by;                    /* 0 => AggregationOperator (no GROUP BY) */
   int32_t n_aggregations;                /* 0 => filter only (used by pg_filter_exec) */
-  const char* const* group_by_columns;
+  const char* const* group_by_columns;   /* column names; group_by_columns[j] may also hold an ARITHMETIC EXPRESSION's text under exactly the rules
+                                            of pg_agg_spec.column (add / sub / mult / div and their aliases over single-value numeric columns
+                                            and literals, a name containing '(' is an expression, <= 15 operations, <= 8 columns), e.g.
+                                            "sub(column1,'100000')": the key is the expression's DOUBLE value, grouped as a raw DOUBLE column's
+                                            values are (-0.0 and 0.0 two groups, every NaN one, +-Inf ordinary keys), handed back through
+                                            pg_result_group_values_double and named by the text in pg_result_data_table_v4.  At most 4 such
+                                            keys per query; refused (PG_ERR_UNSUPPORTED: the Java plan answers): any other function, STRING /
+                                            BYTES / multi-value operands, an operand with nulls under PG_QUERY_FLAG_NULL_HANDLING, a multi-value
+                                            group-by column next to such a key, and PG_QUERY_FLAG_SELECTION.  PG_QUERY_FLAG_DISTINCT takes them. */
   const pg_agg_spec* aggregations;
   /* InstancePlanMakerImplV2.java:75-96 defaults are applied for values <= 0 */
   int32_t num_groups_limit;                     /* DEFAULT_NUM_GROUPS_LIMIT = 100 000 */
@@ -286,7 +294,7 @@ typedef struct pg_query {
                                               (PG_ERR_UNSUPPORTED: the Java plan answers): nulls in a multi-value column, more than 3 nullable
                                               group-by columns, more groups than numGroupsLimit across their null partitions, PG_QUERY_FLAG_KEEP_DEVICE_TABLE next to nulls */
 /* SELECT DISTINCT (DistinctOperator, pinot-core/.../operator/query/DistinctOperator.java).  group_by_columns / n_group_by are the DISTINCT
-   expressions (plain columns), n_aggregations must be 0, order_by entries are PG_ORDER_BY_GROUP_KEY and `limit` is always read (INT32_MAX:
+   expressions (plain columns or arithmetic expressions, see group_by_columns), n_aggregations must be 0, order_by entries are PG_ORDER_BY_GROUP_KEY and `limit` is always read (INT32_MAX:
    unbounded); num_groups_limit and min_segment_group_trim_size are ignored.  The tuples come back through pg_result_num_groups /
    _group_dict_ids / _group_key_type / _group_values_* / _group_values_bytes* like group keys, one row per tuple: sorted under ORDER BY (the
    remaining columns ascending after the ORDER BY ones); without ORDER BY and a bounded limit in the order of their first matching docId —

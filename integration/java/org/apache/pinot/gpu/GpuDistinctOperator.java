@@ -96,7 +96,7 @@ public class GpuDistinctOperator extends BaseOperator<BaseResultsBlock> {
     DataSchema dataSchema = new DataSchema(names, types);
     Object[][] values = new Object[numColumns][];
     for (int j = 0; j < numColumns; j++) {
-      values[j] = columnValues(result, j, columns.get(j).getIdentifier(), numRows);
+      values[j] = columnValues(result, j, columns.get(j), numRows);
     }
     int limit = _queryContext.getLimit();
     boolean nullHandling = _queryContext.isNullHandlingEnabled();
@@ -160,10 +160,13 @@ public class GpuDistinctOperator extends BaseOperator<BaseResultsBlock> {
     }
   }
 
-  /** One column of the tuples: dictIds through the segment's Dictionary (getInternal: the stored type), values of raw columns. */
-  private Object[] columnValues(long result, int j, String column, int numRows) {
+  /**
+   * One column of the tuples: dictIds through the segment's Dictionary (getInternal: the stored type), values of raw columns and of
+   * arithmetic expressions (DOUBLE values).
+   */
+  private Object[] columnValues(long result, int j, ExpressionContext column, int numRows) {
     Object[] out = new Object[numRows];
-    String storedType = _segment.getDataSource(column).getDataSourceMetadata().getDataType().getStoredType().name();
+    String storedType = GpuResultObjects.keyStoredType(_segment, column);
     int keyType = PinotGpu.resultGroupKeyType(result, j);
     if (keyType == PinotGpu.GROUP_KEY_LONG_VALUES) {
       long[] values = new long[numRows];
@@ -189,7 +192,7 @@ public class GpuDistinctOperator extends BaseOperator<BaseResultsBlock> {
     } else {
       int[] dictIds = new int[numRows];
       PinotGpu.resultGroupDictIds(result, j, dictIds);
-      Dictionary dictionary = _segment.getDataSource(column).getDictionary();
+      Dictionary dictionary = _segment.getDataSource(column.getIdentifier()).getDictionary();
       for (int i = 0; i < numRows; i++) {
         out[i] = dictionary.getInternal(dictIds[i]);
       }

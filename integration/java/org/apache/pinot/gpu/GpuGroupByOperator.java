@@ -167,7 +167,8 @@ public class GpuGroupByOperator extends BaseOperator<BaseResultsBlock> {
       // NoDictionaryMultiColumnGroupKeyGenerator.java:60-130): LONG values for INT / LONG, DOUBLE values for FLOAT / DOUBLE
       Object[][] keys = new Object[numGroups][groupBy.size()];
       for (int j = 0; j < groupBy.size(); j++) {
-        String column = groupBy.get(j).getIdentifier();
+        // (an arithmetic expression has no column: its keys always come back as DOUBLE values, named by the expression's text in the schema)
+        String column = groupBy.get(j).getType() == ExpressionContext.Type.IDENTIFIER ? groupBy.get(j).getIdentifier() : null;
         if (PinotGpu.resultGroupKeyType(result, j) == PinotGpu.GROUP_KEY_LONG_VALUES) {
           long[] values = new long[numGroups];
           PinotGpu.resultGroupValuesLong(result, j, values);
@@ -178,7 +179,7 @@ public class GpuGroupByOperator extends BaseOperator<BaseResultsBlock> {
         } else if (PinotGpu.resultGroupKeyType(result, j) == PinotGpu.GROUP_KEY_DOUBLE_VALUES) {
           double[] values = new double[numGroups];
           PinotGpu.resultGroupValuesDouble(result, j, values);
-          boolean isFloat = _segment.getDataSource(column).getDataSourceMetadata().getDataType().getStoredType().name().equals("FLOAT");
+          boolean isFloat = GpuResultObjects.keyStoredType(_segment, groupBy.get(j)).equals("FLOAT");
           for (int g = 0; g < numGroups; g++) {
             keys[g][j] = isFloat ? (Object) (float) values[g] : (Object) values[g];
           }

@@ -84,10 +84,11 @@ public final class NativeQuery implements AutoCloseable {
     b.putInt(q.getLimit()).putInt(orderBy == null ? -1 : q.getMinSegmentGroupTrimSize());
     if (groupBy != null) {
       for (ExpressionContext e : groupBy) {
-        if (e.getType() != ExpressionContext.Type.IDENTIFIER) {
+        String key = keyText(e);
+        if (key == null) {
           return null;
         }
-        putString(b, e.getIdentifier());
+        putString(b, key);
       }
     }
     for (AggregationFunction f : aggs) {
@@ -126,7 +127,8 @@ public final class NativeQuery implements AutoCloseable {
 
   /**
    * SELECT DISTINCT (PG_QUERY_FLAG_DISTINCT): the DISTINCT expressions in the group-by slots, no aggregation, every ORDER BY expression a
-   * group-key entry, LIMIT always read (Integer.MAX_VALUE: every tuple).  null when an expression is not a plain column (the Java plan answers).
+   * group-key entry, LIMIT always read (Integer.MAX_VALUE: every tuple).  null when an expression is neither a plain column nor an arithmetic
+   * expression over columns and literals (the Java plan answers).
    */
   public static NativeQuery fromDistinct(QueryContext q) {
     List<ExpressionContext> columns = q.getSelectExpressions();
@@ -138,10 +140,11 @@ public final class NativeQuery implements AutoCloseable {
         .putInt(q.getFilter() == null ? 0 : 1).putInt(numOrderBy);
     b.putInt(q.getLimit()).putInt(-1);
     for (ExpressionContext e : columns) {
-      if (e.getType() != ExpressionContext.Type.IDENTIFIER) {
+      String key = keyText(e);
+      if (key == null) {
         return null;
       }
-      putString(b, e.getIdentifier());
+      putString(b, key);
     }
     for (int i = 0; i < numOrderBy; i++) {
       OrderByExpressionContext o = orderBy.get(i);
@@ -381,6 +384,14 @@ public final class NativeQuery implements AutoCloseable {
     while ((b.position() & 3) != 0) {
       b.put((byte) 0);
     }
+  }
+
+  /**
+   * A GROUP BY / DISTINCT key as pg_query.group_by_columns carries it: a column's name, or an arithmetic expression as the text
+   * ExpressionContext#toString prints (the library groups its DOUBLE values through a derived key column); null for anything else.
+   */
+  private static String keyText(ExpressionContext e) {
+    return e.getType() == ExpressionContext.Type.IDENTIFIER ? e.getIdentifier() : isArithmetic(e) ? e.toString() : null;
   }
 
   private static boolean takesExpression(int fn) {

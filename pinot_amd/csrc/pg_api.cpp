@@ -257,6 +257,7 @@ int32_t pg_query_supported(pg_segment_t segment, const pg_query* query) {
   return guarded([&] {
     REQUIRE(segment && query, "null argument");
     use_device(segment->seg.device);
+    const ExprKeyScope expr_keys(segment->seg, *query);   // as execute_query opens it: the same refusals, and the execution finds the columns
     // compiled under the segment's lock and cached: the pg_query_exec that follows finds the plan (PlanMaker calls supported()
     // then exec() from many worker threads); throws PG_ERR_UNSUPPORTED for shapes off the GPU path
     if (query->flags & PG_QUERY_FLAG_SELECTION) {   // the checks of the selection path; its filter plan is compiled and cached

@@ -13,6 +13,7 @@
 #include <cmath>
 
 #include "pg_internal.hpp"
+#include "pg_expr.h"
 
 #define PG_DECL_FAST(NAME) extern "C" __global__ void NAME(const PgQueryPlan p);
 #define PG_DECL_GENERIC PG_DECL_FAST(pg_generic_query_f) PG_DECL_FAST(pg_generic_query_l) PG_DECL_FAST(pg_generic_query_g)
@@ -1191,7 +1192,11 @@ void fill_result_schema(Segment& seg, const pg_query& q, Result& r) {
       }
     };
     res->schema_keys.resize((size_t)q.n_group_by);
-    for (int j = 0; j < q.n_group_by; j++) column_of(q.group_by_columns[j], res->schema_keys[(size_t)j]);
+    for (int j = 0; j < q.n_group_by; j++) {
+      column_of(q.group_by_columns[j], res->schema_keys[(size_t)j]);
+      // an expression key: named by its text as given, typed by the transform's result (DOUBLE)
+      if (expr_is_expression(q.group_by_columns[j])) res->schema_keys[(size_t)j].data_type = PG_TYPE_DOUBLE;
+    }
     res->schema_aggs.resize((size_t)q.n_aggregations);
     for (int a = 0; a < q.n_aggregations; a++) {
       const char* col = q.aggregations[a].column;
@@ -1585,7 +1590,7 @@ std::unique_ptr<Result> execute_distinct(Segment& seg, const pg_query& q, const 
     st.device_ms_aggregate = ms;
     st.device_ms_total = ds->stats.device_ms_filter + ms;
     st.num_docs_scanned = docs_scanned;
-    st.num_entries_scanned_post_filter = docs_scanned * n_cols;
+    st.num_entries_scanned_post_filter = docs_scanned * (S.n_read >= 0 ? S.n_read : n_cols);   // (expression keys count their operands)
     // numEntriesScannedInFilter: the whole filter's count unless the operator stopped early; then exact for filters that scan nothing and for
     // one scan predicate (its iterator read whole 256-doc batches up to the last doc consumed), approximate (stats_exact = 0) otherwise
     st.num_entries_scanned_in_filter = ds->stats.num_entries_scanned_in_filter;

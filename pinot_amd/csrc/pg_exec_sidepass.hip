@@ -94,11 +94,13 @@ SideGroups side_groups(Segment& seg, const pg_query& q, const char* subject, con
   SideGroups S;
   for (int j = 0; j < q.n_group_by; j++) {
     const char* name = q.group_by_columns[j];
-    Column* c = name ? seg.find(name) : nullptr;
+    std::shared_ptr<Column> derived;
+    Column* c = group_key_column(seg, name, &derived);   // an expression key: its derived DOUBLE column, grouped through its virtual dictionary
     if (!c) fail(PG_ERR_NOT_FOUND, "column not found: %s", name ? name : "(null)");
+    if (derived) S.keep.push_back(derived);
     if (c->is_mv || c->raw_mv) fail(PG_ERR_UNSUPPORTED, "%s next to the multi-value group-by column %s", subject, c->name.c_str());
     if (null_handling && column_has_nulls(seg, c->name)) fail(PG_ERR_UNSUPPORTED, "enableNullHandling: %s grouped by %s, which holds nulls", subject, c->name.c_str());
-    read.insert(name);
+    for (Column* r : key_columns_read(c)) read.insert(r->name);   // (an expression key counts its operands)
     Column* id = id_column(seg, *c, "group-by", who);
     S.group_cols.push_back(c);
     S.group_ids.push_back(id);

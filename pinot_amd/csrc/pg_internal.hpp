@@ -144,6 +144,10 @@ struct Column {
   int32_t max_entries_per_doc = 0;              // ColumnMetadata#getMaxNumberOfMultiValues
   DeviceBuffer mv_offsets_dev;
   std::vector<int32_t> mv_offsets_host;         // the same offsets for the host-side statistics automaton (pg_filter_stats.cpp)
+  // a DERIVED key column (pg_exprkey.cpp): GROUP BY / DISTINCT over an arithmetic expression.  DOUBLE, no dictionary, no forward index of its
+  // own (fwd_dev stays empty: nothing may read it) — only `vdict`, built from pg_expr_keys' output; `name` is the expression's text.  Non-empty
+  // exactly on such a column: the distinct operand columns, which statistics count in its place.
+  std::vector<Column*> expr_operands;
 };
 
 struct CompiledPlan;
@@ -170,6 +174,16 @@ struct Segment {
     bool has_nonfinite = false;  // a NaN / Inf occurs (division by zero, overflow): such a query stays with the Java plan
   };
   std::map<std::string, ExprBounds> expr_bounds;
+  // per expression text of a GROUP BY / DISTINCT key (pg_exprkey.cpp): its derived column.  Shared-owned — plans hold Column*, so a plan
+  // compiled against a column that was evicted since keeps it alive (CompiledPlan::pinned).  At most PG_MAX_DERIVED_KEYS per segment, the
+  // one used longest ago goes first; read and filled under `mu`, the full-segment passes that build a column run outside it.
+  struct DerivedKey {
+    std::shared_ptr<Column> col;
+    uint64_t last_used = 0;
+    uint64_t bytes = 0;          // its share of device_bytes
+  };
+  std::map<std::string, DerivedKey> derived_keys;
+  uint64_t derived_clock = 0;
   Column* find(const char* name);
   Segment();
   ~Segment();
@@ -195,6 +209,9 @@ struct StarTree {
 
 void segment_add_column(Segment& seg, const pg_column_desc& d);
 void ensure_virtual_dictionary(Segment& seg, Column& c);            // pg_vdict.hip
+// ... and the virtual dictionary of a key column that is an expression (pg_vdict.hip): pg_expr_keys over all docs, then the steps a stored
+// raw DOUBLE column takes.  seg.mu is NOT needed (it reads registered columns only); `id_bytes`: the HBM the bit-packed ids keep.
+std::unique_ptr<Column> expression_virtual_dictionary(Segment& seg, const std::string& text, const PgExprArgs& args, uint64_t* id_bytes);
 int64_t vdict_value_of_key(uint64_t key, int kind, double* as_double);   // the value behind an order-preserving key (FLOAT / DOUBLE: IEEE double bits)
 double limbs_to_double(const int64_t* limbs, int n_limbs, int q);   // sum_j limbs[j] * 2^(32 j + q), correctly rounded (pg_plan.cpp)
 void segment_add_star_tree(Segment& seg, const pg_star_tree_desc& d);
@@ -376,6 +393,26 @@ void expr_leaf_run(Segment& seg, ExprLeafSpec& leaf);                           
 // `expr_leaves`: the filter's expression leaves with their words (a filter that holds one and finds no words is PG_ERR_INTERNAL)
 std::shared_ptr<CompiledPlan> compile_plan(Segment& seg, const pg_filter_node* filter, const pg_query* query, int32_t flags = 0,
                                            const std::vector<ExprLeafSpec>* expr_leaves = nullptr);   // flags: of a filter-only plan (query == nullptr)
+// ---- arithmetic expressions as GROUP BY / DISTINCT keys (pg_exprkey.cpp) -------------------------------------------------------
+#define PG_MAX_DERIVED_KEYS 16   // derived key columns kept per segment
+#define PG_MAX_EXPR_KEYS 4       // expression keys of one query
+// Every entry point that plans a query opens one over it before anything else (execute_query, pg_query_supported): it checks the query's
+// expression keys under seg.mu (every refusal of such a key comes from here), builds the derived columns the segment does not hold WITHOUT
+// the lock, inserts them under it again, and keeps the query's columns alive and findable for the calling thread while it lives.
+class ExprKeyScope {
+ public:
+  ExprKeyScope(Segment& seg, const pg_query& q);
+  ~ExprKeyScope();
+  ExprKeyScope(const ExprKeyScope&) = delete;
+  ExprKeyScope& operator=(const ExprKeyScope&) = delete;
+ private:
+  size_t mark_;
+};
+// THE resolution of a group-by / DISTINCT text (seg.mu held): the derived column of an expression (`*keep` then shares its ownership: a plan
+// or shape that stores the pointer stores `keep` with it), else seg.find(text) — nullptr when the segment has no such column.
+Column* group_key_column(Segment& seg, const char* text, std::shared_ptr<Column>* keep);
+// the columns statistics count for a resolved key column: the operands of a derived column, else the column itself
+inline const std::vector<Column*> key_columns_read(Column* c) { return c->expr_operands.empty() ? std::vector<Column*>{c} : c->expr_operands; }
 // SELECT DISTINCT (PG_QUERY_FLAG_DISTINCT): the checked query and its key space (pg_plan.cpp); execute_distinct runs it (pg_exec.hip)
 struct DistinctShape {
   std::vector<Column*> cols;       // per DISTINCT column: the column of fixed-bit ids (its own dictIds, or its virtual dictionary's ids)
@@ -385,6 +422,8 @@ struct DistinctShape {
   uint64_t key_space = 1;          // product of the cardinalities (<= 2^32)
   bool dict_only = false;          // DictionaryBasedDistinctOperator: no filter, one dictionary-encoded column
   bool ordered = false;            // ORDER BY present
+  std::vector<std::shared_ptr<Column>> keep;   // the derived columns among `vdicts`' owners (expression keys)
+  int n_read = -1;                 // with an expression key: the distinct columns the keys name, operands included (-1: one per DISTINCT column)
 };
 DistinctShape distinct_shape(Segment& seg, const pg_query& q);
 // selection queries (PG_QUERY_FLAG_SELECTION): the checked output columns and ORDER BY (pg_plan.cpp); execute_selection runs them (pg_exec.hip)
@@ -521,6 +560,7 @@ struct SideGroups {
   std::vector<Column*> group_cols, group_ids;   // the group-by columns and their fixed-bit ids
   std::vector<uint64_t> mult;                   // weight of the group column's digit (column 0 least significant)
   uint64_t G = 1;
+  std::vector<std::shared_ptr<Column>> keep;    // the derived columns among group_cols (expression keys)
 };
 SideGroups side_groups(Segment& seg, const pg_query& q, const char* subject, const char* who, std::set<std::string>& read);   // seg.mu held; adds the columns' names to `read`
 void side_base_query(const pg_query& q, bool (*is_side)(const pg_agg_spec&), int32_t clear_flags, SideBaseQuery& out);   // pg_side_query.h, failing through fail()

@@ -465,7 +465,7 @@ void check_null_handling(Segment& seg, const pg_query& q) {
   int null_keys = 0;
   bool mv_keys = false, any_nulls = false;
   for (int j = 0; j < q.n_group_by; j++) {
-    Column* c = seg.find(q.group_by_columns[j]);
+    Column* c = group_key_column(seg, q.group_by_columns[j], nullptr);   // (an expression key holds no nulls: its operands' are refused)
     if (!c) continue;
     mv_keys |= c->is_mv;
     if (!has_nulls(seg, q.group_by_columns[j])) continue;
@@ -489,6 +489,7 @@ void check_null_handling(Segment& seg, const pg_query& q) {
 std::unique_ptr<Result> execute_query(Segment& seg, const pg_query& q_in, const CancelToken* cancel) {
   pg_query q = q_in;
   q.flags &= ~kQueryFlagNullPartition;   // internal
+  const ExprKeyScope expr_keys(seg, q);   // expressions among the group-by / DISTINCT keys: checked, their derived columns built and held
   if (q.flags & PG_QUERY_FLAG_SELECTION) return execute_selection(seg, q, cancel);   // its columns' nulls are refused (selection_shape)
   if (q.flags & PG_QUERY_FLAG_DISTINCT) return execute_distinct(seg, q, cancel);   // its columns' nulls are refused (distinct_shape)
   // aggregations over expressions: before the PERCENTILE check, so that the expression pass is the outer one of a query that carries both —

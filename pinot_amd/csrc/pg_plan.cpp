@@ -1826,16 +1826,25 @@ static std::shared_ptr<CompiledPlan> compile_in_space(Segment& seg, OpPtr root_o
   std::vector<Column*> projected;
   auto project = [&](Column* c) {
     if (c->public_col) c = c->public_col;   // the internal twin of a raw multi-value column counts as that column
-    if (std::find(projected.begin(), projected.end(), c) == projected.end()) projected.push_back(c);
+    // an expression key counts its operand columns, never itself (it has no forward index: nothing is read under its name)
+    for (Column* r : key_columns_read(c))
+      if (std::find(projected.begin(), projected.end(), r) == projected.end()) projected.push_back(r);
   };
   int64_t G = 1;
   bool huge_key_space = false;
   for (int j = 0; j < q->n_group_by; j++) {
     if (!q->group_by_columns) fail(PG_ERR_INVALID_ARGUMENT, "group_by_columns is null");
-    Column* c = seg.find(q->group_by_columns[j]);
+    std::shared_ptr<Column> derived;
+    Column* c = group_key_column(seg, q->group_by_columns[j], &derived);
     if (!c) fail(PG_ERR_NOT_FOUND, "column not found: %s", q->group_by_columns[j] ? q->group_by_columns[j] : "(null)");
+    // an expression key: a DOUBLE column that is nothing but its virtual dictionary — never the hash path over raw values below (it has
+    // none), always the branch "any other raw key"; the plan shares its ownership (the segment's cache may drop it)
+    if (derived) {
+      if (st) fail(PG_ERR_INTERNAL, "expression key %s over a star-tree", c->name.c_str());
+      P.pinned.push_back(derived);
+    }
     // (a LONG column that may hold Long.MAX_VALUE — the hash table's empty marker once biased — goes through its virtual dictionary)
-    const bool one_raw_int = !c->has_dictionary && q->n_group_by == 1 && (c->col_kind == PG_COL_RAW32 || c->col_kind == PG_COL_RAW64) &&
+    const bool one_raw_int = !derived && !c->has_dictionary && q->n_group_by == 1 && (c->col_kind == PG_COL_RAW32 || c->col_kind == PG_COL_RAW64) &&
                              (c->data_type == PG_TYPE_INT || (c->data_type == PG_TYPE_LONG && c->max_abs_int < (uint64_t)INT64_MAX));
     if (one_raw_int) {
       // NoDictionarySingleColumnGroupKeyGenerator (core/query/aggregation/groupby/NoDictionarySingleColumnGroupKeyGenerator.java:53-90,
@@ -2736,15 +2745,20 @@ DistinctShape distinct_shape(Segment& seg, const pg_query& q) {
   DistinctShape S;
   const int n = q.n_group_by;
   std::lock_guard<std::mutex> lock(seg.mu);   // virtual dictionaries are built under the segment's lock
+  std::vector<Column*> read;   // the distinct columns the keys name, the operands of expression keys in their place
+  bool any_derived = false;
   for (int j = 0; j < n; j++) {
     const char* name = q.group_by_columns[j];
-    Column* c = name ? seg.find(name) : nullptr;
+    std::shared_ptr<Column> derived;
+    Column* c = group_key_column(seg, name, &derived);   // an arithmetic expression: its derived DOUBLE column, a raw column from here on
     if (!c) {
       bool identifier = name && *name;
       for (const char* p = name; identifier && *p; p++) identifier = isalnum((unsigned char)*p) || *p == '_' || *p == '.' || *p == '$';
       if (!identifier) fail(PG_ERR_UNSUPPORTED, "DISTINCT over the expression %s", name ? name : "(null)");
       fail(PG_ERR_NOT_FOUND, "column not found: %s", name);
     }
+    if (derived) { S.keep.push_back(derived); any_derived = true; }
+    for (Column* r : key_columns_read(c)) if (std::find(read.begin(), read.end(), r) == read.end()) read.push_back(r);
     if (c->is_mv || c->raw_mv) fail(PG_ERR_UNSUPPORTED, "DISTINCT over the multi-value column %s", c->name.c_str());
     if (q.flags & PG_QUERY_FLAG_NULL_HANDLING) {
       auto it = seg.null_vectors.find(c->name);
@@ -2764,6 +2778,7 @@ DistinctShape distinct_shape(Segment& seg, const pg_query& q) {
     S.cols.push_back(id);
     S.vdicts.push_back(vd);
   }
+  if (any_derived) S.n_read = (int)read.size();
   // digit order: the ORDER BY columns first (most significant, in ORDER BY order), then the others in DISTINCT order
   std::vector<int> order;
   S.desc.assign((size_t)n, 0);

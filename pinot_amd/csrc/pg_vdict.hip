@@ -27,27 +27,15 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include "pg_internal.hpp"
+#include "pg_vdict_key.h"
+
+void pg_expr_launch_keys(const PgExprArgs* args, uint64_t* keys, int grid, hipStream_t stream);   // pg_kernels_exprkey.hip
 
 namespace pg {
 namespace {
 
-// order-preserving unsigned keys; kind: 0 INT, 1 LONG, 2 FLOAT, 3 DOUBLE
-__device__ __host__ inline uint64_t key_of_bits(uint64_t be_value, int kind) {
-  switch (kind) {
-    case 0: return (uint64_t)(int64_t)(int32_t)(uint32_t)be_value ^ (1ULL << 63);
-    case 1: return be_value ^ (1ULL << 63);
-    case 2: {
-      uint32_t f = (uint32_t)be_value;
-      if ((f & 0x7FFFFFFFu) > 0x7F800000u) f = 0x7FC00000u;          // floatToIntBits: one NaN
-      return (uint64_t)(f ^ ((f >> 31) ? 0xFFFFFFFFu : 0x80000000u));
-    }
-    default: {
-      uint64_t d = be_value;
-      if ((d & 0x7FFFFFFFFFFFFFFFULL) > 0x7FF0000000000000ULL) d = 0x7FF8000000000000ULL;
-      return d ^ ((d >> 63) ? ~0ULL : (1ULL << 63));
-    }
-  }
-}
+// order-preserving unsigned keys (pg_vdict_key.h, shared with pg_expr_keys); kind: 0 INT, 1 LONG, 2 FLOAT, 3 DOUBLE
+__device__ __host__ inline uint64_t key_of_bits(uint64_t be_value, int kind) { return pg_vdict_key_of_bits(be_value, kind); }
 
 __global__ void pg_vdict_keys_kernel(const uint8_t* __restrict__ raw, int width, int kind, uint64_t* __restrict__ keys, int64_t n) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -157,28 +145,24 @@ int64_t vdict_value_of_key(uint64_t key, int kind, double* as_double) {
   }
 }
 
-// Builds c.vdict (idempotent; the caller holds the segment's lock).  The segment's device is current.
-void ensure_virtual_dictionary(Segment& seg, Column& c) {
-  if (c.vdict) return;
-  const bool var_bytes = c.col_kind == PG_COL_VAR_BYTES;
-  if (c.has_dictionary || (!var_bytes && ((c.col_kind != PG_COL_RAW32 && c.col_kind != PG_COL_RAW64) || c.data_type > PG_TYPE_DOUBLE)))
-    fail(PG_ERR_UNSUPPORTED, "no-dictionary group-by column %s: only raw INT / LONG / FLOAT / DOUBLE / STRING / BYTES columns get a virtual dictionary", c.name.c_str());
-  const int kind = var_bytes ? 4 : c.data_type == PG_TYPE_INT ? 0 : c.data_type == PG_TYPE_LONG ? 1 : c.data_type == PG_TYPE_FLOAT ? 2 : 3;
-  const int width = c.col_kind == PG_COL_RAW32 ? 4 : 8;
+// Everything after the key pass: `keys` holds the n docs' order-preserving keys (kind 0-3) or hashes (kind 4, `bytes_src` the raw
+// STRING / BYTES column they were taken from) in HBM.  Sort, unique, ids, the bit-packed forward index, the hash over the distinct keys.
+// `named` is what messages call the column; `*id_bytes` the HBM the id column keeps.  The segment's device is current.
+static std::unique_ptr<Column> vdict_from_keys(Segment& seg, const std::string& named, int32_t data_type, int32_t val_type, int kind, DeviceBuffer& keys,
+                                               const Column* bytes_src, uint64_t* id_bytes) {
+  const bool var_bytes = kind == 4;
   const int64_t n = seg.total_docs;
   auto vd = std::make_unique<Column>();
-  vd->name = c.name + "$ids";
-  vd->data_type = c.data_type;
+  vd->name = named + "$ids";
+  vd->data_type = data_type;
   vd->has_dictionary = true;
   vd->col_kind = PG_COL_FIXED_BIT;
-  vd->val_type = c.val_type;
+  vd->val_type = val_type;
   std::vector<uint64_t> distinct_host;
+  *id_bytes = 0;
   if (n > 0) {
-    DeviceBuffer keys((size_t)n * 8), sorted((size_t)n * 8), count(8, true);
+    DeviceBuffer sorted((size_t)n * 8), count(8, true);
     const unsigned grid = (unsigned)((n + 255) / 256);
-    if (var_bytes) hipLaunchKernelGGL(pg_vdict_hash_kernel, dim3(grid), dim3(256), 0, 0, c.fwd_dev.as<uint8_t>(), c.vb_offsets_dev.as<int64_t>(), keys.as<uint64_t>(), n);
-    else hipLaunchKernelGGL(pg_vdict_keys_kernel, dim3(grid), dim3(256), 0, 0, c.fwd_dev.as<uint8_t>(), width, kind, keys.as<uint64_t>(), n);
-    PG_HIP(hipGetLastError());
     size_t tmp_bytes = 0;
     PG_HIP(rocprim::radix_sort_keys(nullptr, tmp_bytes, keys.as<uint64_t>(), sorted.as<uint64_t>(), (size_t)n));
     {
@@ -195,7 +179,7 @@ void ensure_virtual_dictionary(Segment& seg, Column& c) {
     }
     uint32_t card = 0;
     PG_HIP(hipMemcpy(&card, count.ptr, 4, hipMemcpyDeviceToHost));
-    if (card == 0 || card > 0x7FFFFFFFu) fail(PG_ERR_UNSUPPORTED, "column %s: %u distinct values", c.name.c_str(), card);
+    if (card == 0 || card > 0x7FFFFFFFu) fail(PG_ERR_UNSUPPORTED, "column %s: %u distinct values", named.c_str(), card);
     distinct_host.resize(card);
     PG_HIP(hipMemcpy(distinct_host.data(), distinct.ptr, (size_t)card * 8, hipMemcpyDeviceToHost));
     // ids (reusing `sorted` as the 32-bit id array), then the bit-packed forward index
@@ -213,6 +197,7 @@ void ensure_virtual_dictionary(Segment& seg, Column& c) {
     hipLaunchKernelGGL(pg_vdict_pack_kernel, dim3((unsigned)((n_dwords + 255) / 256)), dim3(256), 0, 0, ids, n, bits, vd->fwd_dev.as<uint32_t>(), n_dwords);
     PG_HIP(hipGetLastError());
     if (var_bytes) {
+      const Column& c = *bytes_src;
       // the hash is an identity on this column?  representatives, then every doc against its representative
       DeviceBuffer rep((size_t)card * 4), flag(8, true);
       PG_HIP(hipMemset(rep.ptr, 0xFF, (size_t)card * 4));
@@ -223,7 +208,7 @@ void ensure_virtual_dictionary(Segment& seg, Column& c) {
       PG_HIP(hipGetLastError());
       uint32_t collided = 0;
       PG_HIP(hipMemcpy(&collided, flag.ptr, 4, hipMemcpyDeviceToHost));
-      if (collided) fail(PG_ERR_UNSUPPORTED, "column %s: two distinct values share a 64-bit hash; its GROUP BY stays with the Java plan", c.name.c_str());
+      if (collided) fail(PG_ERR_UNSUPPORTED, "column %s: two distinct values share a 64-bit hash; its GROUP BY stays with the Java plan", named.c_str());
       // the distinct values in id order: lengths, exclusive scan, gather; copied to the host once (the groups' keys come from here)
       DeviceBuffer len(((size_t)card + 1) * 8, true), out_off(((size_t)card + 1) * 8, true);
       hipLaunchKernelGGL(pg_vdict_value_len_kernel, dim3((card + 255) / 256), dim3(256), 0, 0, c.vb_offsets_dev.as<int64_t>(), rep.as<uint32_t>(), len.as<int64_t>(), card);
@@ -244,7 +229,7 @@ void ensure_virtual_dictionary(Segment& seg, Column& c) {
       if (total > 0) PG_HIP(hipMemcpy(vd->vdict_bytes.data(), values.ptr, (size_t)total, hipMemcpyDeviceToHost));
     }
     PG_HIP(hipDeviceSynchronize());
-    seg.device_bytes += bytes;
+    *id_bytes = bytes;
   } else {
     vd->bits = 1;
     vd->cardinality = 1;
@@ -258,7 +243,45 @@ void ensure_virtual_dictionary(Segment& seg, Column& c) {
   for (uint64_t k : vd->vdict_keys) { h ^= k; h *= 1099511628211ULL; }
   for (uint8_t b : vd->vdict_bytes) { h ^= b; h *= 1099511628211ULL; }   // var-byte keys: the values themselves (ids follow hash order)
   vd->vdict_hash = h;
-  c.vdict = std::move(vd);
+  return vd;
+}
+
+// Builds c.vdict (idempotent; the caller holds the segment's lock).  The segment's device is current.
+void ensure_virtual_dictionary(Segment& seg, Column& c) {
+  if (c.vdict) return;
+  const bool var_bytes = c.col_kind == PG_COL_VAR_BYTES;
+  if (c.has_dictionary || (!var_bytes && ((c.col_kind != PG_COL_RAW32 && c.col_kind != PG_COL_RAW64) || c.data_type > PG_TYPE_DOUBLE)))
+    fail(PG_ERR_UNSUPPORTED, "no-dictionary group-by column %s: only raw INT / LONG / FLOAT / DOUBLE / STRING / BYTES columns get a virtual dictionary", c.name.c_str());
+  const int kind = var_bytes ? 4 : c.data_type == PG_TYPE_INT ? 0 : c.data_type == PG_TYPE_LONG ? 1 : c.data_type == PG_TYPE_FLOAT ? 2 : 3;
+  const int width = c.col_kind == PG_COL_RAW32 ? 4 : 8;
+  const int64_t n = seg.total_docs;
+  DeviceBuffer keys;
+  if (n > 0) {
+    keys.alloc((size_t)n * 8);
+    const unsigned grid = (unsigned)((n + 255) / 256);
+    if (var_bytes) hipLaunchKernelGGL(pg_vdict_hash_kernel, dim3(grid), dim3(256), 0, 0, c.fwd_dev.as<uint8_t>(), c.vb_offsets_dev.as<int64_t>(), keys.as<uint64_t>(), n);
+    else hipLaunchKernelGGL(pg_vdict_keys_kernel, dim3(grid), dim3(256), 0, 0, c.fwd_dev.as<uint8_t>(), width, kind, keys.as<uint64_t>(), n);
+    PG_HIP(hipGetLastError());
+  }
+  uint64_t id_bytes = 0;
+  c.vdict = vdict_from_keys(seg, c.name, c.data_type, c.val_type, kind, keys, var_bytes ? &c : nullptr, &id_bytes);
+  seg.device_bytes += id_bytes;
+}
+
+// The virtual dictionary of an expression key: pg_expr_keys writes the docs' DOUBLE keys, and from there on the expression is a raw DOUBLE
+// column.  The 8 B/doc of keys die with this call; the bit-packed ids and the distinct keys stay.  Runs WITHOUT seg.mu.
+std::unique_ptr<Column> expression_virtual_dictionary(Segment& seg, const std::string& text, const PgExprArgs& args, uint64_t* id_bytes) {
+  use_device(seg.device);
+  const int64_t n = seg.total_docs;
+  DeviceBuffer keys;
+  if (n > 0) {
+    keys.alloc((size_t)n * 8);
+    const int64_t per_wg = 4 * PG_EXPR_PRED_WORDS;   // 64-doc words per workgroup and iteration (4 wavefronts of 256 threads)
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)device_cus(seg.device) * 8, (args.scan.n_words + per_wg - 1) / per_wg));
+    pg_expr_launch_keys(&args, keys.as<uint64_t>(), grid, nullptr);   // the stream the sort and the id kernels run on
+    PG_HIP(hipGetLastError());
+  }
+  return vdict_from_keys(seg, text, PG_TYPE_DOUBLE, PG_V_F64, 3, keys, nullptr, id_bytes);
 }
 
 }  // namespace pg

@@ -91,9 +91,9 @@ class AggregationSpec:
 class QueryContext:
     table: str = "testTable"
     filter: Optional[FilterContext] = None
-    group_by: List[str] = field(default_factory=list)
+    group_by: List[str] = field(default_factory=list)   # columns, or arithmetic expressions as their canonical text, e.g. "sub(column1,'100000')"
     aggregations: List[AggregationSpec] = field(default_factory=list)
-    select_columns: List[str] = field(default_factory=list)   # plain identifiers in the select list
+    select_columns: List[str] = field(default_factory=list)   # identifiers and arithmetic expressions (canonical text) in the select list
     order_by: List[Tuple[str, bool]] = field(default_factory=list)  # (expression text, ascending)
     order_by_nulls_last: List[Optional[bool]] = field(default_factory=list)   # parallel: NULLS LAST / NULLS FIRST, None = the default (OrderByExpressionContext#isNullsLast: as ascending)
     limit: int = 10
@@ -102,7 +102,7 @@ class QueryContext:
     flags: int = 0
     has_group_by: bool = False
     min_segment_group_trim_size: int = -1   # InstancePlanMakerImplV2.DEFAULT_MIN_SEGMENT_GROUP_TRIM_SIZE: the segment's groups are not trimmed
-    distinct: List[str] = field(default_factory=list)   # SELECT DISTINCT a, b: the DISTINCT columns (empty: not a DISTINCT query)
+    distinct: List[str] = field(default_factory=list)   # SELECT DISTINCT a, b + c: the DISTINCT columns and expressions (empty: not a DISTINCT query)
     selection: List[str] = field(default_factory=list)  # a selection query (no aggregation, GROUP BY or DISTINCT): its select list, "*" kept
 
     def extract_expressions(self, column_names) -> List[str]:
@@ -134,9 +134,13 @@ class QueryContext:
         for i, a in enumerate(self.aggregations):
             if "(" in (a.column or ""):
                 expr_aggs.setdefault((a.function, a.column), i)
+        # group-by expressions by canonical text: 'SUB(   column1, 100000\t)' names the key "sub(column1,'100000')"
+        keys = [canonical_expression(g) if "(" in g else g for g in self.group_by]
         for text, asc in self.order_by:
             if text in self.group_by:
                 out.append((capi.ORDER_BY_GROUP_KEY, self.group_by.index(text), asc))
+            elif canonical_expression(text) is not None and canonical_expression(text) in keys:
+                out.append((capi.ORDER_BY_GROUP_KEY, keys.index(canonical_expression(text)), asc))
             elif norm(text) in aggs:
                 out.append((capi.ORDER_BY_AGGREGATION, aggs.index(norm(text)), asc))
             elif _percentile_of_text(text) is not None and _percentile_of_text(text) in pctl:   # any of PERCENTILE's spellings names the same aggregation
@@ -188,6 +192,20 @@ def _expression_aggregation_of_text(text: str):
     if p.peek()[0] != "eof" or len(q.aggregations) != 1 or "(" not in (q.aggregations[0].column or ""):
         return None
     return (q.aggregations[0].function, q.aggregations[0].column)
+
+
+@functools.lru_cache(maxsize=256)
+def canonical_expression(text: str):
+    """The canonical text of an arithmetic expression in any spelling (infix or function form, any case and whitespace, literals quoted or
+    bare); a lone column gives its name; None when the text is no such expression."""
+    try:
+        p = _Parser(text)
+        e = p.expression()
+    except (SqlError, IndexError):
+        return None
+    if p.peek()[0] != "eof" or e.startswith("'"):
+        return None
+    return e
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -428,6 +446,27 @@ class _Parser:
             return f"{t[1].lower().replace('_', '')}({','.join(args)})"
         return t[1]
 
+    _ARITHMETIC = frozenset(("add", "sub", "mult", "div", "plus", "minus", "times", "divide"))
+
+    def starts_expression(self) -> bool:
+        """Does an arithmetic expression start here, where a select item, a GROUP BY key or an ORDER BY expression is expected: one of the
+        eight function forms, a parenthesis, or an operand followed by an infix operator?"""
+        t, u = self.peek(), self.peek(1)
+        if t == ("op", "("):
+            return True
+        if t[0] == "id" and u == ("op", "("):
+            return t[1].lower().replace("_", "") in self._ARITHMETIC
+        if t[0] in ("id", "num"):
+            return (u[0] == "op" and u[1] in self._INFIX) or (u[0] == "num" and u[1].startswith("-"))
+        return False
+
+    def key_expression(self) -> str:
+        """a GROUP BY / DISTINCT key: a column, or an arithmetic expression as its canonical text"""
+        e = self.expression()
+        if e.startswith("'"):
+            raise SqlError(f"a literal ({e}) where a column or an expression is expected")
+        return e
+
     def aggregation_argument(self) -> str:
         e = self.expression()
         if e.startswith("'"):
@@ -436,6 +475,11 @@ class _Parser:
 
     # --- select -------------------------------------------------------------------------------------------------
     def select_item(self, q: QueryContext):
+        if self.peek() != ("op", "*") and self.starts_expression():   # an arithmetic expression: a DISTINCT / GROUP BY key of the select list
+            q.select_columns.append(self.key_expression())
+            if self.kw("AS"):
+                self.i += 2
+            return
         t = self.take()
         if t == ("op", "*"):   # SELECT *
             q.select_columns.append("*")
@@ -498,17 +542,20 @@ class _Parser:
             self.i += 1
             self.expect_kw("BY")
             q.has_group_by = True
-            q.group_by.append(self.take()[1])
+            q.group_by.append(self.key_expression())
             while self.peek() == ("op", ","):
                 self.i += 1
-                q.group_by.append(self.take()[1])
+                q.group_by.append(self.key_expression())
         if self.kw("ORDER"):
             self.i += 1
             self.expect_kw("BY")
             while True:
-                t = self.take()
-                text = t[1]
-                if self.peek() == ("op", "("):
+                if self.starts_expression():   # an arithmetic expression: its canonical text, as GROUP BY and the select list carry it
+                    t, text = None, self.key_expression()
+                else:
+                    t = self.take()
+                    text = t[1]
+                if t is not None and self.peek() == ("op", "("):
                     depth = 0
                     while True:
                         u = self.take()
