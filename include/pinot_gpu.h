@@ -249,7 +249,18 @@ typedef struct pg_query {
                                             pg_result_group_values_double and named by the text in pg_result_data_table_v4.  At most 4 such
                                             keys per query; refused (PG_ERR_UNSUPPORTED: the Java plan answers): any other function, STRING /
                                             BYTES / multi-value operands, an operand with nulls under PG_QUERY_FLAG_NULL_HANDLING, a multi-value
-                                            group-by column next to such a key, and PG_QUERY_FLAG_SELECTION.  PG_QUERY_FLAG_DISTINCT takes them. */
+                                            group-by column next to such a key, and PG_QUERY_FLAG_SELECTION.  PG_QUERY_FLAG_DISTINCT takes them.
+                                            Or a TIME-BUCKET TRANSFORM's text (here only, not in pg_agg_spec.column or a filter), as
+                                            ExpressionContext#toString prints it, every literal single-quoted with its case kept:
+                                            timeconvert(x,'IN','OUT'); toepoch{seconds,minutes,hours,days}(x), ...rounded(x,'n'), ...bucket(x,'n');
+                                            datetimeconvert(x,'inFmt','outFmt','gran') between EPOCH formats; datetrunc('unit',x[,'inUnit'[,'tz'
+                                            [,'outUnit']]]) with tz UTC or a fixed offset +-HH:MM — x one single-value INT / LONG column.  The key
+                                            is the transform's LONG value, grouped as a raw LONG column's values are, handed back through
+                                            pg_result_group_values_long and named by the text in pg_result_data_table_v4 (type LONG).  Such keys
+                                            count among the 4 above.  PG_ERR_INVALID_ARGUMENT: a wrong argument count, an unknown unit name, a
+                                            malformed format, n = 0; PG_ERR_UNSUPPORTED: an x that is no plain column or not INT / LONG, WEEKS /
+                                            MONTHS / YEARS units, named time zones, SIMPLE_DATE_FORMAT / TIMESTAMP formats, a bucketing time zone,
+                                            and what is refused for arithmetic keys. */
   const pg_agg_spec* aggregations;
   /* InstancePlanMakerImplV2.java:75-96 defaults are applied for values <= 0 */
   int32_t num_groups_limit;                     /* DEFAULT_NUM_GROUPS_LIMIT = 100 000 */

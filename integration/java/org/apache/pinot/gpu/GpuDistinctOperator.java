@@ -162,7 +162,7 @@ public class GpuDistinctOperator extends BaseOperator<BaseResultsBlock> {
 
   /**
    * One column of the tuples: dictIds through the segment's Dictionary (getInternal: the stored type), values of raw columns and of
-   * arithmetic expressions (DOUBLE values).
+   * arithmetic expressions (DOUBLE values) and of time-bucket transforms (LONG values).
    */
   private Object[] columnValues(long result, int j, ExpressionContext column, int numRows) {
     Object[] out = new Object[numRows];

@@ -167,12 +167,13 @@ public class GpuGroupByOperator extends BaseOperator<BaseResultsBlock> {
       // NoDictionaryMultiColumnGroupKeyGenerator.java:60-130): LONG values for INT / LONG, DOUBLE values for FLOAT / DOUBLE
       Object[][] keys = new Object[numGroups][groupBy.size()];
       for (int j = 0; j < groupBy.size(); j++) {
-        // (an arithmetic expression has no column: its keys always come back as DOUBLE values, named by the expression's text in the schema)
+        // (an expression key has no column: an arithmetic expression's keys always come back as DOUBLE values, a time-bucket transform's as
+        // LONG values, named by the expression's text in the schema)
         String column = groupBy.get(j).getType() == ExpressionContext.Type.IDENTIFIER ? groupBy.get(j).getIdentifier() : null;
         if (PinotGpu.resultGroupKeyType(result, j) == PinotGpu.GROUP_KEY_LONG_VALUES) {
           long[] values = new long[numGroups];
           PinotGpu.resultGroupValuesLong(result, j, values);
-          boolean isInt = _segment.getDataSource(column).getDataSourceMetadata().getDataType().getStoredType().name().equals("INT");
+          boolean isInt = GpuResultObjects.keyStoredType(_segment, groupBy.get(j)).equals("INT");   // (a time-bucket transform: LONG)
           for (int g = 0; g < numGroups; g++) {
             keys[g][j] = isInt ? (Object) (int) values[g] : (Object) values[g];
           }

@@ -250,13 +250,14 @@ public final class GpuResultObjects {
 
   /**
    * DataSchema column types of the group-by columns (GroupByOperator.java:74-97 takes them from the expressions' result metadata): the
-   * column's type, or DOUBLE for an arithmetic expression (the result metadata of the add / sub / mult / div transform functions).
+   * column's type, DOUBLE for an arithmetic expression (the result metadata of the add / sub / mult / div transform functions), LONG for a
+   * time-bucket transform (LONG_SV_NO_DICTIONARY_METADATA).
    */
   public static DataSchema.ColumnDataType[] keyTypes(IndexSegment segment, List<ExpressionContext> groupBy) {
     DataSchema.ColumnDataType[] types = new DataSchema.ColumnDataType[groupBy.size()];
     for (int i = 0; i < types.length; i++) {
       if (groupBy.get(i).getType() != ExpressionContext.Type.IDENTIFIER) {
-        types[i] = DataSchema.ColumnDataType.DOUBLE;
+        types[i] = NativeQuery.isTimeBucket(groupBy.get(i)) ? DataSchema.ColumnDataType.LONG : DataSchema.ColumnDataType.DOUBLE;
         continue;
       }
       DataType dataType = segment.getDataSource(groupBy.get(i).getIdentifier()).getDataSourceMetadata().getDataType();
@@ -265,10 +266,13 @@ public final class GpuResultObjects {
     return types;
   }
 
-  /** The stored type's name behind a key: the column's, or DOUBLE for an arithmetic expression (its values come back as DOUBLE value keys). */
+  /**
+   * The stored type's name behind a key: the column's, DOUBLE for an arithmetic expression (its values come back as DOUBLE value keys), LONG
+   * for a time-bucket transform (LONG value keys).
+   */
   public static String keyStoredType(IndexSegment segment, ExpressionContext key) {
     if (key.getType() != ExpressionContext.Type.IDENTIFIER) {
-      return "DOUBLE";
+      return NativeQuery.isTimeBucket(key) ? "LONG" : "DOUBLE";
     }
     return segment.getDataSource(key.getIdentifier()).getDataSourceMetadata().getDataType().getStoredType().name();
   }

@@ -387,11 +387,40 @@ public final class NativeQuery implements AutoCloseable {
   }
 
   /**
-   * A GROUP BY / DISTINCT key as pg_query.group_by_columns carries it: a column's name, or an arithmetic expression as the text
-   * ExpressionContext#toString prints (the library groups its DOUBLE values through a derived key column); null for anything else.
+   * A GROUP BY / DISTINCT key as pg_query.group_by_columns carries it: a column's name, or an arithmetic expression or a time-bucket transform
+   * as the text ExpressionContext#toString prints (the library groups its DOUBLE / LONG values through a derived key column); null for
+   * anything else.
    */
   private static String keyText(ExpressionContext e) {
-    return e.getType() == ExpressionContext.Type.IDENTIFIER ? e.getIdentifier() : isArithmetic(e) ? e.toString() : null;
+    return e.getType() == ExpressionContext.Type.IDENTIFIER ? e.getIdentifier() : isArithmetic(e) || isTimeBucket(e) ? e.toString() : null;
+  }
+
+  /**
+   * A time-bucket transform as a GROUP BY / DISTINCT key (and only there: not an aggregation's argument, a filter's left-hand side or a
+   * selection): timeConvert, toEpoch{Seconds,Minutes,Hours,Days}[Rounded|Bucket], dateTimeConvert or dateTrunc over ONE identifier, every
+   * other argument a literal.  The library parses the text ExpressionContext#toString prints, groups the transform's LONG values through a
+   * derived key column and refuses what it does not run (named time zones, SIMPLE_DATE_FORMAT, WEEKS / MONTHS / YEARS units): the Java plan
+   * answers then.
+   */
+  static boolean isTimeBucket(ExpressionContext e) {
+    if (e.getType() != ExpressionContext.Type.FUNCTION || e.getFunction().getType() != FunctionContext.Type.TRANSFORM) {
+      return false;
+    }
+    FunctionContext f = e.getFunction();
+    String name = f.getFunctionName();
+    boolean family = name.equals("timeconvert") || name.equals("datetimeconvert") || name.equals("datetrunc")
+        || name.matches("toepoch(seconds|minutes|hours|days)(rounded|bucket)?");
+    if (!family) {
+      return false;
+    }
+    int value = name.equals("datetrunc") ? 1 : 0;
+    List<ExpressionContext> args = f.getArguments();
+    for (int i = 0; i < args.size(); i++) {
+      if (args.get(i).getType() != (i == value ? ExpressionContext.Type.IDENTIFIER : ExpressionContext.Type.LITERAL)) {
+        return false;
+      }
+    }
+    return args.size() > value;
   }
 
   private static boolean takesExpression(int fn) {

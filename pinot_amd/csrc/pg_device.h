@@ -597,6 +597,7 @@ struct PgSelectOutCol {
 // [G][slots_per_group] of int64.  Per expression: four limbs of the exact fixed-point SUM (pg_fixed_point.h, L = 4, scale q), the MIN and the
 // MAX as order-preserving int64 keys of doubles; one doc count for AVG.  Unused slots are left out.
 #include "pg_expr_program.h"
+#include "pg_time_program.h"
 #define PG_EXPR_SUM_LIMBS 4
 #define PG_EXPR_MAX_SLOTS (PG_EXPR_MAX_EXPRS * (PG_EXPR_SUM_LIMBS + 2) + 1)
 #define PG_EXPR_LDS_SLOTS 16384   // 128 KiB of the CU's 160 KiB: one persistent workgroup per CU, as pg_pctl_lds
@@ -621,6 +622,13 @@ struct PgExprArgs {
   PgExprDesc exprs[PG_EXPR_MAX_EXPRS];
   int64_t ident[PG_EXPR_MAX_SLOTS];   // per slot of a row: 0 (SUM limbs, count), INT64_MAX (MIN), INT64_MIN (MAX)
   pg_expr_step steps[PG_EXPR_MAX_EXPRS * PG_EXPR_MAX_OPS];
+};
+// a time-bucket transform as a key (pg_kernels_timekey.hip): the value column and the normal form, wave-uniform kernel arguments
+struct PgTimeKeyArgs {
+  PgValueSrc src;
+  int64_t n_docs;
+  int64_t n_words;   // ceil(n_docs / 64)
+  pg_time_program prog;
 };
 // ---- an arithmetic expression as a filter leaf (pg_kernels_exprpred.hip) -----------------------------------------------------------------------
 // The reference's ExpressionFilterOperator: expression 0 of a PgExprArgs evaluated over ALL docs and compared by the raw DOUBLE predicate

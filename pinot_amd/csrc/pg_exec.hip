@@ -14,6 +14,7 @@
 
 #include "pg_internal.hpp"
 #include "pg_expr.h"
+#include "pg_time_expr.h"
 
 #define PG_DECL_FAST(NAME) extern "C" __global__ void NAME(const PgQueryPlan p);
 #define PG_DECL_GENERIC PG_DECL_FAST(pg_generic_query_f) PG_DECL_FAST(pg_generic_query_l) PG_DECL_FAST(pg_generic_query_g)
@@ -1194,8 +1195,9 @@ void fill_result_schema(Segment& seg, const pg_query& q, Result& r) {
     res->schema_keys.resize((size_t)q.n_group_by);
     for (int j = 0; j < q.n_group_by; j++) {
       column_of(q.group_by_columns[j], res->schema_keys[(size_t)j]);
-      // an expression key: named by its text as given, typed by the transform's result (DOUBLE)
-      if (expr_is_expression(q.group_by_columns[j])) res->schema_keys[(size_t)j].data_type = PG_TYPE_DOUBLE;
+      // an expression key: named by its text as given, typed by the transform's result (DOUBLE; a time-bucket transform's: LONG)
+      if (expr_is_expression(q.group_by_columns[j]))
+        res->schema_keys[(size_t)j].data_type = time_expr_is_time_function(q.group_by_columns[j]) ? PG_TYPE_LONG : PG_TYPE_DOUBLE;
     }
     res->schema_aggs.resize((size_t)q.n_aggregations);
     for (int a = 0; a < q.n_aggregations; a++) {

@@ -10,6 +10,7 @@
 // first insertion stays.
 #include "pg_internal.hpp"
 #include "pg_expr.h"
+#include "pg_time_expr.h"
 
 #include <algorithm>
 
@@ -27,19 +28,46 @@ std::string short_text(const std::string& t) { return t.size() > 200 ? t.substr(
 
 struct KeySpec {
   std::string text;
+  bool time = false;     // a time-bucket transform: `targs`, a LONG column; else `args`, a DOUBLE column
   PgExprArgs args;
+  PgTimeKeyArgs targs;
   std::vector<Column*> cols;
 };
+
+// the value column of a time-bucket transform, checked (seg.mu held): a single-value INT / LONG column, dictionary-encoded or raw
+Column* time_value_column(Segment& seg, const std::string& name, bool null_handling) {
+  Column* c = seg.find(name.c_str());
+  if (!c) fail(PG_ERR_NOT_FOUND, "column not found: %s", short_text(name).c_str());
+  if (c->is_mv || c->raw_mv) fail(PG_ERR_UNSUPPORTED, "time function over the multi-value column %s", c->name.c_str());
+  if (c->data_type != PG_TYPE_INT && c->data_type != PG_TYPE_LONG)
+    fail(PG_ERR_UNSUPPORTED, "time function over the %s column %s (INT and LONG value columns run on the GPU path)",
+         c->data_type == PG_TYPE_FLOAT ? "FLOAT" : c->data_type == PG_TYPE_DOUBLE ? "DOUBLE" : c->data_type == PG_TYPE_STRING ? "STRING" : "BYTES", c->name.c_str());
+  return expr_operand_column(seg, name, null_handling);   // nulls and layout: the rules and texts every expression shares (pg_plan.cpp)
+}
 
 // one expression key, checked and resolved (seg.mu held): the program and its operand columns
 KeySpec key_spec(Segment& seg, const char* text, bool null_handling) {
   KeySpec K;
   K.text = text;
-  ExprProgram prog;
+  memset(&K.args, 0, sizeof(K.args));
+  memset(&K.targs, 0, sizeof(K.targs));
   std::string error;
+  if (time_expr_is_time_function(text)) {   // by function name, before the arithmetic parser (which knows none of them)
+    TimeProgram tp;
+    const int32_t st = time_expr_parse(text, tp, error);
+    if (st != PG_OK) fail(st, "%s (in %s)", error.c_str(), short_text(K.text).c_str());
+    Column* c = time_value_column(seg, tp.column, null_handling);
+    K.time = true;
+    expr_fill_src(K.targs.src, *c);
+    K.targs.n_docs = seg.total_docs;
+    K.targs.n_words = ((int64_t)seg.total_docs + 63) / 64;
+    K.targs.prog = tp.prog;
+    K.cols.push_back(c);
+    return K;
+  }
+  ExprProgram prog;
   const int32_t st = expr_parse(text, prog, error);
   if (st != PG_OK) fail(st, "%s (in %s)", error.c_str(), short_text(K.text).c_str());
-  memset(&K.args, 0, sizeof(K.args));
   for (const std::string& name : prog.columns) {
     Column* c = expr_operand_column(seg, name, null_handling);   // the rules every expression shares (pg_plan.cpp)
     expr_fill_src(K.args.srcs[K.cols.size()], *c);               // (expr_parse admits at most PG_EXPR_MAX_SRCS columns)
@@ -56,16 +84,16 @@ KeySpec key_spec(Segment& seg, const char* text, bool null_handling) {
   return K;
 }
 
-// the derived column of K: one pass of pg_expr_keys and the virtual dictionary's build (seg.mu NOT held)
+// the derived column of K: one pass of pg_expr_keys / pg_time_keys and the virtual dictionary's build (seg.mu NOT held)
 std::shared_ptr<Column> build_column(Segment& seg, const KeySpec& K, uint64_t* bytes) {
   auto col = std::make_shared<Column>();
   col->name = K.text;
-  col->data_type = PG_TYPE_DOUBLE;
+  col->data_type = K.time ? PG_TYPE_LONG : PG_TYPE_DOUBLE;
   col->has_dictionary = false;
   col->col_kind = PG_COL_RAW64;
-  col->val_type = PG_V_F64;
+  col->val_type = K.time ? PG_V_I64 : PG_V_F64;
   col->expr_operands = K.cols;
-  col->vdict = expression_virtual_dictionary(seg, K.text, K.args, bytes);
+  col->vdict = K.time ? time_virtual_dictionary(seg, K.text, K.targs, bytes) : expression_virtual_dictionary(seg, K.text, K.args, bytes);
   return col;
 }
 

@@ -212,6 +212,8 @@ void ensure_virtual_dictionary(Segment& seg, Column& c);            // pg_vdict.
 // ... and the virtual dictionary of a key column that is an expression (pg_vdict.hip): pg_expr_keys over all docs, then the steps a stored
 // raw DOUBLE column takes.  seg.mu is NOT needed (it reads registered columns only); `id_bytes`: the HBM the bit-packed ids keep.
 std::unique_ptr<Column> expression_virtual_dictionary(Segment& seg, const std::string& text, const PgExprArgs& args, uint64_t* id_bytes);
+// ... and of one that is a time-bucket transform: pg_time_keys over all docs, then the steps a stored raw LONG column takes
+std::unique_ptr<Column> time_virtual_dictionary(Segment& seg, const std::string& text, const PgTimeKeyArgs& args, uint64_t* id_bytes);
 int64_t vdict_value_of_key(uint64_t key, int kind, double* as_double);   // the value behind an order-preserving key (FLOAT / DOUBLE: IEEE double bits)
 double limbs_to_double(const int64_t* limbs, int n_limbs, int q);   // sum_j limbs[j] * 2^(32 j + q), correctly rounded (pg_plan.cpp)
 void segment_add_star_tree(Segment& seg, const pg_star_tree_desc& d);
@@ -395,7 +397,7 @@ std::shared_ptr<CompiledPlan> compile_plan(Segment& seg, const pg_filter_node* f
                                            const std::vector<ExprLeafSpec>* expr_leaves = nullptr);   // flags: of a filter-only plan (query == nullptr)
 // ---- arithmetic expressions as GROUP BY / DISTINCT keys (pg_exprkey.cpp) -------------------------------------------------------
 #define PG_MAX_DERIVED_KEYS 16   // derived key columns kept per segment
-#define PG_MAX_EXPR_KEYS 4       // expression keys of one query
+#define PG_MAX_EXPR_KEYS 4       // expression keys of one query, arithmetic and time-bucket ones together
 // Every entry point that plans a query opens one over it before anything else (execute_query, pg_query_supported): it checks the query's
 // expression keys under seg.mu (every refusal of such a key comes from here), builds the derived columns the segment does not hold WITHOUT
 // the lock, inserts them under it again, and keeps the query's columns alive and findable for the calling thread while it lives.

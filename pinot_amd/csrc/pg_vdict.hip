@@ -30,6 +30,7 @@
 #include "pg_vdict_key.h"
 
 void pg_expr_launch_keys(const PgExprArgs* args, uint64_t* keys, int grid, hipStream_t stream);   // pg_kernels_exprkey.hip
+void pg_time_launch_keys(const PgTimeKeyArgs* args, uint64_t* keys, int grid, hipStream_t stream);   // pg_kernels_timekey.hip
 
 namespace pg {
 namespace {
@@ -282,6 +283,22 @@ std::unique_ptr<Column> expression_virtual_dictionary(Segment& seg, const std::s
     PG_HIP(hipGetLastError());
   }
   return vdict_from_keys(seg, text, PG_TYPE_DOUBLE, PG_V_F64, 3, keys, nullptr, id_bytes);
+}
+
+// The virtual dictionary of a time-bucket key: pg_time_keys writes the docs' LONG keys, and from there on the transform is a raw LONG column.
+// The 8 B/doc of keys die with this call; the bit-packed ids and the distinct keys stay.  Runs WITHOUT seg.mu.
+std::unique_ptr<Column> time_virtual_dictionary(Segment& seg, const std::string& text, const PgTimeKeyArgs& args, uint64_t* id_bytes) {
+  use_device(seg.device);
+  const int64_t n = seg.total_docs;
+  DeviceBuffer keys;
+  if (n > 0) {
+    keys.alloc((size_t)n * 8);
+    const int64_t per_wg = 4 * PG_EXPR_PRED_WORDS;   // 64-doc words per workgroup and iteration (4 wavefronts of 256 threads)
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)device_cus(seg.device) * 8, (args.n_words + per_wg - 1) / per_wg));
+    pg_time_launch_keys(&args, keys.as<uint64_t>(), grid, nullptr);   // the stream the sort and the id kernels run on
+    PG_HIP(hipGetLastError());
+  }
+  return vdict_from_keys(seg, text, PG_TYPE_LONG, PG_V_I64, 1, keys, nullptr, id_bytes);
 }
 
 }  // namespace pg

@@ -438,24 +438,39 @@ class _Parser:
             raise SqlError(f"bad aggregation argument {t}")
         if self.peek() == ("op", "("):   # a function call: its name in lower case, without underscores (FunctionContext's canonical name)
             self.i += 1
-            args = [self.expression()]
+            name = t[1].lower().replace("_", "")
+            argument = self.time_argument if name in self._TIME else self.expression
+            args = [argument()]
             while self.peek() == ("op", ","):
                 self.i += 1
-                args.append(self.expression())
+                args.append(argument())
             self.expect_op(")")
-            return f"{t[1].lower().replace('_', '')}({','.join(args)})"
+            return f"{name}({','.join(args)})"
         return t[1]
+
+    # The time-bucket transforms: GROUP BY / DISTINCT keys such as dateTrunc('day', ts).  Their arguments other than the value are
+    # literals of any text (units, formats, time zones), printed single-quoted with their case kept; nowhere else is a non-numeric string literal
+    # an operand.
+    _TIME = frozenset(["timeconvert", "datetimeconvert", "datetrunc"]
+                      + ["toepoch" + u + v for u in ("seconds", "minutes", "hours", "days") for v in ("", "rounded", "bucket")])
+
+    def time_argument(self) -> str:
+        t = self.peek()
+        if t[0] == "str" and self.peek(1) in (("op", ","), ("op", ")")):
+            self.i += 1
+            return f"'{t[1]}'"
+        return self.expression()
 
     _ARITHMETIC = frozenset(("add", "sub", "mult", "div", "plus", "minus", "times", "divide"))
 
     def starts_expression(self) -> bool:
-        """Does an arithmetic expression start here, where a select item, a GROUP BY key or an ORDER BY expression is expected: one of the
-        eight function forms, a parenthesis, or an operand followed by an infix operator?"""
+        """Does an expression start here, where a select item, a GROUP BY key or an ORDER BY expression is expected: one of the eight
+        arithmetic function forms, a time-bucket transform, a parenthesis, or an operand followed by an infix operator?"""
         t, u = self.peek(), self.peek(1)
         if t == ("op", "("):
             return True
         if t[0] == "id" and u == ("op", "("):
-            return t[1].lower().replace("_", "") in self._ARITHMETIC
+            return t[1].lower().replace("_", "") in self._ARITHMETIC or t[1].lower().replace("_", "") in self._TIME
         if t[0] in ("id", "num"):
             return (u[0] == "op" and u[1] in self._INFIX) or (u[0] == "num" and u[1].startswith("-"))
         return False
