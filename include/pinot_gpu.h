@@ -206,7 +206,25 @@ typedef enum pg_agg_function {   /* AggregationFunctionType (subset named by nor
    * PG_PCTL_HBM_MAX_BYTES of counters (default 256 MiB) whose sort of every matching doc's key would exceed PG_PCTL_SORT_MAX_BYTES
    * (default 8 GiB).  p outside [0, 100] or NaN, or agg_params == NULL: PG_ERR_INVALID_ARGUMENT.  The star-tree route is never
    * taken for such a query; pg_result_merge / pg_result_all_reduce refuse its results (the lists merge by value on the Java side). */
-  PG_AGG_PERCENTILE = 16
+  PG_AGG_PERCENTILE = 16,
+  /* VAR_POP / VAR_SAMP / STDDEV_POP / STDDEV_SAMP (VarianceAggregationFunction.java; intermediate VarianceTuple(count, sum, m2)) over one
+   * single-value INT / LONG / FLOAT / DOUBLE column, dictionary-encoded or raw, read as getDoubleValuesSV reads it (an INT exact, a LONG
+   * (double) rounded first, a FLOAT widened exactly).  All four produce the same intermediate, PG_RESULT_VARIANCE_TUPLE; they differ in the
+   * final value — m2 / count (POP) or m2 / (count - 1) (SAMP), Math.sqrt of that for STDDEV, Double.NEGATIVE_INFINITY for count 0 and, for
+   * SAMP, count 1 — and in the result column's name.  The values are NOT the reference's docId-order doubles (it updates m2 doc by doc):
+   * count is exact, sum is the exact sum rounded once (what SUM returns), m2 is the exact sum x^2 - (sum x)^2 / n rounded once to
+   * nearest-even — order-free, bit-reproducible, 0.0 for n = 1, never negative, never -0.0.  Squares are held in a 192-bit window below the
+   * column's largest magnitude 2^E: values truncated below it leave |m2 - exact| < n (2^(2E - 191) + 2^(2E - 126)) before the rounding
+   * (pg_moments.h).  A query without GROUP BY whose filter matches no doc returns (0, 0.0, 0.0).
+   * Refused (PG_ERR_UNSUPPORTED, the Java plan answers): a STRING / BYTES or multi-value argument, an expression argument, a multi-value
+   * group-by column next to it, under PG_QUERY_FLAG_NULL_HANDLING an argument or group-by column that holds nulls, a group key space over
+   * 2^32, a FLOAT / DOUBLE column that holds a NaN or an infinity, more than 4 distinct argument columns in one query, a slot table beyond
+   * PG_VAR_HBM_MAX_BYTES (default 256 MiB).  The star-tree route is never taken for such a query; pg_result_merge /
+   * pg_result_all_reduce refuse its results (the Java side merges with VarianceTuple#apply). */
+  PG_AGG_VARPOP = 17,
+  PG_AGG_VARSAMP = 18,
+  PG_AGG_STDDEVPOP = 19,
+  PG_AGG_STDDEVSAMP = 20
 } pg_agg_function;
 
 typedef struct pg_agg_spec {
@@ -389,6 +407,8 @@ typedef enum pg_result_kind {
   PG_RESULT_HLL = 5,       /* HyperLogLog registers, m = 2^log2m bytes per group */
   PG_RESULT_VALUE_SET = 6, /* DISTINCTCOUNT over a raw (no-dictionary) INT / LONG / FLOAT / DOUBLE column: set of VALUES — the typed open-hash sets of
                               BaseDistinctAggregateAggregationFunction.java:325-380 (pg_result_set_sizes + pg_result_set_values_long / _double) */
+  PG_RESULT_VARIANCE_TUPLE = 8, /* VAR_POP / VAR_SAMP / STDDEV_POP / STDDEV_SAMP: VarianceTuple — pg_result_longs(r, agg, 0) the count,
+                              pg_result_doubles(r, agg, 0) the sum, pg_result_doubles(r, agg, 1) m2 */
   PG_RESULT_VALUE_COUNTS = 7 /* PERCENTILE: the group's DoubleArrayList as runs — pg_result_set_sizes gives the runs per group, pg_result_set_values_double
                               the runs' values (ascending under Double.compare within a group), pg_result_set_counts how often each occurs */
 } pg_result_kind;

@@ -314,6 +314,8 @@ public class GpuGroupByOperator extends BaseOperator<BaseResultsBlock> {
         return GpuResultObjects.rawValueSets(result, a, n, _segment, function);  // a raw column's values -> typed value Set (:325-380)
       case PinotGpu.RESULT_VALUE_COUNTS:
         return GpuResultObjects.doubleLists(result, a, n);                       // PERCENTILE: (value, count) runs -> DoubleArrayList (PercentileAggregationFunction.java:77-100)
+      case PinotGpu.RESULT_VARIANCE_TUPLE:
+        return GpuResultObjects.varianceTuples(result, a, n);                    // (count, sum, m2) -> VarianceTuple, the holder's value and the intermediate alike (VarianceAggregationFunction.java:66-74)
       default:
         return GpuResultObjects.hyperLogLogs(result, a, n, function);            // register bytes -> com.clearspring HyperLogLog (RegisterSet)
     }

@@ -225,6 +225,23 @@ public final class GpuResultObjects {
     return out;
   }
 
+  /** VAR_POP / VAR_SAMP / STDDEV_POP / STDDEV_SAMP (pg_result_kind PG_RESULT_VARIANCE_TUPLE): per group the function's VarianceTuple from the
+   *  library's three components — the count, the exact sum rounded once, the exact m2 rounded once.  Tuples of several segments merge with
+   *  VarianceTuple#apply (VarianceAggregationFunction#merge), as the reference's own do. */
+  public static Object[] varianceTuples(long result, int aggregation, int numGroups) {
+    long[] count = new long[numGroups];
+    double[] sum = new double[numGroups];
+    double[] m2 = new double[numGroups];
+    PinotGpu.resultLongs(result, aggregation, 0, count);
+    PinotGpu.resultDoubles(result, aggregation, 0, sum);
+    PinotGpu.resultDoubles(result, aggregation, 1, m2);
+    Object[] out = new Object[numGroups];
+    for (int g = 0; g < numGroups; g++) {
+      out[g] = new org.apache.pinot.segment.local.customobject.VarianceTuple(count[g], sum[g], m2[g]);
+    }
+    return out;
+  }
+
   /** One HyperLogLog per group from its 2^log2m register bytes. */
   public static Object[] hyperLogLogs(long result, int aggregation, int numGroups, AggregationFunction function) {
     int log2m = ((org.apache.pinot.core.query.aggregation.function.DistinctCountHLLAggregationFunction) function).getLog2m();

@@ -291,6 +291,11 @@ public final class NativeQuery implements AutoCloseable {
       case DISTINCTCOUNTHLLMV: return 15;
       // exact PERCENTILE only: the digest-based members of the family (TDigest, KLL, ...) are other types and stay with the Java plan
       case PERCENTILE: return f instanceof org.apache.pinot.core.query.aggregation.function.PercentileAggregationFunction ? 16 : -1;
+      // the second-moment statistics (pg_agg_function 17..20): one intermediate (VarianceTuple), four final values
+      case VARPOP: return f instanceof org.apache.pinot.core.query.aggregation.function.VarianceAggregationFunction ? 17 : -1;
+      case VARSAMP: return f instanceof org.apache.pinot.core.query.aggregation.function.VarianceAggregationFunction ? 18 : -1;
+      case STDDEVPOP: return f instanceof org.apache.pinot.core.query.aggregation.function.VarianceAggregationFunction ? 19 : -1;
+      case STDDEVSAMP: return f instanceof org.apache.pinot.core.query.aggregation.function.VarianceAggregationFunction ? 20 : -1;
       default: return -1;
     }
   }

@@ -37,10 +37,13 @@ FILTER_AND, FILTER_OR, FILTER_NOT, FILTER_PREDICATE, FILTER_CONSTANT_TRUE, FILTE
 PRED_EQ, PRED_NOT_EQ, PRED_IN, PRED_NOT_IN, PRED_RANGE, PRED_IS_NULL, PRED_IS_NOT_NULL = range(7)
 AGG_FUNCTIONS = {"COUNT": 0, "SUM": 1, "MIN": 2, "MAX": 3, "AVG": 4, "DISTINCTCOUNT": 5, "DISTINCTCOUNTHLL": 6,
                  "MINMAXRANGE": 7, "COUNTMV": 8, "SUMMV": 9, "MINMV": 10, "MAXMV": 11, "AVGMV": 12, "MINMAXRANGEMV": 13,
-                 "DISTINCTCOUNTMV": 14, "DISTINCTCOUNTHLLMV": 15, "PERCENTILE": 16}
+                 "DISTINCTCOUNTMV": 14, "DISTINCTCOUNTHLLMV": 15, "PERCENTILE": 16,
+                 "VARPOP": 17, "VARSAMP": 18, "STDDEVPOP": 19, "STDDEVSAMP": 20}
+VARIANCE_FUNCTIONS = ("VARPOP", "VARSAMP", "STDDEVPOP", "STDDEVSAMP")   # VarianceAggregationFunction: one intermediate, four final values
 MV_TO_SV_FUNCTION = {"COUNTMV": "COUNT", "SUMMV": "SUM", "MINMV": "MIN", "MAXMV": "MAX", "AVGMV": "AVG", "MINMAXRANGEMV": "MINMAXRANGE",
                      "DISTINCTCOUNTMV": "DISTINCTCOUNT", "DISTINCTCOUNTHLLMV": "DISTINCTCOUNTHLL"}
 RESULT_LONG, RESULT_DOUBLE, RESULT_AVG_PAIR, RESULT_MINMAX_PAIR, RESULT_DICTID_SET, RESULT_HLL, RESULT_VALUE_SET, RESULT_VALUE_COUNTS = range(8)
+RESULT_VARIANCE_TUPLE = 8   # VarianceTuple: result_longs(.., 0) the count, result_doubles(.., 0) the sum, result_doubles(.., 1) m2
 
 QUERY_FLAG_PROFILE = 0x1
 QUERY_FLAG_SKIP_STAR_TREE = 0x2

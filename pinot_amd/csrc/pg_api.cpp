@@ -45,6 +45,7 @@ static void knobs_read(Knobs& k) {
   k.pctl_sort_max_bytes = num("PG_PCTL_SORT_MAX_BYTES", (int64_t)8 << 30);
   k.expr_lds_max_slots = std::max<int64_t>(1, std::min<int64_t>(PG_EXPR_LDS_SLOTS, num("PG_EXPR_LDS_MAX_SLOTS", PG_EXPR_LDS_SLOTS)));
   k.expr_hbm_max_bytes = std::max<int64_t>(8, num("PG_EXPR_HBM_MAX_BYTES", (int64_t)256 << 20));
+  k.var_hbm_max_bytes = std::max<int64_t>(8, num("PG_VAR_HBM_MAX_BYTES", (int64_t)256 << 20));
   k.limit_prefix_min_docs = std::max<int64_t>(PG_WAVE_DOCS, num("PG_LIMIT_PREFIX_MIN_DOCS", (int64_t)1 << 20));
   k.oct_passes = str("PG_OCT_PASSES"); k.rccl_library = str("PG_RCCL_LIBRARY");
 }
@@ -274,6 +275,10 @@ int32_t pg_query_supported(pg_segment_t segment, const pg_query* query) {
       expression_check(segment->seg, *query);
       return;
     }
+    if (has_variance(*query)) {   // the checks of the variance path (and of a PERCENTILE next to it)
+      variance_check(segment->seg, *query);
+      return;
+    }
     if (has_percentile(*query)) {   // the checks of the percentile path; the ordinary part's plan is compiled by the execution
       percentile_check(segment->seg, *query);
       return;
@@ -322,6 +327,7 @@ int32_t pg_result_merge(pg_result_t dst, pg_result_t src) {
     if (dst->r->selection || src->r->selection) fail(PG_ERR_UNSUPPORTED, "selection results are merged by value (SelectionCombineOperator)");
     if (dst->r->percentile || src->r->percentile) fail(PG_ERR_UNSUPPORTED, "PERCENTILE results are merged by value (DoubleArrayList#addAll on the Java side)");
     if (dst->r->expression || src->r->expression) fail(PG_ERR_UNSUPPORTED, "results of aggregations over expressions are merged by value on the Java side (the scale of their exact sums differs per segment)");
+    if (dst->r->variance || src->r->variance) fail(PG_ERR_UNSUPPORTED, "results of variance aggregations are merged on the Java side (VarianceTuple#apply)");
     result_merge(*dst->r, *src->r);
   });
 }
@@ -332,6 +338,7 @@ int32_t pg_result_all_reduce(pg_result_t result, pg_comm_t comm) {
     if (result->r->selection) fail(PG_ERR_UNSUPPORTED, "selection results are merged by value (SelectionCombineOperator)");
     if (result->r->percentile) fail(PG_ERR_UNSUPPORTED, "PERCENTILE results are merged by value (DoubleArrayList#addAll on the Java side)");
     if (result->r->expression) fail(PG_ERR_UNSUPPORTED, "results of aggregations over expressions are merged by value on the Java side (the scale of their exact sums differs per segment)");
+    if (result->r->variance) fail(PG_ERR_UNSUPPORTED, "results of variance aggregations are merged on the Java side (VarianceTuple#apply)");
     result_all_reduce(*result->r, *comm->c);
   });
 }

@@ -79,6 +79,10 @@ const char* function_name(int32_t fn) {   // AggregationFunctionType#getName().t
     case PG_AGG_DISTINCTCOUNTMV: return "distinctcountmv";
     case PG_AGG_DISTINCTCOUNTHLLMV: return "distinctcounthllmv";
     case PG_AGG_PERCENTILE: return "percentile";
+    case PG_AGG_VARPOP: return "varpop";   // BaseSingleInputAggregationFunction#getResultColumnName: getType().getName().toLowerCase() + "(" + column + ")"
+    case PG_AGG_VARSAMP: return "varsamp";
+    case PG_AGG_STDDEVPOP: return "stddevpop";
+    case PG_AGG_STDDEVSAMP: return "stddevsamp";
     default: fail(PG_ERR_INTERNAL, "aggregation function %d has no name", fn);
   }
   return "";
@@ -309,6 +313,14 @@ std::vector<uint8_t> result_data_table_v4(const Result& r) {
           p.i32((int32_t)total);
           for (int32_t e = 0; e < n; e++) for (int64_t k = 0; k < ar.l[0][at + (size_t)e]; k++) p.f64(ar.d[0][at + (size_t)e]);
           object(3, p);
+          break;
+        }
+        case PG_RESULT_VARIANCE_TUPLE: {   // VarianceTuple#toBytes: long count, double sum, double m2 (ObjectSerDeUtils type 33)
+          Out p;
+          p.i64(ar.l[0][(size_t)i]);
+          p.f64(ar.d[0][(size_t)i]);
+          p.f64(ar.d[1][(size_t)i]);
+          object(33, p);
           break;
         }
         default: fail(PG_ERR_INTERNAL, "result kind %d in a data table", ar.kind);

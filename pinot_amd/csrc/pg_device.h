@@ -475,7 +475,7 @@ __device__ __forceinline__ uint32_t pg_fixed_bit_id(const uint8_t* data, int32_t
 }
 __device__ __forceinline__ uint32_t pg_fixed_bit_id_at(const PgDistinctCol& c, uint32_t doc) { return pg_fixed_bit_id(c.data, c.bits, doc); }
 #endif
-// What the side passes' kernels (PERCENTILE, expressions) scan: the filter's match words and the group columns whose ids form the group key.
+// What the side passes' kernels (PERCENTILE, expressions, the variance family) scan: the filter's match words and the group columns whose ids form the group key.
 // The first member of their arguments; the host fills it in one place (side_scan_fill, pg_exec_sidepass.hip).
 struct PgGroupScan {
   const uint64_t* match;       // the filter's match words (bit b of word w is doc 64 w + b); NULL: every doc below n_docs matches
@@ -622,6 +622,29 @@ struct PgExprArgs {
   PgExprDesc exprs[PG_EXPR_MAX_EXPRS];
   int64_t ident[PG_EXPR_MAX_SLOTS];   // per slot of a row: 0 (SUM limbs, count), INT64_MAX (MIN), INT64_MIN (MAX)
   pg_expr_step steps[PG_EXPR_MAX_EXPRS * PG_EXPR_MAX_OPS];
+};
+// ---- VAR_POP / VAR_SAMP / STDDEV_POP / STDDEV_SAMP (pg_kernels_var.hip) -------------------------------------------------------------
+// One accumulation pass for all variance aggregations of a query: per matching doc the group key, then the group's 64-bit slots — a table
+// [G][slots] of int64, every slot a sum (identity 0).  Slot 0 is the doc count; every distinct argument column follows with the exact power
+// sums of pg_moments.h: PG_VAR_INT_SLOTS slots on the integer path (INT columns), PG_VAR_DBL_SLOTS on the double path.
+#include "pg_moments.h"
+#define PG_VAR_MAX_COLS 4        // distinct argument columns of one query
+#define PG_VAR_MAX_SLOTS (1 + PG_VAR_MAX_COLS * PG_VAR_DBL_SLOTS)
+#define PG_VAR_LDS_SLOTS 16384   // 128 KiB of the CU's 160 KiB: one persistent workgroup per CU, as pg_expr_lds
+struct PgVarCol {
+  PgValueSrc src;
+  int32_t is_int;                // the integer path (wave-uniform)
+  int32_t first_slot;            // the column's first slot within the group's row
+  int32_t q1, q2;                // double path: the scales of the sum's and the squares' digits
+};
+struct PgVarArgs {
+  PgGroupScan scan;            // match words and group columns
+  int32_t n_cols;
+  int32_t slots;               // slots per group
+  uint64_t n_groups;           // G (<= 2^32)
+  uint64_t n_slots;            // G x slots
+  int64_t* table;              // [G][slots] in HBM, zeroed by the caller
+  PgVarCol cols[PG_VAR_MAX_COLS];
 };
 // a time-bucket transform as a key (pg_kernels_timekey.hip): the value column and the normal form, wave-uniform kernel arguments
 struct PgTimeKeyArgs {

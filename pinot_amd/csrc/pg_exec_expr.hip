@@ -53,6 +53,10 @@ const char* function_text(int32_t fn) {
     case PG_AGG_MINMAXRANGEMV: return "MINMAXRANGEMV";
     case PG_AGG_DISTINCTCOUNTMV: return "DISTINCTCOUNTMV";
     case PG_AGG_DISTINCTCOUNTHLLMV: return "DISTINCTCOUNTHLLMV";
+    case PG_AGG_VARPOP: return "VAR_POP";
+    case PG_AGG_VARSAMP: return "VAR_SAMP";
+    case PG_AGG_STDDEVPOP: return "STDDEV_POP";
+    case PG_AGG_STDDEVSAMP: return "STDDEV_SAMP";
     default: return "this aggregation function";
   }
 }
@@ -229,6 +233,7 @@ void expression_check(Segment& seg, const pg_query& q) {
   (void)expr_plan(seg, q, false);
   SideBaseQuery B;   // ... and what the ordinary part refuses
   side_base_query(q, is_expression_agg, kBaseClears, B);
+  if (has_variance(B.q)) { variance_check(seg, B.q); return; }
   if (has_percentile(B.q)) { percentile_check(seg, B.q); return; }
   check_null_handling(seg, B.q);
   (void)get_plan(seg, B.q.filter, &B.q);

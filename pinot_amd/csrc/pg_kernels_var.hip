@@ -1,0 +1,185 @@
+// VAR_POP / VAR_SAMP / STDDEV_POP / STDDEV_SAMP on the device (VarianceAggregationFunction under pinot-core/.../aggregation/function/, its
+// intermediate VarianceTuple(count, sum, m2)).  The reference updates m2 doc by doc in docId order; here every matching doc adds the exact
+// integer digits of x and of x^2 (pg_moments.h) to the int64 slots of its group, and the host forms m2 = sum x^2 - (sum x)^2 / n in exact
+// integer arithmetic, rounded once (pg_exec_var.hip).  Integer additions commute: the result does not depend on the tier, the grid or the
+// order of the atomics.
+//   pg_var_reg   no GROUP BY: the row stays in registers (a digit is below 2^32 and a segment has < 2^31 docs: no int64 overflows), one
+//                reduction across the wavefront and one global atomic per slot at the end
+//   pg_var_lds   up to PG_VAR_LDS_SLOTS slots: one persistent workgroup per CU, 64-bit LDS atomics, zero digits skipped, one flush of the
+//                touched slots
+//   pg_var_hbm   beyond that: global 64-bit atomics
+// All three walk the filter's match words (none: every doc) as pg_expr_* / pg_pctl_* do: a wavefront takes kWordsPerWave 64-doc words per
+// iteration, lane = doc.  The columns and their type split (integer path or digits of a double) are kernel arguments: wave-uniform, scalar
+// branches; the register tier indexes its accumulators statically — no scratch (the resource log of this file is checked by
+// tests/test_gpu_variance.py).  A plain tile loop, not a software pipeline.  The table is zeroed by a memset and its admitted rows are
+// gathered by pg_expr_gather (pg_kernels_expr.hip).  Kernel names are stable; the executor reports the tier's (pg_exec_var.hip).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "pg_internal.hpp"
+#include "pg_fixed_point.h"
+#include "pg_moments.h"
+#include "pg_expr_device.h"
+
+#define DEVFN __device__ __forceinline__
+
+namespace {
+
+constexpr int kWordsPerWave = 4;
+
+DEVFN int64_t wave_sum_i64(int64_t v) {
+  for (int off = 32; off > 0; off >>= 1) v += (int64_t)__shfl_xor((long long)v, off);
+  return v;
+}
+
+// an INT column's value: raw big-endian, or through its INT dictionary
+DEVFN int64_t var_load_int(const PgValueSrc& S, uint32_t doc) {
+  if (S.col_kind == PG_COL_FIXED_BIT) return (int64_t)reinterpret_cast<const int32_t*>(S.dict)[pg_fixed_bit_id(S.data, S.bits, doc)];   // wave-uniform
+  return (int64_t)(int32_t)__builtin_bswap32(reinterpret_cast<const uint32_t*>(S.data)[doc]);
+}
+
+template <typename Ptr>
+DEVFN void var_add(Ptr slot, int64_t d) {
+  if (d) atomicAdd(reinterpret_cast<unsigned long long*>(slot), (unsigned long long)d);
+}
+
+// the tiers with a table: `row0` is the table's first slot — the workgroup's copy in LDS, or the table in HBM
+template <typename Ptr>
+DEVFN void var_update(const PgVarArgs& a, Ptr row0, uint32_t doc) {
+  const uint64_t g = pg_scan_group_key(a.scan, doc);
+  if (g >= a.n_groups) return;   // (ids below their cardinalities never are)
+  Ptr row = row0 + g * (uint64_t)a.slots;
+  atomicAdd(reinterpret_cast<unsigned long long*>(&row[0]), 1ULL);
+#pragma unroll 1
+  for (int c = 0; c < a.n_cols; c++) {   // wave-uniform
+    const PgVarCol& C = a.cols[c];
+    Ptr s = row + C.first_slot;
+    if (C.is_int) {
+      const int64_t x = var_load_int(C.src, doc);
+      const int64_t sq = x * x;   // <= 2^62
+      var_add(&s[0], x);
+      var_add(&s[1], pg_long_digit(sq, 0));
+      var_add(&s[2], pg_long_digit(sq, 1));
+    } else {
+      const double v = expr_load(C.src, doc);
+#pragma unroll
+      for (int l = 0; l < PG_VAR_SUM_LIMBS; l++) var_add(&s[l], pg_fx_digit(v, C.q1, l));
+#pragma unroll
+      for (int l = 0; l < PG_VAR_SQ_LIMBS; l++) var_add(&s[PG_VAR_SUM_LIMBS + l], (int64_t)pg_sq_digit(v, C.q2, l));
+    }
+  }
+}
+
+template <bool LDS>
+DEVFN void var_table_body(const PgVarArgs& a) {
+  extern __shared__ int64_t s_tab[];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int waves = blockDim.x >> 6;
+  if (LDS) {
+    for (uint32_t i = threadIdx.x; i < (uint32_t)a.n_slots; i += blockDim.x) s_tab[i] = 0;
+    __syncthreads();
+  }
+  const int64_t stride = (int64_t)gridDim.x * waves * kWordsPerWave;
+  for (int64_t w0 = ((int64_t)blockIdx.x * waves + wave) * kWordsPerWave; w0 < a.scan.n_words; w0 += stride) {
+#pragma unroll 1
+    for (int u = 0; u < kWordsPerWave; u++) {
+      const int64_t w = w0 + u;
+      if (w >= a.scan.n_words) break;
+      const uint64_t m = pg_scan_match_word(a.scan, w);
+      if (m == 0) continue;   // a word without a match costs one scalar load
+      if ((m >> lane) & 1) {
+        if (LDS) var_update(a, s_tab, (uint32_t)(w * 64 + lane));
+        else var_update(a, a.table, (uint32_t)(w * 64 + lane));
+      }
+    }
+  }
+  if (LDS) {
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < (uint32_t)a.n_slots; i += blockDim.x) {   // only the touched slots
+      const int64_t v = s_tab[i];
+      if (v) atomicAdd(reinterpret_cast<unsigned long long*>(a.table + i), (unsigned long long)v);
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" __global__ void __launch_bounds__(512) pg_var_lds(const PgVarArgs a) { var_table_body<true>(a); }
+extern "C" __global__ void __launch_bounds__(256) pg_var_hbm(const PgVarArgs a) { var_table_body<false>(a); }
+
+// No GROUP BY: one row.  Every lane keeps the row in registers over all its docs; one reduction across the wavefront and one global atomic
+// per slot at the end.
+extern "C" __global__ void __launch_bounds__(256) pg_var_reg(const PgVarArgs a) {
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int waves = blockDim.x >> 6;
+  int64_t acc[PG_VAR_MAX_COLS][PG_VAR_DBL_SLOTS], count = 0;
+#pragma unroll
+  for (int c = 0; c < PG_VAR_MAX_COLS; c++) {
+#pragma unroll
+    for (int l = 0; l < PG_VAR_DBL_SLOTS; l++) acc[c][l] = 0;
+  }
+  const int64_t stride = (int64_t)gridDim.x * waves * kWordsPerWave;
+  for (int64_t w0 = ((int64_t)blockIdx.x * waves + wave) * kWordsPerWave; w0 < a.scan.n_words; w0 += stride) {
+#pragma unroll 1
+    for (int u = 0; u < kWordsPerWave; u++) {
+      const int64_t w = w0 + u;
+      if (w >= a.scan.n_words) break;
+      const uint64_t m = pg_scan_match_word(a.scan, w);
+      if (m == 0) continue;
+      if (!((m >> lane) & 1)) continue;
+      const uint32_t doc = (uint32_t)(w * 64 + lane);
+      count++;
+#pragma unroll
+      for (int c = 0; c < PG_VAR_MAX_COLS; c++) {
+        if (c < a.n_cols) {   // wave-uniform
+          const PgVarCol& C = a.cols[c];
+          if (C.is_int) {
+            const int64_t x = var_load_int(C.src, doc);
+            const int64_t sq = x * x;
+            acc[c][0] += x;
+            acc[c][1] += pg_long_digit(sq, 0);
+            acc[c][2] += pg_long_digit(sq, 1);
+          } else {
+            const double v = expr_load(C.src, doc);
+#pragma unroll
+            for (int l = 0; l < PG_VAR_SUM_LIMBS; l++) acc[c][l] += pg_fx_digit(v, C.q1, l);
+#pragma unroll
+            for (int l = 0; l < PG_VAR_SQ_LIMBS; l++) acc[c][PG_VAR_SUM_LIMBS + l] += (int64_t)pg_sq_digit(v, C.q2, l);
+          }
+        }
+      }
+    }
+  }
+  {
+    const int64_t v = wave_sum_i64(count);
+    if (lane == 0 && v) atomicAdd(reinterpret_cast<unsigned long long*>(a.table), (unsigned long long)v);
+  }
+#pragma unroll
+  for (int c = 0; c < PG_VAR_MAX_COLS; c++) {
+    if (c < a.n_cols) {
+      const PgVarCol& C = a.cols[c];
+#pragma unroll
+      for (int l = 0; l < PG_VAR_DBL_SLOTS; l++) {
+        if (C.is_int && l >= PG_VAR_INT_SLOTS) break;   // wave-uniform
+        const int64_t v = wave_sum_i64(acc[c][l]);
+        if (lane == 0 && v) atomicAdd(reinterpret_cast<unsigned long long*>(a.table + C.first_slot + l), (unsigned long long)v);
+      }
+    }
+  }
+}
+
+// ---- launcher (pg_exec_var.hip) ---------------------------------------------------------------------------------------------------------------
+// tier: 0 pg_var_reg, 1 pg_var_lds, 2 pg_var_hbm
+void pg_var_launch_pass(const PgVarArgs* args, int tier, int grid, hipStream_t stream) {
+  const PgVarArgs a = *args;
+  if (tier == 1) {
+    PG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(pg_var_lds), hipFuncAttributeMaxDynamicSharedMemorySize, PG_VAR_LDS_SLOTS * 8));
+    hipLaunchKernelGGL(pg_var_lds, dim3(grid), dim3(512), (size_t)a.n_slots * 8, stream, a);
+  } else if (tier == 2) {
+    hipLaunchKernelGGL(pg_var_hbm, dim3(grid), dim3(256), 0, stream, a);
+  } else {
+    hipLaunchKernelGGL(pg_var_reg, dim3(grid), dim3(256), 0, stream, a);
+  }
+}

@@ -437,6 +437,14 @@ class ResultsBlock:
                 api.call("result_set_values_double", h, a, values.ctypes.data, total)
                 api.call("result_set_counts", h, a, counts.ctypes.data, total)
                 rb.arrays.append((k, sizes, values[:total], counts[:total]))
+            elif k == capi.RESULT_VARIANCE_TUPLE:   # VAR_POP / VAR_SAMP / STDDEV_POP / STDDEV_SAMP: VarianceTuple(count, sum, m2)
+                n = np.zeros(ng, dtype=np.int64)
+                s = np.zeros(ng, dtype=np.float64)
+                m2 = np.zeros(ng, dtype=np.float64)
+                api.call("result_longs", h, a, 0, n.ctypes.data, ng)
+                api.call("result_doubles", h, a, 0, s.ctypes.data, ng)
+                api.call("result_doubles", h, a, 1, m2.ctypes.data, ng)
+                rb.arrays.append((k, n, s, m2))
             elif k == capi.RESULT_HLL:
                 m = 1 << (spec.log2m or 8)
                 regs = np.empty(max(ng * m, 1), dtype=np.uint8)
@@ -528,6 +536,8 @@ class ResultsBlock:
                         col.append(frozenset(arr[2][pos:pos + sz].tolist()))
                         pos += sz
                     cols.append(col)
+                elif k == capi.RESULT_VARIANCE_TUPLE:   # (count, sum, m2) per group
+                    cols.append([(int(n), float(s), float(m2)) for n, s, m2 in zip(arr[1], arr[2], arr[3])])
                 elif k == capi.RESULT_VALUE_COUNTS:   # (values, counts) per group
                     col, pos = [], 0
                     for sz in arr[1]:
@@ -600,6 +610,27 @@ def percentile_final(runs, p: float) -> float:
     return float(values[int(np.searchsorted(np.cumsum(counts), rank, side="right"))])
 
 
+def variance_final(function: str, t) -> float:
+    """VarianceAggregationFunction#extractFinalResult over the tuple (count, sum, m2): m2 / count for the population forms, m2 / (count - 1)
+    for the sample forms, Math.sqrt of that for STDDEV; Double.NEGATIVE_INFINITY for count 0 and, for the sample forms, count 1."""
+    n, _, m2 = t
+    sample = function in ("VARSAMP", "STDDEVSAMP")
+    if n == 0 or (sample and n == 1):
+        return float("-inf")
+    v = m2 / (n - 1) if sample else m2 / n
+    return math.sqrt(v) if function in ("STDDEVPOP", "STDDEVSAMP") else v
+
+
+def variance_merge(a, b):
+    """VarianceTuple#apply(VarianceTuple): `b` merged into `a` (what the Java side does with the tuples of two segments)."""
+    if b[0] == 0:
+        return a
+    n, s, m2 = a
+    avg = 0.0 if n == 0 else s / n
+    delta = (b[1] / b[0]) - avg
+    return (n + b[0], s + b[1], m2 + (b[2] + delta * delta * b[0] * n / (b[0] + n)))
+
+
 def hll_merge(a: bytes, b: bytes) -> bytes:
     return bytes(max(x, y) for x, y in zip(a, b))
 
@@ -625,6 +656,8 @@ def merge_intermediate(function: str, a, b):
         return a | b
     if function == "DISTINCTCOUNTHLL":
         return hll_merge(a, b)
+    if function in capi.VARIANCE_FUNCTIONS:
+        return variance_merge(a, b)
     raise ValueError(function)
 
 
@@ -639,6 +672,8 @@ def extract_final(function: str, v):
         return len(v)
     if function == "DISTINCTCOUNTHLL":
         return hll_cardinality(v)
+    if function in capi.VARIANCE_FUNCTIONS:
+        return variance_final(function, v)
     return v
 
 

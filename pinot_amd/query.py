@@ -127,7 +127,10 @@ class QueryContext:
         """(kind, index, ascending) per ORDER BY expression as TableResizer resolves them (TableResizer.java:129-161): a group-by expression
         or an aggregation of the select list; None when some expression is neither (post-aggregations, literals: not carried by the ABI)."""
         out = []
-        norm = lambda t: re.sub(r"\s+", "", t).upper()   # noqa: E731
+        def norm(t):
+            t = re.sub(r"\s+", "", t).upper()
+            head, paren, rest = t.partition("(")   # VAR_POP(x) names the aggregation VARPOP(x): AggregationFunctionType strips underscores
+            return variance_function_name(head) + paren + rest if paren and variance_function_name(head) else t
         aggs = [norm(f"{a.function}({a.column or '*'}{',' + str(a.log2m) if a.log2m else ''})") for a in self.aggregations]
         pctl = [(a.column, a.percentile) if a.function == "PERCENTILE" else None for a in self.aggregations]
         expr_aggs = {}   # (function, canonical text) of the aggregations over expressions -> the first one's index
@@ -151,6 +154,13 @@ class QueryContext:
             else:
                 return None
         return out
+
+
+def variance_function_name(fn: str):
+    """VARPOP / VARSAMP / STDDEVPOP / STDDEVSAMP for any spelling of them (VAR_POP, stddev_samp, STD_DEV_POP: AggregationFunctionType
+    strips underscores and ignores case), else None."""
+    name = fn.replace("_", "").upper()
+    return name if name in capi.VARIANCE_FUNCTIONS else None
 
 
 _PERCENTILE_LEGACY = re.compile(r"^PERCENTILE(\d+)$")
@@ -502,7 +512,7 @@ class _Parser:
         if t[0] != "id":
             raise SqlError(f"bad select item {t}")
         if self.peek() == ("op", "("):
-            fn = t[1].upper()
+            fn = variance_function_name(t[1]) or t[1].upper()
             self.i += 1
             if self.peek() == ("op", "*") and self.peek(1) == ("op", ")"):
                 self.i += 1
