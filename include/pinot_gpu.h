@@ -224,7 +224,30 @@ typedef enum pg_agg_function {   /* AggregationFunctionType (subset named by nor
   PG_AGG_VARPOP = 17,
   PG_AGG_VARSAMP = 18,
   PG_AGG_STDDEVPOP = 19,
-  PG_AGG_STDDEVSAMP = 20
+  PG_AGG_STDDEVSAMP = 20,
+  /* FIRSTWITHTIME(x, t, 'T') / LASTWITHTIME(x, t, 'T') with T in INT, LONG, FLOAT, DOUBLE (any case): the value of x at the matching doc with
+   * the smallest / greatest time t; among docs tied at that time the GREATEST docId wins, for FIRST and LAST alike
+   * (LastWithTimeAggregationFunction.java:104-117,194-199 and FirstWithTimeAggregationFunction.java:103-116,198-203 compare with >= / <= in
+   * docId order).  The intermediate is ValueLongPair(value, time), PG_RESULT_VALUE_TIME_PAIR, bit for bit the reference's: the winner is the
+   * maximum of a total order.
+   * AGGREGATIONS WITH MORE THAN ONE ARGUMENT carry their ARGUMENT LIST in pg_agg_spec.column, as getResultColumnName prints it between the
+   * parentheses — column arguments first, literal arguments single-quoted, separated by commas at depth 0 ("x,t,'DOUBLE'"); blanks around
+   * an argument are ignored.  This is the general form; a later function with two column arguments adopts it unchanged.  A wrong number of
+   * arguments, a third argument that is no quoted literal or names no data type: PG_ERR_INVALID_ARGUMENT.
+   * t is read as getLongValuesSV reads it: a single-value INT or LONG column, dictionary-encoded or raw.  x is a single-value INT / LONG /
+   * FLOAT / DOUBLE column, dictionary-encoded or raw, read as get<T>ValuesSV of the DECLARED type reads it — a Java primitive conversion of
+   * the stored value ((int) of a double saturates and maps NaN to 0, (int) of a long keeps the low 32 bits, (float) of a double rounds
+   * once); a FLOAT / DOUBLE read as its own type keeps its bits (NaN payloads, -0.0).  Long.MIN_VALUE and Long.MAX_VALUE are ordinary times.
+   * A query without GROUP BY whose filter matches no doc returns the function's default pair: the value Integer.MIN_VALUE / Long.MIN_VALUE /
+   * Float.NaN / Double.NaN, the time Long.MIN_VALUE (LAST) / Long.MAX_VALUE (FIRST).
+   * Refused (PG_ERR_UNSUPPORTED, the Java plan answers): a declared type other than the four ('BOOLEAN', 'STRING', ...), a STRING / BYTES or
+   * multi-value x or t, a FLOAT / DOUBLE t, an argument that is an expression, a multi-value group-by column next to it, under
+   * PG_QUERY_FLAG_NULL_HANDLING an x, t or group-by column that holds nulls, a group key space over 2^32, more than 4 distinct (time column,
+   * direction) pairs or 8 such aggregations in one query, a table beyond PG_WT_HBM_MAX_BYTES (default 256 MiB).  The star-tree route is
+   * never taken for such a query; pg_result_merge / pg_result_all_reduce refuse its results (the Java side merges with the functions' own
+   * merge). */
+  PG_AGG_FIRSTWITHTIME = 21,
+  PG_AGG_LASTWITHTIME = 22
 } pg_agg_function;
 
 typedef struct pg_agg_spec {
@@ -236,7 +259,8 @@ typedef struct pg_agg_spec {
                              "add(column1,column9)", "mult(price,'1.5')" — a column name cannot contain '(', so an argument holding one is
                              an expression.  At most 15 operations and 8 distinct columns per expression, 4 distinct expressions per query
                              (PG_ERR_UNSUPPORTED beyond); malformed text is PG_ERR_INVALID_ARGUMENT.  Evaluated in IEEE double, one rounded
-                             operation at a time in the reference's argument order; results that carry one are not merged in the library. */
+                             operation at a time in the reference's argument order; results that carry one are not merged in the library.
+                             FIRSTWITHTIME / LASTWITHTIME: the argument list, "x,t,'DOUBLE'" (see PG_AGG_FIRSTWITHTIME). */
 } pg_agg_spec;
 
 /* One ORDER BY expression of a group-by query, as TableResizer resolves it (pinot-core/.../core/data/table/TableResizer.java:129-161):
@@ -409,6 +433,9 @@ typedef enum pg_result_kind {
                               BaseDistinctAggregateAggregationFunction.java:325-380 (pg_result_set_sizes + pg_result_set_values_long / _double) */
   PG_RESULT_VARIANCE_TUPLE = 8, /* VAR_POP / VAR_SAMP / STDDEV_POP / STDDEV_SAMP: VarianceTuple — pg_result_longs(r, agg, 0) the count,
                               pg_result_doubles(r, agg, 0) the sum, pg_result_doubles(r, agg, 1) m2 */
+  PG_RESULT_VALUE_TIME_PAIR = 9, /* FIRSTWITHTIME / LASTWITHTIME: ValueLongPair — pg_result_longs(r, agg, 0) the time; pg_result_longs(r, agg, 1)
+                              the value of a declared INT / LONG (for a declared FLOAT / DOUBLE: its raw IEEE bits, a FLOAT's 32 zero-extended);
+                              pg_result_doubles(r, agg, 0) the value of a declared FLOAT / DOUBLE (a FLOAT widened exactly) */
   PG_RESULT_VALUE_COUNTS = 7 /* PERCENTILE: the group's DoubleArrayList as runs — pg_result_set_sizes gives the runs per group, pg_result_set_values_double
                               the runs' values (ascending under Double.compare within a group), pg_result_set_counts how often each occurs */
 } pg_result_kind;

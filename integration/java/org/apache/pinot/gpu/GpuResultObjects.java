@@ -242,6 +242,36 @@ public final class GpuResultObjects {
     return out;
   }
 
+  /** FIRSTWITHTIME / LASTWITHTIME (pg_result_kind PG_RESULT_VALUE_TIME_PAIR): per group the function's ValueLongPair of the declared type —
+   *  the concrete subclass tells it — from the library's (value, time).  Pairs of several segments merge with the functions' own merge. */
+  public static Object[] valueTimePairs(long result, int aggregation, int numGroups, AggregationFunction function) {
+    long[] time = new long[numGroups];
+    PinotGpu.resultLongs(result, aggregation, 0, time);
+    Object[] out = new Object[numGroups];
+    boolean isFloat = function instanceof org.apache.pinot.core.query.aggregation.function.FirstFloatValueWithTimeAggregationFunction
+        || function instanceof org.apache.pinot.core.query.aggregation.function.LastFloatValueWithTimeAggregationFunction;
+    boolean isDouble = function instanceof org.apache.pinot.core.query.aggregation.function.FirstDoubleValueWithTimeAggregationFunction
+        || function instanceof org.apache.pinot.core.query.aggregation.function.LastDoubleValueWithTimeAggregationFunction;
+    if (isFloat || isDouble) {
+      double[] value = new double[numGroups];
+      PinotGpu.resultDoubles(result, aggregation, 0, value);
+      for (int g = 0; g < numGroups; g++) {
+        out[g] = isFloat ? new org.apache.pinot.segment.local.customobject.FloatLongPair((float) value[g], time[g])   // widened exactly: the cast is exact
+            : new org.apache.pinot.segment.local.customobject.DoubleLongPair(value[g], time[g]);
+      }
+      return out;
+    }
+    boolean isLong = function instanceof org.apache.pinot.core.query.aggregation.function.FirstLongValueWithTimeAggregationFunction
+        || function instanceof org.apache.pinot.core.query.aggregation.function.LastLongValueWithTimeAggregationFunction;
+    long[] value = new long[numGroups];
+    PinotGpu.resultLongs(result, aggregation, 1, value);
+    for (int g = 0; g < numGroups; g++) {
+      out[g] = isLong ? new org.apache.pinot.segment.local.customobject.LongLongPair(value[g], time[g])
+          : new org.apache.pinot.segment.local.customobject.IntLongPair((int) value[g], time[g]);
+    }
+    return out;
+  }
+
   /** One HyperLogLog per group from its 2^log2m register bytes. */
   public static Object[] hyperLogLogs(long result, int aggregation, int numGroups, AggregationFunction function) {
     int log2m = ((org.apache.pinot.core.query.aggregation.function.DistinctCountHLLAggregationFunction) function).getLog2m();

@@ -94,6 +94,15 @@ public final class NativeQuery implements AutoCloseable {
     for (AggregationFunction f : aggs) {
       int fn = function(f);
       List<ExpressionContext> args = f.getInputExpressions();
+      if (fn == 21 || fn == 22) {   // PG_AGG_FIRSTWITHTIME / PG_AGG_LASTWITHTIME: the argument list "x,t,'TYPE'" in pg_agg_spec.column
+        String list = withTimeArguments(f, args);
+        if (list == null) {
+          return null;
+        }
+        b.putInt(fn).putInt(0);
+        putString(b, list);
+        continue;
+      }
       if (fn < 0 || args.size() > 1) {
         return null;
       }
@@ -270,6 +279,39 @@ public final class NativeQuery implements AutoCloseable {
     }
   }
 
+  /** FIRSTWITHTIME / LASTWITHTIME: the argument list as getResultColumnName prints it between the parentheses — the value column, the time
+   *  column (getInputExpressions().get(1)), the declared type quoted; the type comes from the concrete subclass.  Null for an argument that
+   *  is no column and for the Boolean / String variants (the Java plan answers). */
+  private static String withTimeArguments(AggregationFunction f, List<ExpressionContext> args) {
+    String type = withTimeType(f);
+    if (type == null || args.size() != 2 || args.get(0).getType() != ExpressionContext.Type.IDENTIFIER
+        || args.get(1).getType() != ExpressionContext.Type.IDENTIFIER) {
+      return null;
+    }
+    return args.get(0).getIdentifier() + "," + args.get(1).getIdentifier() + ",'" + type + "'";
+  }
+
+  private static String withTimeType(AggregationFunction f) {
+    if (f instanceof org.apache.pinot.core.query.aggregation.function.FirstIntValueWithTimeAggregationFunction
+        || f instanceof org.apache.pinot.core.query.aggregation.function.LastIntValueWithTimeAggregationFunction) {
+      // (a declared BOOLEAN builds the Int class with its boolean flag set: it keeps its own name through getResultColumnName)
+      return f.getResultColumnName().toUpperCase().endsWith("'BOOLEAN')") ? null : "INT";
+    }
+    if (f instanceof org.apache.pinot.core.query.aggregation.function.FirstLongValueWithTimeAggregationFunction
+        || f instanceof org.apache.pinot.core.query.aggregation.function.LastLongValueWithTimeAggregationFunction) {
+      return "LONG";
+    }
+    if (f instanceof org.apache.pinot.core.query.aggregation.function.FirstFloatValueWithTimeAggregationFunction
+        || f instanceof org.apache.pinot.core.query.aggregation.function.LastFloatValueWithTimeAggregationFunction) {
+      return "FLOAT";
+    }
+    if (f instanceof org.apache.pinot.core.query.aggregation.function.FirstDoubleValueWithTimeAggregationFunction
+        || f instanceof org.apache.pinot.core.query.aggregation.function.LastDoubleValueWithTimeAggregationFunction) {
+      return "DOUBLE";
+    }
+    return null;   // FirstStringValueWithTime... / LastStringValueWithTime...
+  }
+
   private static int function(AggregationFunction f) {
     switch (f.getType()) {
       case COUNT: return 0;
@@ -296,6 +338,11 @@ public final class NativeQuery implements AutoCloseable {
       case VARSAMP: return f instanceof org.apache.pinot.core.query.aggregation.function.VarianceAggregationFunction ? 18 : -1;
       case STDDEVPOP: return f instanceof org.apache.pinot.core.query.aggregation.function.VarianceAggregationFunction ? 19 : -1;
       case STDDEVSAMP: return f instanceof org.apache.pinot.core.query.aggregation.function.VarianceAggregationFunction ? 20 : -1;
+      // the latest / earliest value per key (pg_agg_function 21 / 22): INT / LONG / FLOAT / DOUBLE variants only (withTimeType)
+      case FIRSTWITHTIME:
+        return f instanceof org.apache.pinot.core.query.aggregation.function.FirstWithTimeAggregationFunction && withTimeType(f) != null ? 21 : -1;
+      case LASTWITHTIME:
+        return f instanceof org.apache.pinot.core.query.aggregation.function.LastWithTimeAggregationFunction && withTimeType(f) != null ? 22 : -1;
       default: return -1;
     }
   }

@@ -46,6 +46,7 @@ static void knobs_read(Knobs& k) {
   k.expr_lds_max_slots = std::max<int64_t>(1, std::min<int64_t>(PG_EXPR_LDS_SLOTS, num("PG_EXPR_LDS_MAX_SLOTS", PG_EXPR_LDS_SLOTS)));
   k.expr_hbm_max_bytes = std::max<int64_t>(8, num("PG_EXPR_HBM_MAX_BYTES", (int64_t)256 << 20));
   k.var_hbm_max_bytes = std::max<int64_t>(8, num("PG_VAR_HBM_MAX_BYTES", (int64_t)256 << 20));
+  k.wt_hbm_max_bytes = std::max<int64_t>(8, num("PG_WT_HBM_MAX_BYTES", (int64_t)256 << 20));
   k.limit_prefix_min_docs = std::max<int64_t>(PG_WAVE_DOCS, num("PG_LIMIT_PREFIX_MIN_DOCS", (int64_t)1 << 20));
   k.oct_passes = str("PG_OCT_PASSES"); k.rccl_library = str("PG_RCCL_LIBRARY");
 }
@@ -275,6 +276,10 @@ int32_t pg_query_supported(pg_segment_t segment, const pg_query* query) {
       expression_check(segment->seg, *query);
       return;
     }
+    if (has_with_time(*query)) {   // the checks of the FIRSTWITHTIME / LASTWITHTIME path (and of a variance or PERCENTILE next to it)
+      with_time_check(segment->seg, *query);
+      return;
+    }
     if (has_variance(*query)) {   // the checks of the variance path (and of a PERCENTILE next to it)
       variance_check(segment->seg, *query);
       return;
@@ -328,6 +333,7 @@ int32_t pg_result_merge(pg_result_t dst, pg_result_t src) {
     if (dst->r->percentile || src->r->percentile) fail(PG_ERR_UNSUPPORTED, "PERCENTILE results are merged by value (DoubleArrayList#addAll on the Java side)");
     if (dst->r->expression || src->r->expression) fail(PG_ERR_UNSUPPORTED, "results of aggregations over expressions are merged by value on the Java side (the scale of their exact sums differs per segment)");
     if (dst->r->variance || src->r->variance) fail(PG_ERR_UNSUPPORTED, "results of variance aggregations are merged on the Java side (VarianceTuple#apply)");
+    if (dst->r->with_time || src->r->with_time) fail(PG_ERR_UNSUPPORTED, "results of FIRSTWITHTIME / LASTWITHTIME are merged on the Java side (the functions' own merge of ValueLongPair)");
     result_merge(*dst->r, *src->r);
   });
 }
@@ -339,6 +345,7 @@ int32_t pg_result_all_reduce(pg_result_t result, pg_comm_t comm) {
     if (result->r->percentile) fail(PG_ERR_UNSUPPORTED, "PERCENTILE results are merged by value (DoubleArrayList#addAll on the Java side)");
     if (result->r->expression) fail(PG_ERR_UNSUPPORTED, "results of aggregations over expressions are merged by value on the Java side (the scale of their exact sums differs per segment)");
     if (result->r->variance) fail(PG_ERR_UNSUPPORTED, "results of variance aggregations are merged on the Java side (VarianceTuple#apply)");
+    if (result->r->with_time) fail(PG_ERR_UNSUPPORTED, "results of FIRSTWITHTIME / LASTWITHTIME are merged on the Java side (the functions' own merge of ValueLongPair)");
     result_all_reduce(*result->r, *comm->c);
   });
 }

@@ -83,6 +83,8 @@ const char* function_name(int32_t fn) {   // AggregationFunctionType#getName().t
     case PG_AGG_VARSAMP: return "varsamp";
     case PG_AGG_STDDEVPOP: return "stddevpop";
     case PG_AGG_STDDEVSAMP: return "stddevsamp";
+    case PG_AGG_FIRSTWITHTIME: return "firstwithtime";   // getResultColumnName: the lower-case name + "(" + the argument list as given + ")"
+    case PG_AGG_LASTWITHTIME: return "lastwithtime";
     default: fail(PG_ERR_INTERNAL, "aggregation function %d has no name", fn);
   }
   return "";
@@ -321,6 +323,21 @@ std::vector<uint8_t> result_data_table_v4(const Result& r) {
           p.f64(ar.d[0][(size_t)i]);
           p.f64(ar.d[1][(size_t)i]);
           object(33, p);
+          break;
+        }
+        case PG_RESULT_VALUE_TIME_PAIR: {   // ValueLongPair#toBytes: the value big-endian (4 or 8 bytes), then the time as a big-endian long
+          Out p;   // ObjectSerDeUtils types 27 IntLongPair, 28 LongLongPair, 29 FloatLongPair, 30 DoubleLongPair
+          const int64_t bits = ar.l[1][(size_t)i];
+          int type = 0;
+          switch (ar.value_type) {
+            case PG_TYPE_INT: type = 27; p.i32((int32_t)bits); break;
+            case PG_TYPE_LONG: type = 28; p.i64(bits); break;
+            case PG_TYPE_FLOAT: type = 29; p.i32((int32_t)(uint32_t)bits); break;
+            case PG_TYPE_DOUBLE: type = 30; p.i64(bits); break;
+            default: fail(PG_ERR_INTERNAL, "a value-time pair of declared type %d in a data table", ar.value_type);
+          }
+          p.i64(ar.l[0][(size_t)i]);
+          object(type, p);
           break;
         }
         default: fail(PG_ERR_INTERNAL, "result kind %d in a data table", ar.kind);

@@ -475,7 +475,7 @@ __device__ __forceinline__ uint32_t pg_fixed_bit_id(const uint8_t* data, int32_t
 }
 __device__ __forceinline__ uint32_t pg_fixed_bit_id_at(const PgDistinctCol& c, uint32_t doc) { return pg_fixed_bit_id(c.data, c.bits, doc); }
 #endif
-// What the side passes' kernels (PERCENTILE, expressions, the variance family) scan: the filter's match words and the group columns whose ids form the group key.
+// What the side passes' kernels (PERCENTILE, expressions, the variance family, FIRSTWITHTIME / LASTWITHTIME) scan: the filter's match words and the group columns whose ids form the group key.
 // The first member of their arguments; the host fills it in one place (side_scan_fill, pg_exec_sidepass.hip).
 struct PgGroupScan {
   const uint64_t* match;       // the filter's match words (bit b of word w is doc 64 w + b); NULL: every doc below n_docs matches
@@ -645,6 +645,44 @@ struct PgVarArgs {
   uint64_t n_slots;            // G x slots
   int64_t* table;              // [G][slots] in HBM, zeroed by the caller
   PgVarCol cols[PG_VAR_MAX_COLS];
+};
+// ---- FIRSTWITHTIME / LASTWITHTIME (pg_kernels_withtime.hip) --------------------------------------------------------------------------
+// An arg-max per group: per matching doc the group key, then one 64-bit atomic max per SLOT — a distinct (time column, direction) of the
+// query — into the table [G][slots] of `keys`: the packed (time, doc) of pg_with_time.h, or in wide mode the time's order key (pass 0) and,
+// in pass 1, doc + 1 into `docs` for the docs whose key equals their slot's maximum.  Both planes start at 0.
+#include "pg_with_time.h"
+struct PgWtSlot {
+  PgValueSrc time;             // the time column: INT / LONG, dictionary-encoded or raw
+  int32_t first;               // FIRSTWITHTIME (wave-uniform)
+  int32_t packed;              // packed mode; else wide
+  int64_t base;                // packed mode: tmin (LAST) / tmax (FIRST)
+};
+struct PgWtArgs {
+  PgGroupScan scan;            // match words and group columns
+  int32_t slots;               // slots per group (<= PG_WT_MAX_SLOTS)
+  int32_t pass;                // 0: the keys; 1: the doc plane of the wide slots
+  int32_t doc_bits;            // D of packed mode
+  int32_t pad;
+  uint64_t n_groups;           // G (<= 2^32)
+  uint64_t n_slots;            // G x slots
+  unsigned long long* keys;    // [G][slots] in HBM, zeroed by the caller
+  unsigned long long* docs;    // [G][slots] in HBM, zeroed by the caller; NULL when every slot is packed
+  PgWtSlot slot[PG_WT_MAX_SLOTS];
+};
+// the gather of the admitted rows: per row and slot the winner doc (-1: none) and its time, per row and aggregation the value's 64 bits
+struct PgWtGatherArgs {
+  const unsigned long long* keys;
+  const unsigned long long* docs;
+  const uint32_t* rows;        // [n_rows] group keys
+  int32_t n_rows;
+  int32_t slots;
+  int32_t n_aggs;
+  int32_t doc_bits;
+  int64_t n_docs;
+  int64_t* out;                // [n_rows][2 x slots + n_aggs]: (doc, time) per slot, then the values
+  PgWtSlot slot[PG_WT_MAX_SLOTS];
+  PgValueSrc value[PG_WT_MAX_AGGS];
+  int32_t value_slot[PG_WT_MAX_AGGS];
 };
 // a time-bucket transform as a key (pg_kernels_timekey.hip): the value column and the normal form, wave-uniform kernel arguments
 struct PgTimeKeyArgs {

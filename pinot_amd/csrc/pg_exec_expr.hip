@@ -57,6 +57,8 @@ const char* function_text(int32_t fn) {
     case PG_AGG_VARSAMP: return "VAR_SAMP";
     case PG_AGG_STDDEVPOP: return "STDDEV_POP";
     case PG_AGG_STDDEVSAMP: return "STDDEV_SAMP";
+    case PG_AGG_FIRSTWITHTIME: return "FIRSTWITHTIME";
+    case PG_AGG_LASTWITHTIME: return "LASTWITHTIME";
     default: return "this aggregation function";
   }
 }
@@ -134,7 +136,8 @@ ExprPlan expr_plan(Segment& seg, const pg_query& q, bool compute_bounds) {
   for (int a = 0; a < q.n_aggregations; a++) {
     const pg_agg_spec& s = q.aggregations[a];
     if (!is_expression_agg(s)) {
-      if (s.column && strcmp(s.column, "*") != 0) read.insert(s.column);
+      if (is_with_time_function(s.function)) with_time_columns_read(s, read);   // its column is an argument list
+      else if (s.column && strcmp(s.column, "*") != 0) read.insert(s.column);
       continue;
     }
     int32_t acc = 0;
@@ -233,6 +236,7 @@ void expression_check(Segment& seg, const pg_query& q) {
   (void)expr_plan(seg, q, false);
   SideBaseQuery B;   // ... and what the ordinary part refuses
   side_base_query(q, is_expression_agg, kBaseClears, B);
+  if (has_with_time(B.q)) { with_time_check(seg, B.q); return; }
   if (has_variance(B.q)) { variance_check(seg, B.q); return; }
   if (has_percentile(B.q)) { percentile_check(seg, B.q); return; }
   check_null_handling(seg, B.q);

@@ -1,5 +1,5 @@
 // The frame of the side passes: aggregations answered by a pass of their own and joined to the ordinary plan by group key (exact PERCENTILE:
-// pg_exec_percentile.hip; aggregations over an expression: pg_exec_expr.hip; the variance family: pg_exec_var.hip).  A path plans its aggregations and its group-by
+// pg_exec_percentile.hip; aggregations over an expression: pg_exec_expr.hip; the variance family: pg_exec_var.hip; FIRSTWITHTIME / LASTWITHTIME: pg_exec_withtime.hip).  A path plans its aggregations and its group-by
 // columns (side_groups), splits the query (side_base_query), and then
 //   1. side_pass_begin runs the ordinary part through execute_query — it decides the groups, the numGroupsLimit admission and the other
 //      aggregations' results —, runs the filter again for its match words (the filter kernels and cached filter plan of the DISTINCT path; none

@@ -178,6 +178,54 @@ struct Parser {
 
 }  // namespace
 
+int32_t expr_split_arguments(const char* text, std::vector<ExprArgument>& out, std::string& error) {
+  out.clear();
+  error.clear();
+  auto bad = [&](const std::string& msg) { out.clear(); error = msg; return (int32_t)PG_ERR_INVALID_ARGUMENT; };
+  if (!text) return bad("argument list: null text");
+  ExprProgram unused;
+  Parser p(text, unused, error);   // the lexer's blanks and delimiters
+  for (;;) {
+    p.skip_ws();
+    ExprArgument arg;
+    if (p.i < p.n && p.s[p.i] == '\'') {   // a quoted literal
+      const size_t from = ++p.i;
+      while (p.i < p.n && p.s[p.i] != '\'') p.i++;
+      if (p.i >= p.n) return bad("argument list: unterminated quote");
+      arg.text.assign(p.s + from, p.i - from);
+      arg.quoted = true;
+      p.i++;
+    } else {
+      const size_t from = p.i;
+      int depth = 0;
+      for (; p.i < p.n; p.i++) {
+        const char c = p.s[p.i];
+        if (c == '\'') {   // a literal inside a nested call
+          p.i++;
+          while (p.i < p.n && p.s[p.i] != '\'') p.i++;
+          if (p.i >= p.n) return bad("argument list: unterminated quote");
+        } else if (c == '(') {
+          depth++;
+        } else if (c == ')') {
+          if (--depth < 0) return bad("argument list: unbalanced parentheses");
+        } else if (c == ',' && depth == 0) {
+          break;
+        }
+      }
+      if (depth != 0) return bad("argument list: unbalanced parentheses");
+      size_t to = p.i;
+      while (to > from && (p.s[to - 1] == ' ' || p.s[to - 1] == '\t' || p.s[to - 1] == '\n' || p.s[to - 1] == '\r')) to--;
+      if (to == from) return bad("argument list: an empty argument");
+      arg.text.assign(p.s + from, to - from);
+    }
+    out.push_back(std::move(arg));
+    p.skip_ws();
+    if (p.i >= p.n) return PG_OK;
+    if (p.s[p.i] != ',') return bad("argument list: ',' expected at '" + p.shown(p.i, p.n) + "'");
+    p.i++;
+  }
+}
+
 int32_t expr_parse(const char* text, ExprProgram& out, std::string& error) {
   out.columns.clear();
   out.n_steps = 0;

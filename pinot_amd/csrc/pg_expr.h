@@ -33,4 +33,13 @@ inline bool expr_is_expression(const char* text) {
 // PG_OK, or PG_ERR_INVALID_ARGUMENT (malformed text, a wrong argument count, a literal that is no number, no column in it) /
 // PG_ERR_UNSUPPORTED (another function, more than PG_EXPR_MAX_SRCS columns or PG_EXPR_MAX_OPS operations) with the reason in `error`
 int32_t expr_parse(const char* text, ExprProgram& out, std::string& error);
+// The argument list of an aggregation with more than one argument (pg_agg_spec.column of FIRSTWITHTIME / LASTWITHTIME, "x,t,'DOUBLE'"), split
+// by the lexer of the expression texts above: commas at depth 0, single-quoted literals, blanks around an argument dropped.  A nested call
+// stays one argument with its parentheses (expr_is_expression tells).  PG_OK, or PG_ERR_INVALID_ARGUMENT (null or empty text, an empty
+// argument, an unterminated quote, text behind a quoted literal, unbalanced parentheses) with the reason in `error`.
+struct ExprArgument {
+  std::string text;      // a quoted literal: without its quotes
+  bool quoted = false;
+};
+int32_t expr_split_arguments(const char* text, std::vector<ExprArgument>& out, std::string& error);
 }  // namespace pg

@@ -462,6 +462,10 @@ struct AggResult {
   std::vector<int64_t> hll_gids;
   int32_t log2m = 0;
   // PG_RESULT_VARIANCE_TUPLE (VAR_POP / VAR_SAMP / STDDEV_POP / STDDEV_SAMP): l[0] = count, d[0] = sum, d[1] = m2
+  // PG_RESULT_VALUE_TIME_PAIR (FIRSTWITHTIME / LASTWITHTIME): l[0] = time; l[1] = the value in its declared type — an INT / LONG value, or the
+  // raw IEEE bits of a FLOAT (32, zero-extended) / DOUBLE —, d[0] = a FLOAT / DOUBLE value (the FLOAT widened exactly); `value_type` the
+  // declared type (pg_data_type: the data table's object type and the width of its value)
+  int32_t value_type = -1;
   // PG_RESULT_VALUE_COUNTS (PERCENTILE): set_sizes = runs per group, d[0] = the runs' values (ascending under Double.compare within a group),
   // l[0] = their counts; `param` is the aggregation's p (also kept on a final PG_RESULT_DOUBLE: the data table names the column by it)
   double param = 0;
@@ -526,6 +530,7 @@ struct Result {
   bool percentile = false;      // the query carried a PERCENTILE: its lists merge by value on the Java side (never merged in the library)
   bool expression = false;      // the query carried an aggregation over an expression: the scale of its sums differs per segment (never merged in the library)
   bool variance = false;        // the query carried a variance aggregation: its tuples merge on the Java side, VarianceTuple#apply (never merged in the library)
+  bool with_time = false;       // the query carried a FIRSTWITHTIME / LASTWITHTIME: its pairs merge on the Java side with the functions' own merge (never merged in the library)
   pg_exec_stats stats{};
 };
 struct DocIdSet {
@@ -553,8 +558,9 @@ constexpr int32_t kQueryFlagNullPartition = 0x40000000;
 std::unique_ptr<Result> execute_distinct(Segment& seg, const pg_query& q, const CancelToken* cancel);   // PG_QUERY_FLAG_DISTINCT (pg_exec.hip)
 std::unique_ptr<Result> execute_selection(Segment& seg, const pg_query& q, const CancelToken* cancel);  // PG_QUERY_FLAG_SELECTION (pg_exec.hip)
 // ---- side passes: aggregations answered by a pass of their own and joined to the ordinary plan by group key -------------------------------
-// The frame they share (pg_exec_sidepass.hip; `who` names the path in messages — "PERCENTILE" / "expression" / "variance" —, `subject` is
-// how a refusal names its aggregation: "PERCENTILE" / "an aggregation over an expression" / "a variance aggregation").
+// The frame they share (pg_exec_sidepass.hip; `who` names the path in messages — "PERCENTILE" / "expression" / "variance" / "FIRSTWITHTIME / LASTWITHTIME" —,
+// `subject` is how a refusal names its aggregation: "PERCENTILE" / "an aggregation over an expression" / "a variance aggregation" /
+// "FIRSTWITHTIME / LASTWITHTIME").
 bool column_has_nulls(Segment& seg, const std::string& name);   // seg.mu held
 Column* id_column(Segment& seg, Column& c, const char* what, const char* who);   // seg.mu held
 std::vector<uint32_t> group_ids_of(const Result& r, int j, const Column& col, const Column& ids, int32_t n_rows, const char* who);
@@ -630,6 +636,15 @@ std::unique_ptr<Result> execute_expression(Segment& seg, const pg_query& q, cons
 bool has_variance(const pg_query& q);
 void variance_check(Segment& seg, const pg_query& q);
 std::unique_ptr<Result> execute_variance(Segment& seg, const pg_query& q, const CancelToken* cancel);
+// Queries with a FIRSTWITHTIME / LASTWITHTIME aggregation (pg_exec_withtime.hip): one arg-max pass (two in wide mode, pg_with_time.h) for
+// all of them and a gather of the winners' values.  with_time_check: the checks of the path (pg_query_supported).  with_time_columns_read:
+// the argument columns of such an aggregation, whose pg_agg_spec.column is an argument list, added to `read` (an outer side pass counts
+// them; a malformed list adds nothing — the path's own checks refuse it).
+bool is_with_time_function(int32_t fn);
+bool has_with_time(const pg_query& q);
+void with_time_check(Segment& seg, const pg_query& q);
+void with_time_columns_read(const pg_agg_spec& s, std::set<std::string>& read);
+std::unique_ptr<Result> execute_with_time(Segment& seg, const pg_query& q, const CancelToken* cancel);
 std::unique_ptr<Result> execute_query_plain(Segment& seg, const pg_query& q, const CancelToken* cancel);   // ... the executor proper (pg_exec.hip)
 void fill_result_schema(Segment& seg, const pg_query& q, Result& r);
 int64_t hll_cardinality(const uint8_t* regs, int log2m);   // HyperLogLog#cardinality of one register row (pg_exec.hip)
@@ -703,6 +718,7 @@ struct Knobs {
   int64_t expr_lds_max_slots = 16384;                // PG_EXPR_LDS_MAX_SLOTS
   int64_t expr_hbm_max_bytes = (int64_t)256 << 20;   // PG_EXPR_HBM_MAX_BYTES
   int64_t var_hbm_max_bytes = (int64_t)256 << 20;    // PG_VAR_HBM_MAX_BYTES: the slot table of the variance aggregations (pg_exec_var.hip) beyond its LDS tier; larger ones are refused
+  int64_t wt_hbm_max_bytes = (int64_t)256 << 20;     // PG_WT_HBM_MAX_BYTES: the planes of FIRSTWITHTIME / LASTWITHTIME (pg_exec_withtime.hip) beyond their LDS tier; larger ones are refused
   int64_t limit_prefix_min_docs = (int64_t)1 << 20;   // PG_LIMIT_PREFIX_MIN_DOCS: smallest doc prefix of the numGroupsLimit admission pass (tests lower it)
   std::string oct_passes;      // PG_OCT_PASSES: cumulative fractions, e.g. "0.02,0.08,0.3,1"
   // pg_comm.cpp

@@ -495,6 +495,7 @@ std::unique_ptr<Result> execute_query(Segment& seg, const pg_query& q_in, const 
   // aggregations over expressions: before the PERCENTILE check, so that the expression pass is the outer one of a query that carries both —
   // its statistics count the operand columns, and its ordinary part (PERCENTILEs included) comes back through here
   if (has_expression(q)) return execute_expression(seg, q, cancel);
+  if (has_with_time(q)) return execute_with_time(seg, q, cancel);   // inside the expression pass, outside the variance's and the PERCENTILE's: its statistics count its two argument columns
   if (has_variance(q)) return execute_variance(seg, q, cancel);   // inside the expression pass, outside the PERCENTILE's: its ordinary part comes back through here
   if (has_percentile(q)) return execute_percentile(seg, q, cancel);   // its ordinary part comes back through here; nulls in its columns are refused (percentile_check)
   if (!(q.flags & PG_QUERY_FLAG_NULL_HANDLING)) return execute_query_plain(seg, q, cancel);

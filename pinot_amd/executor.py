@@ -22,7 +22,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import capi
-from .query import CQuery, QueryContext, parse_sql
+from .query import CQuery, QueryContext, parse_sql, with_time_arguments
 from .segment import HostSegment
 
 
@@ -445,6 +445,16 @@ class ResultsBlock:
                 api.call("result_doubles", h, a, 0, s.ctypes.data, ng)
                 api.call("result_doubles", h, a, 1, m2.ctypes.data, ng)
                 rb.arrays.append((k, n, s, m2))
+            elif k == capi.RESULT_VALUE_TIME_PAIR:   # FIRSTWITHTIME / LASTWITHTIME: ValueLongPair(value, time), the value in its declared type
+                floating = with_time_arguments(spec.column)[2] in ("FLOAT", "DOUBLE")
+                t = np.zeros(ng, dtype=np.int64)
+                v = np.zeros(ng, dtype=np.float64 if floating else np.int64)
+                api.call("result_longs", h, a, 0, t.ctypes.data, ng)
+                if floating:
+                    api.call("result_doubles", h, a, 0, v.ctypes.data, ng)
+                else:
+                    api.call("result_longs", h, a, 1, v.ctypes.data, ng)
+                rb.arrays.append((k, v, t))
             elif k == capi.RESULT_HLL:
                 m = 1 << (spec.log2m or 8)
                 regs = np.empty(max(ng * m, 1), dtype=np.uint8)
@@ -538,6 +548,8 @@ class ResultsBlock:
                     cols.append(col)
                 elif k == capi.RESULT_VARIANCE_TUPLE:   # (count, sum, m2) per group
                     cols.append([(int(n), float(s), float(m2)) for n, s, m2 in zip(arr[1], arr[2], arr[3])])
+                elif k == capi.RESULT_VALUE_TIME_PAIR:   # (value, time) per group; a FLOAT / DOUBLE value keeps its bits (NaN payloads, -0.0)
+                    cols.append([(v.item(), int(t)) for v, t in zip(arr[1], arr[2])])
                 elif k == capi.RESULT_VALUE_COUNTS:   # (values, counts) per group
                     col, pos = [], 0
                     for sz in arr[1]:
@@ -631,6 +643,14 @@ def variance_merge(a, b):
     return (n + b[0], s + b[1], m2 + (b[2] + delta * delta * b[0] * n / (b[0] + n)))
 
 
+def with_time_merge(function: str, a, b):
+    """FirstWithTimeAggregationFunction#merge / LastWithTimeAggregationFunction#merge over two (value, time) pairs, what the Java side does
+    with the pairs of two segments: LAST keeps `a` where a.time >= b.time, FIRST where a.time <= b.time — the first argument wins a tie."""
+    if function == "LASTWITHTIME":
+        return a if a[1] >= b[1] else b
+    return a if a[1] <= b[1] else b
+
+
 def hll_merge(a: bytes, b: bytes) -> bytes:
     return bytes(max(x, y) for x, y in zip(a, b))
 
@@ -658,6 +678,8 @@ def merge_intermediate(function: str, a, b):
         return hll_merge(a, b)
     if function in capi.VARIANCE_FUNCTIONS:
         return variance_merge(a, b)
+    if function in capi.WITH_TIME_FUNCTIONS:
+        return with_time_merge(function, a, b)
     raise ValueError(function)
 
 
@@ -674,6 +696,8 @@ def extract_final(function: str, v):
         return hll_cardinality(v)
     if function in capi.VARIANCE_FUNCTIONS:
         return variance_final(function, v)
+    if function in capi.WITH_TIME_FUNCTIONS:   # the pair's value
+        return v[0]
     return v
 
 

@@ -130,6 +130,8 @@ class QueryContext:
         def norm(t):
             t = re.sub(r"\s+", "", t).upper()
             head, paren, rest = t.partition("(")   # VAR_POP(x) names the aggregation VARPOP(x): AggregationFunctionType strips underscores
+            if paren and with_time_function_name(head):   # ... and LAST_WITH_TIME(x, t, 'int') names LASTWITHTIME(X,T,INT): the type literal with or without its quotes
+                return with_time_function_name(head) + paren + rest.replace("'", "")
             return variance_function_name(head) + paren + rest if paren and variance_function_name(head) else t
         aggs = [norm(f"{a.function}({a.column or '*'}{',' + str(a.log2m) if a.log2m else ''})") for a in self.aggregations]
         pctl = [(a.column, a.percentile) if a.function == "PERCENTILE" else None for a in self.aggregations]
@@ -161,6 +163,18 @@ def variance_function_name(fn: str):
     strips underscores and ignores case), else None."""
     name = fn.replace("_", "").upper()
     return name if name in capi.VARIANCE_FUNCTIONS else None
+
+
+def with_time_function_name(fn: str):
+    """FIRSTWITHTIME / LASTWITHTIME for any spelling of them (FIRST_WITH_TIME, lastWithTime), else None."""
+    name = fn.replace("_", "").upper()
+    return name if name in capi.WITH_TIME_FUNCTIONS else None
+
+
+def with_time_arguments(column: str):
+    """(x, t, TYPE) of a FIRSTWITHTIME / LASTWITHTIME argument list "x,t,'type'" (the type upper-cased, as DataType.valueOf(toUpperCase()))."""
+    x, t, ty = (p.strip() for p in column.split(","))
+    return x, t, ty.strip("'").upper()
 
 
 _PERCENTILE_LEGACY = re.compile(r"^PERCENTILE(\d+)$")
@@ -512,8 +526,21 @@ class _Parser:
         if t[0] != "id":
             raise SqlError(f"bad select item {t}")
         if self.peek() == ("op", "("):
-            fn = variance_function_name(t[1]) or t[1].upper()
+            fn = variance_function_name(t[1]) or with_time_function_name(t[1]) or t[1].upper()
             self.i += 1
+            if fn in capi.WITH_TIME_FUNCTIONS:   # FIRSTWITHTIME(x, t, 'TYPE'): the argument list travels as getResultColumnName prints it
+                args = [self.aggregation_argument()]
+                self.expect_op(",")
+                args.append(self.aggregation_argument())
+                self.expect_op(",")
+                t3 = self.take()
+                if t3[0] != "str":
+                    raise SqlError(f"{fn}: the third argument must be a quoted data type literal, got {t3}")
+                self.expect_op(")")
+                q.aggregations.append(AggregationSpec(fn, f"{args[0]},{args[1]},'{t3[1]}'"))
+                if self.kw("AS"):
+                    self.i += 2
+                return
             if self.peek() == ("op", "*") and self.peek(1) == ("op", ")"):
                 self.i += 1
                 col = None
