@@ -272,24 +272,7 @@ int32_t pg_query_supported(pg_segment_t segment, const pg_query* query) {
       (void)get_plan(segment->seg, query->filter, nullptr, query->flags & PG_QUERY_FLAG_NULL_HANDLING);
       return;
     }
-    if (has_expression(*query)) {   // the checks of the expression path (and of a PERCENTILE next to it)
-      expression_check(segment->seg, *query);
-      return;
-    }
-    if (has_with_time(*query)) {   // the checks of the FIRSTWITHTIME / LASTWITHTIME path (and of a variance or PERCENTILE next to it)
-      with_time_check(segment->seg, *query);
-      return;
-    }
-    if (has_variance(*query)) {   // the checks of the variance path (and of a PERCENTILE next to it)
-      variance_check(segment->seg, *query);
-      return;
-    }
-    if (has_percentile(*query)) {   // the checks of the percentile path; the ordinary part's plan is compiled by the execution
-      percentile_check(segment->seg, *query);
-      return;
-    }
-    check_null_handling(segment->seg, *query);
-    (void)get_plan(segment->seg, query->filter, query);
+    side_check(segment->seg, *query);   // the checks of every side path the query nests (kSidePaths), then the ordinary part's checks and plan
   });
 }
 

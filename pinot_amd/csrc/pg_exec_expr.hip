@@ -34,34 +34,7 @@ namespace {
 const char* kWho = "expression";
 const char* kSubject = "an aggregation over an expression";
 constexpr size_t kMaxCachedBounds = 256;   // Segment::expr_bounds entries per segment (some tens of bytes each)
-enum Tier { TIER_REG = 0, TIER_LDS = 1, TIER_HBM = 2 };
 const char* const kTierKernel[3] = {"pg_expr_reg", "pg_expr_lds", "pg_expr_hbm"};
-
-bool is_expression_agg(const pg_agg_spec& s) { return expr_is_expression(s.column); }
-
-const char* function_text(int32_t fn) {
-  switch (fn) {
-    case PG_AGG_COUNT: return "COUNT";
-    case PG_AGG_DISTINCTCOUNT: return "DISTINCTCOUNT";
-    case PG_AGG_DISTINCTCOUNTHLL: return "DISTINCTCOUNTHLL";
-    case PG_AGG_PERCENTILE: return "PERCENTILE";
-    case PG_AGG_COUNTMV: return "COUNTMV";
-    case PG_AGG_SUMMV: return "SUMMV";
-    case PG_AGG_MINMV: return "MINMV";
-    case PG_AGG_MAXMV: return "MAXMV";
-    case PG_AGG_AVGMV: return "AVGMV";
-    case PG_AGG_MINMAXRANGEMV: return "MINMAXRANGEMV";
-    case PG_AGG_DISTINCTCOUNTMV: return "DISTINCTCOUNTMV";
-    case PG_AGG_DISTINCTCOUNTHLLMV: return "DISTINCTCOUNTHLLMV";
-    case PG_AGG_VARPOP: return "VAR_POP";
-    case PG_AGG_VARSAMP: return "VAR_SAMP";
-    case PG_AGG_STDDEVPOP: return "STDDEV_POP";
-    case PG_AGG_STDDEVSAMP: return "STDDEV_SAMP";
-    case PG_AGG_FIRSTWITHTIME: return "FIRSTWITHTIME";
-    case PG_AGG_LASTWITHTIME: return "LASTWITHTIME";
-    default: return "this aggregation function";
-  }
-}
 
 struct ExprItem {
   std::string text;
@@ -148,7 +121,7 @@ ExprPlan expr_plan(Segment& seg, const pg_query& q, bool compute_bounds) {
       case PG_AGG_AVG: acc = PG_EXPR_ACC_SUM; need_count = true; break;
       case PG_AGG_MINMAXRANGE: acc = PG_EXPR_ACC_MIN | PG_EXPR_ACC_MAX; break;
       default:
-        fail(PG_ERR_UNSUPPORTED, "%s over an expression (%s): SUM, MIN, MAX, AVG and MINMAXRANGE take one on the GPU path", function_text(s.function), s.column);
+        fail(PG_ERR_UNSUPPORTED, "%s over an expression (%s): SUM, MIN, MAX, AVG and MINMAXRANGE take one on the GPU path", agg_function_text(s.function), s.column);
     }
     size_t k = 0;
     while (k < P.exprs.size() && P.exprs[k].text != s.column) k++;
@@ -204,17 +177,12 @@ ExprPlan expr_plan(Segment& seg, const pg_query& q, bool compute_bounds) {
   if (need_count) P.count_slot = P.slots++;
   P.n_slots = P.groups.G * (uint64_t)P.slots;   // < 2^37
   const Knobs& K = knobs();
-  if (q.n_group_by == 0) P.tier = TIER_REG;
-  else if (P.n_slots <= (uint64_t)std::min<int64_t>(K.expr_lds_max_slots, PG_EXPR_LDS_SLOTS)) P.tier = TIER_LDS;
-  else if (P.n_slots * 8 <= (uint64_t)K.expr_hbm_max_bytes) P.tier = TIER_HBM;
-  else
+  P.tier = side_tier(q.n_group_by, P.n_slots, (uint64_t)std::min<int64_t>(K.expr_lds_max_slots, PG_EXPR_LDS_SLOTS), P.n_slots * 8, K.expr_hbm_max_bytes);
+  if (P.tier == TIER_REFUSED)
     fail(PG_ERR_UNSUPPORTED, "aggregations over expressions: %llu groups x %d slots need a table of %llu bytes, more than PG_EXPR_HBM_MAX_BYTES (%lld)",
          (unsigned long long)P.groups.G, P.slots, (unsigned long long)(P.n_slots * 8), (long long)K.expr_hbm_max_bytes);
   return P;
 }
-
-// the ordinary part may hold a PERCENTILE, which reads PG_QUERY_FLAG_FINAL_PERCENTILE; it does not keep its table (the result is not merged in the library)
-constexpr int32_t kBaseClears = PG_QUERY_FLAG_KEEP_DEVICE_TABLE;
 
 double order_key_to_double(int64_t k) {
   const int64_t b = k ^ ((k >> 63) & 0x7FFFFFFFFFFFFFFFLL);
@@ -225,23 +193,8 @@ double order_key_to_double(int64_t k) {
 
 }  // namespace
 
-bool has_expression(const pg_query& q) {
-  if (q.flags & (PG_QUERY_FLAG_DISTINCT | PG_QUERY_FLAG_SELECTION)) return false;
-  if (!q.aggregations) return false;
-  for (int a = 0; a < q.n_aggregations; a++) if (is_expression_agg(q.aggregations[a])) return true;
-  return false;
-}
-
-void expression_check(Segment& seg, const pg_query& q) {
-  (void)expr_plan(seg, q, false);
-  SideBaseQuery B;   // ... and what the ordinary part refuses
-  side_base_query(q, is_expression_agg, kBaseClears, B);
-  if (has_with_time(B.q)) { with_time_check(seg, B.q); return; }
-  if (has_variance(B.q)) { variance_check(seg, B.q); return; }
-  if (has_percentile(B.q)) { percentile_check(seg, B.q); return; }
-  check_null_handling(seg, B.q);
-  (void)get_plan(seg, B.q.filter, &B.q);
-}
+bool is_expression_agg(const pg_agg_spec& s) { return expr_is_expression(s.column); }
+void expression_plan_check(Segment& seg, const pg_query& q) { (void)expr_plan(seg, q, false); }
 
 std::unique_ptr<Result> execute_expression(Segment& seg, const pg_query& q, const CancelToken* cancel) {
   const double t0 = now_ms();
@@ -249,7 +202,7 @@ std::unique_ptr<Result> execute_expression(Segment& seg, const pg_query& q, cons
   const ExprPlan P = expr_plan(seg, q, true);
   const double t_plan = now_ms();
   SideBaseQuery B;
-  side_base_query(q, is_expression_agg, kBaseClears, B);
+  side_base_query(q, B);
   SidePass S = side_pass_begin(seg, q, B, P.groups, kWho, cancel);
   const int32_t n_rows = S.n_rows;
   const int64_t M = S.M, n_words = S.n_words;
@@ -267,7 +220,7 @@ std::unique_ptr<Result> execute_expression(Segment& seg, const pg_query& q, cons
   A.n_slots = P.n_slots;
   for (size_t i = 0; i < P.srcs.size(); i++) {
     fill_src(A.srcs[i], *P.srcs[i]);
-    doc_bits += P.srcs[i]->col_kind == PG_COL_FIXED_BIT ? P.srcs[i]->bits : (P.srcs[i]->col_kind == PG_COL_RAW32 ? 32 : 64);
+    doc_bits += value_src_bits(*P.srcs[i]);
   }
   int32_t n_steps = 0;
   for (size_t e = 0; e < P.exprs.size(); e++) {
@@ -294,26 +247,16 @@ std::unique_ptr<Result> execute_expression(Segment& seg, const pg_query& q, cons
   // PG_QUERY_FLAG_PROFILE: the pass (initialisation, accumulation, gather and its copy) between two events of its own
   ProfileTimer timer(q.flags);
   timer.start(stream);
-  pg_expr_launch_init(&A, (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)cus * 8, ((int64_t)P.n_slots + 255) / 256)), stream);
+  pg_expr_launch_init(&A, side_flat_grid(cus, (int64_t)P.n_slots), stream);
   PG_HIP(hipGetLastError());
   if (M > 0 && n_words > 0) {
-    const int64_t words_per_wg = P.tier == TIER_LDS ? 32 : 16;
-    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(P.tier == TIER_LDS ? cus : cus * 8, (n_words + words_per_wg - 1) / words_per_wg));
-    pg_expr_launch_pass(&A, P.tier, grid, stream);
+    pg_expr_launch_pass(&A, P.tier, side_pass_grid(P.tier, cus, n_words), stream);
     PG_HIP(hipGetLastError());
   }
   std::vector<int64_t> got((size_t)n_rows * (size_t)P.slots);
-  if (n_rows > 0) {
-    DeviceBuffer d_rows((size_t)n_rows * 4), d_out(got.size() * 8);
-    PG_HIP(hipMemcpyAsync(d_rows.ptr, S.rows.data(), (size_t)n_rows * 4, hipMemcpyHostToDevice, stream));
-    pg_expr_launch_gather(table.as<int64_t>(), d_rows.as<uint32_t>(), n_rows, P.slots, P.groups.G, d_out.as<int64_t>(),
-                          (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)cus * 8, ((int64_t)got.size() + 255) / 256)), stream);
-    PG_HIP(hipGetLastError());
-    PG_HIP(hipMemcpyAsync(got.data(), d_out.ptr, got.size() * 8, hipMemcpyDeviceToHost, stream));
-    wait_stream(stream, cancel);   // d_rows and d_out go out of scope
-  } else {
-    wait_stream(stream, cancel);
-  }
+  side_gather_rows(S, got, cancel, [&](const uint32_t* rows, int64_t* out) {
+    pg_expr_launch_gather(table.as<int64_t>(), rows, n_rows, P.slots, P.groups.G, out, side_flat_grid(cus, (int64_t)got.size()), stream);
+  });
   const float pass_ms = timer.stop_ms();
   // ---- the expression aggregations' results: the reference's defaults over no doc fall out of the identities -----------------------------------
   std::vector<AggResult> out((size_t)q.n_aggregations);
@@ -363,8 +306,7 @@ std::unique_ptr<Result> execute_expression(Segment& seg, const pg_query& q, cons
   }
   if (q.n_group_by == 0 && P.count_slot >= 0 && got[(size_t)P.count_slot] != M)
     fail(PG_ERR_INTERNAL, "expression: %lld docs counted for %lld matching docs", (long long)got[(size_t)P.count_slot], (long long)M);
-  const int64_t pass_bytes = ((int64_t)seg.total_docs * doc_bits + 7) / 8 + (S.ds ? n_words * 8 : 0);
-  std::unique_ptr<Result> res = side_pass_finish(seg, q, B, S, out, {kTierKernel[P.tier], pass_bytes, P.n_columns_read, pass_ms, t0, t_plan});
+  std::unique_ptr<Result> res = side_pass_finish(seg, q, B, S, out, {kTierKernel[P.tier], side_pass_bytes(seg, S, 1, doc_bits), P.n_columns_read, pass_ms, t0, t_plan});
   res->expression = true;
   return res;
 }

@@ -62,11 +62,8 @@ PctlPlan pctl_plan(Segment& seg, const pg_query& q) {
     const double p = q.agg_params[a];
     if (!(p >= 0.0 && p <= 100.0)) fail(PG_ERR_INVALID_ARGUMENT, "PERCENTILE(%s, %g): the percentile must be in [0, 100]", s.column ? s.column : "*", p);
     if (!s.column || strcmp(s.column, "*") == 0) fail(PG_ERR_INVALID_ARGUMENT, "PERCENTILE needs a column");
-    Column* c = seg.find(s.column);
-    if (!c) fail(PG_ERR_NOT_FOUND, "column not found: %s", s.column);
-    if (c->is_mv || c->raw_mv) fail(PG_ERR_UNSUPPORTED, "PERCENTILE over the multi-value column %s (PERCENTILEMV stays with the Java plan)", c->name.c_str());
-    if (c->data_type > PG_TYPE_DOUBLE) fail(PG_ERR_UNSUPPORTED, "PERCENTILE over the %s column %s", c->data_type == PG_TYPE_STRING ? "STRING" : "BYTES", c->name.c_str());
-    if (null_handling && column_has_nulls(seg, c->name)) fail(PG_ERR_UNSUPPORTED, "enableNullHandling: PERCENTILE over %s, which holds nulls", c->name.c_str());
+    // (no layout check: the pass counts ids — the column's dictIds, or its virtual dictionary's, id_column below)
+    Column* c = side_argument_column(seg, s.column, kWho, "column", nullptr, " (PERCENTILEMV stays with the Java plan)", null_handling);
     size_t k = 0;
     while (k < P.cols.size() && P.cols[k].col != c) k++;
     if (k == P.cols.size()) {
@@ -96,26 +93,10 @@ double value_of_id(const Column& col, const Column& ids, int32_t id) {   // Dict
   return d;
 }
 
-bool is_percentile_agg(const pg_agg_spec& s) { return s.function == PG_AGG_PERCENTILE; }
-// the ordinary part holds no PERCENTILE: it neither keeps its table (the result is not merged in the library) nor reads the final-form flag
-constexpr int32_t kBaseClears = PG_QUERY_FLAG_FINAL_PERCENTILE | PG_QUERY_FLAG_KEEP_DEVICE_TABLE;
-
 }  // namespace
 
-bool has_percentile(const pg_query& q) {
-  if (q.flags & (PG_QUERY_FLAG_DISTINCT | PG_QUERY_FLAG_SELECTION)) return false;
-  if (!q.aggregations) return false;
-  for (int a = 0; a < q.n_aggregations; a++) if (q.aggregations[a].function == PG_AGG_PERCENTILE) return true;
-  return false;
-}
-
-void percentile_check(Segment& seg, const pg_query& q) {
-  (void)pctl_plan(seg, q);
-  SideBaseQuery B;   // ... and what the ordinary part's plan refuses; compiled and cached for the execution that follows
-  side_base_query(q, is_percentile_agg, kBaseClears, B);
-  check_null_handling(seg, B.q);
-  (void)get_plan(seg, B.q.filter, &B.q);
-}
+bool is_percentile_agg(const pg_agg_spec& s) { return s.function == PG_AGG_PERCENTILE; }
+void percentile_plan_check(Segment& seg, const pg_query& q) { (void)pctl_plan(seg, q); }
 
 std::unique_ptr<Result> execute_percentile(Segment& seg, const pg_query& q, const CancelToken* cancel) {
   const double t0 = now_ms();
@@ -124,7 +105,7 @@ std::unique_ptr<Result> execute_percentile(Segment& seg, const pg_query& q, cons
   const double t_plan = now_ms();
   const bool final_values = (q.flags & PG_QUERY_FLAG_FINAL_PERCENTILE) != 0;
   SideBaseQuery B;
-  side_base_query(q, is_percentile_agg, kBaseClears, B);
+  side_base_query(q, B);
   SidePass S = side_pass_begin(seg, q, B, P.groups, kWho, cancel);
   const int32_t n_rows = S.n_rows;
   const int64_t M = S.M, n_words = S.n_words;

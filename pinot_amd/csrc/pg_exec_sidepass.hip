@@ -1,11 +1,14 @@
 // The frame of the side passes: aggregations answered by a pass of their own and joined to the ordinary plan by group key (exact PERCENTILE:
-// pg_exec_percentile.hip; aggregations over an expression: pg_exec_expr.hip; the variance family: pg_exec_var.hip; FIRSTWITHTIME / LASTWITHTIME: pg_exec_withtime.hip).  A path plans its aggregations and its group-by
-// columns (side_groups), splits the query (side_base_query), and then
+// pg_exec_percentile.hip; aggregations over an expression: pg_exec_expr.hip; the variance family: pg_exec_var.hip; FIRSTWITHTIME / LASTWITHTIME: pg_exec_withtime.hip).
+// The paths are the entries of kSidePaths below, in nesting order; side_path_of, side_check and execute_query (pg_nullaware.cpp) follow that list.  A path plans its aggregations and its group-by
+// columns (side_groups, side_argument_column), splits the query (side_base_query), and then
 //   1. side_pass_begin runs the ordinary part through execute_query — it decides the groups, the numGroupsLimit admission and the other
 //      aggregations' results —, runs the filter again for its match words (the filter kernels and cached filter plan of the DISTINCT path; none
 //      without a filter and without an upsert snapshot) and maps the admitted groups to rows of the path's table;
 //   2. the path runs its own kernels over the match words (side_scan_fill: the head of their arguments) between a ProfileTimer's events;
 //   3. side_pass_finish joins the columns and writes the statistics.
+// The paths with a table [G][slots] of 64-bit slots share more: where the table lives (side_tier), the pass's grid (side_pass_grid), the gather of the
+// admitted rows (side_gather_rows) and the pass's bytes (side_pass_bytes, value_src_bits).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -111,10 +114,115 @@ SideGroups side_groups(Segment& seg, const pg_query& q, const char* subject, con
   return S;
 }
 
-void side_base_query(const pg_query& q, bool (*is_side)(const pg_agg_spec&), int32_t clear_flags, SideBaseQuery& out) {
+// ---- the side paths in nesting order: the outermost first.  A query that carries several kinds is answered by the first one here; its ordinary
+// part comes back through execute_query and meets the next.
+// the ordinary part may hold a PERCENTILE, which reads PG_QUERY_FLAG_FINAL_PERCENTILE; it does not keep its table (the result is not merged in the library)
+constexpr int32_t kSideBaseClears = PG_QUERY_FLAG_KEEP_DEVICE_TABLE;
+// the PERCENTILE's ordinary part holds none: it neither keeps its table (the result is not merged in the library) nor reads the final-form flag
+constexpr int32_t kPercentileBaseClears = PG_QUERY_FLAG_FINAL_PERCENTILE | PG_QUERY_FLAG_KEEP_DEVICE_TABLE;
+const SidePath kSidePaths[] = {
+    // aggregations over expressions: before the PERCENTILE, so that the expression pass is the outer one of a query that carries both — its
+    // statistics count the operand columns, and its ordinary part (PERCENTILEs included) comes back through execute_query
+    {is_expression_agg, expression_plan_check, execute_expression, kSideBaseClears},
+    // inside the expression pass, outside the variance's and the PERCENTILE's: its statistics count its two argument columns
+    {is_with_time_agg, with_time_plan_check, execute_with_time, kSideBaseClears},
+    // inside the expression pass, outside the PERCENTILE's: its ordinary part comes back through execute_query
+    {is_variance_agg, variance_plan_check, execute_variance, kSideBaseClears},
+    // its ordinary part comes back through execute_query; nulls in its columns are refused (percentile_plan_check)
+    {is_percentile_agg, percentile_plan_check, execute_percentile, kPercentileBaseClears},
+};
+
+const SidePath* side_path_of(const pg_query& q) {
+  if (q.flags & (PG_QUERY_FLAG_DISTINCT | PG_QUERY_FLAG_SELECTION)) return nullptr;
+  if (!q.aggregations) return nullptr;
+  for (const SidePath& path : kSidePaths)
+    for (int a = 0; a < q.n_aggregations; a++) if (path.is_side(q.aggregations[a])) return &path;
+  return nullptr;
+}
+
+void side_base_query(const pg_query& q, SideBaseQuery& out) {
+  const SidePath* path = side_path_of(q);
+  if (!path) fail(PG_ERR_INTERNAL, "a side pass over a query without a side aggregation");
   std::string error;
-  const int32_t st = side_base_query(q, is_side, clear_flags, out, error);
+  const int32_t st = side_base_query(q, path->is_side, path->base_clears, out, error);
   if (st != PG_OK) fail(st, "%s", error.c_str());
+}
+
+void side_check(Segment& seg, const pg_query& q) {
+  const SidePath* path = side_path_of(q);
+  if (!path) {   // the ordinary part: what its plan refuses; compiled and cached for the execution that follows
+    check_null_handling(seg, q);
+    (void)get_plan(seg, q.filter, &q);
+    return;
+  }
+  path->plan_check(seg, q);
+  SideBaseQuery B;   // ... and what the ordinary part refuses
+  side_base_query(q, B);
+  side_check(seg, B.q);
+}
+
+// ---- what the slot-table paths share ---------------------------------------------------------------------------------------------------------
+int side_flat_grid(int cus, int64_t items) { return (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)cus * 8, (items + 255) / 256)); }
+
+int side_pass_grid(int tier, int cus, int64_t n_words, int64_t lds_wgs_per_cu) {
+  const int64_t words_per_wg = tier == TIER_LDS ? 32 : 16;
+  return (int)std::max<int64_t>(1, std::min<int64_t>(tier == TIER_LDS ? cus * lds_wgs_per_cu : (int64_t)cus * 8, (n_words + words_per_wg - 1) / words_per_wg));
+}
+
+int64_t value_src_bits(const Column& c) { return c.col_kind == PG_COL_FIXED_BIT ? c.bits : (c.col_kind == PG_COL_RAW32 ? 32 : 64); }
+
+void side_gather_rows(const SidePass& S, std::vector<int64_t>& got, const CancelToken* cancel, const std::function<void(const uint32_t*, int64_t*)>& launch) {
+  if (S.n_rows > 0) {
+    DeviceBuffer d_rows((size_t)S.n_rows * 4), d_out(got.size() * 8);
+    PG_HIP(hipMemcpyAsync(d_rows.ptr, S.rows.data(), (size_t)S.n_rows * 4, hipMemcpyHostToDevice, S.stream));
+    launch(d_rows.as<uint32_t>(), d_out.as<int64_t>());
+    PG_HIP(hipGetLastError());
+    PG_HIP(hipMemcpyAsync(got.data(), d_out.ptr, got.size() * 8, hipMemcpyDeviceToHost, S.stream));
+    wait_stream(S.stream, cancel);   // d_rows and d_out go out of scope
+  } else {
+    wait_stream(S.stream, cancel);
+  }
+}
+
+int64_t side_pass_bytes(const Segment& seg, const SidePass& S, int passes, int64_t doc_bits, int64_t extra) {
+  return passes * (((int64_t)seg.total_docs * doc_bits + 7) / 8 + (S.ds ? S.n_words * 8 : 0)) + extra;
+}
+
+Column* side_argument_column(Segment& seg, const char* name, const char* fn, const char* role, const char* layout_role, const char* mv_note, bool null_handling) {
+  Column* c = seg.find(name);
+  if (!c) fail(PG_ERR_NOT_FOUND, "column not found: %s", name);
+  if (c->is_mv || c->raw_mv) fail(PG_ERR_UNSUPPORTED, "%s over the multi-value %s %s%s", fn, role, c->name.c_str(), mv_note);
+  if (c->data_type > PG_TYPE_DOUBLE) fail(PG_ERR_UNSUPPORTED, "%s over the %s %s %s", fn, c->data_type == PG_TYPE_STRING ? "STRING" : "BYTES", role, c->name.c_str());
+  if (null_handling && column_has_nulls(seg, c->name)) fail(PG_ERR_UNSUPPORTED, "enableNullHandling: %s over %s, which holds nulls", fn, c->name.c_str());
+  if (!layout_role) return c;
+  const bool dict_ok = c->has_dictionary && c->col_kind == PG_COL_FIXED_BIT && c->bits >= 1 && c->bits <= 31 && c->cardinality >= 1 && c->dict_dev.ptr;
+  const bool raw_ok = !c->has_dictionary && (c->col_kind == PG_COL_RAW32 || c->col_kind == PG_COL_RAW64);
+  if (!dict_ok && !raw_ok) fail(PG_ERR_UNSUPPORTED, "%s: %s %s (layout %d, %d bits)", fn, layout_role, c->name.c_str(), c->col_kind, c->bits);
+  return c;
+}
+
+const char* agg_function_text(int32_t fn) {
+  switch (fn) {
+    case PG_AGG_COUNT: return "COUNT";
+    case PG_AGG_DISTINCTCOUNT: return "DISTINCTCOUNT";
+    case PG_AGG_DISTINCTCOUNTHLL: return "DISTINCTCOUNTHLL";
+    case PG_AGG_PERCENTILE: return "PERCENTILE";
+    case PG_AGG_COUNTMV: return "COUNTMV";
+    case PG_AGG_SUMMV: return "SUMMV";
+    case PG_AGG_MINMV: return "MINMV";
+    case PG_AGG_MAXMV: return "MAXMV";
+    case PG_AGG_AVGMV: return "AVGMV";
+    case PG_AGG_MINMAXRANGEMV: return "MINMAXRANGEMV";
+    case PG_AGG_DISTINCTCOUNTMV: return "DISTINCTCOUNTMV";
+    case PG_AGG_DISTINCTCOUNTHLLMV: return "DISTINCTCOUNTHLLMV";
+    case PG_AGG_VARPOP: return "VAR_POP";
+    case PG_AGG_VARSAMP: return "VAR_SAMP";
+    case PG_AGG_STDDEVPOP: return "STDDEV_POP";
+    case PG_AGG_STDDEVSAMP: return "STDDEV_SAMP";
+    case PG_AGG_FIRSTWITHTIME: return "FIRSTWITHTIME";
+    case PG_AGG_LASTWITHTIME: return "LASTWITHTIME";
+    default: return "this aggregation function";
+  }
 }
 
 SidePass side_pass_begin(Segment& seg, const pg_query& q, const SideBaseQuery& B, const SideGroups& G, const char* who, const CancelToken* cancel) {

@@ -29,20 +29,9 @@ namespace {
 
 const char* kWho = "variance";
 const char* kSubject = "a variance aggregation";
-enum Tier { TIER_REG = 0, TIER_LDS = 1, TIER_HBM = 2 };
 const char* const kTierKernel[3] = {"pg_var_reg", "pg_var_lds", "pg_var_hbm"};
 
 bool is_variance_function(int32_t fn) { return fn >= PG_AGG_VARPOP && fn <= PG_AGG_STDDEVSAMP; }
-bool is_variance_agg(const pg_agg_spec& s) { return is_variance_function(s.function); }
-
-const char* function_text(int32_t fn) {
-  switch (fn) {
-    case PG_AGG_VARPOP: return "VAR_POP";
-    case PG_AGG_VARSAMP: return "VAR_SAMP";
-    case PG_AGG_STDDEVPOP: return "STDDEV_POP";
-    default: return "STDDEV_SAMP";
-  }
-}
 
 struct VarColumn {
   Column* col = nullptr;
@@ -70,16 +59,9 @@ VarPlan var_plan(Segment& seg, const pg_query& q) {
     const pg_agg_spec& s = q.aggregations[a];
     if (s.column && strcmp(s.column, "*") != 0) read.insert(s.column);
     if (!is_variance_agg(s)) continue;
-    const char* fn = function_text(s.function);
+    const char* fn = agg_function_text(s.function);
     if (!s.column || strcmp(s.column, "*") == 0) fail(PG_ERR_INVALID_ARGUMENT, "%s needs a column", fn);
-    Column* c = seg.find(s.column);
-    if (!c) fail(PG_ERR_NOT_FOUND, "column not found: %s", s.column);
-    if (c->is_mv || c->raw_mv) fail(PG_ERR_UNSUPPORTED, "%s over the multi-value column %s", fn, c->name.c_str());
-    if (c->data_type > PG_TYPE_DOUBLE) fail(PG_ERR_UNSUPPORTED, "%s over the %s column %s", fn, c->data_type == PG_TYPE_STRING ? "STRING" : "BYTES", c->name.c_str());
-    if (null_handling && column_has_nulls(seg, c->name)) fail(PG_ERR_UNSUPPORTED, "enableNullHandling: %s over %s, which holds nulls", fn, c->name.c_str());
-    const bool dict_ok = c->has_dictionary && c->col_kind == PG_COL_FIXED_BIT && c->bits >= 1 && c->bits <= 31 && c->cardinality >= 1 && c->dict_dev.ptr;
-    const bool raw_ok = !c->has_dictionary && (c->col_kind == PG_COL_RAW32 || c->col_kind == PG_COL_RAW64);
-    if (!dict_ok && !raw_ok) fail(PG_ERR_UNSUPPORTED, "%s: argument column %s (layout %d, %d bits)", fn, c->name.c_str(), c->col_kind, c->bits);
+    Column* c = side_argument_column(seg, s.column, fn, "column", "argument column", "", null_handling);
     // the registration pass (pg_segment.cpp) knows every FLOAT / DOUBLE column's non-finite values: the power sums have no digits for them
     if ((c->val_type == PG_V_F32 || c->val_type == PG_V_F64) && c->has_nonfinite)
       fail(PG_ERR_UNSUPPORTED, "%s over %s, which holds a NaN or an infinity: the Java plan answers such a query", fn, c->name.c_str());
@@ -101,35 +83,17 @@ VarPlan var_plan(Segment& seg, const pg_query& q) {
   P.n_columns_read = (int)read.size();
   P.n_slots = P.groups.G * (uint64_t)P.slots;   // < 2^38
   const Knobs& K = knobs();
-  if (q.n_group_by == 0) P.tier = TIER_REG;
-  else if (P.n_slots <= (uint64_t)PG_VAR_LDS_SLOTS) P.tier = TIER_LDS;
-  else if (P.n_slots * 8 <= (uint64_t)K.var_hbm_max_bytes) P.tier = TIER_HBM;
-  else
+  P.tier = side_tier(q.n_group_by, P.n_slots, PG_VAR_LDS_SLOTS, P.n_slots * 8, K.var_hbm_max_bytes);
+  if (P.tier == TIER_REFUSED)
     fail(PG_ERR_UNSUPPORTED, "variance aggregations: %llu groups x %d slots need a table of %llu bytes, more than PG_VAR_HBM_MAX_BYTES (%lld)",
          (unsigned long long)P.groups.G, P.slots, (unsigned long long)(P.n_slots * 8), (long long)K.var_hbm_max_bytes);
   return P;
 }
 
-// the ordinary part may hold a PERCENTILE, which reads PG_QUERY_FLAG_FINAL_PERCENTILE; it does not keep its table (the result is not merged in the library)
-constexpr int32_t kBaseClears = PG_QUERY_FLAG_KEEP_DEVICE_TABLE;
-
 }  // namespace
 
-bool has_variance(const pg_query& q) {
-  if (q.flags & (PG_QUERY_FLAG_DISTINCT | PG_QUERY_FLAG_SELECTION)) return false;
-  if (!q.aggregations) return false;
-  for (int a = 0; a < q.n_aggregations; a++) if (is_variance_agg(q.aggregations[a])) return true;
-  return false;
-}
-
-void variance_check(Segment& seg, const pg_query& q) {
-  (void)var_plan(seg, q);
-  SideBaseQuery B;   // ... and what the ordinary part refuses
-  side_base_query(q, is_variance_agg, kBaseClears, B);
-  if (has_percentile(B.q)) { percentile_check(seg, B.q); return; }
-  check_null_handling(seg, B.q);
-  (void)get_plan(seg, B.q.filter, &B.q);
-}
+bool is_variance_agg(const pg_agg_spec& s) { return is_variance_function(s.function); }
+void variance_plan_check(Segment& seg, const pg_query& q) { (void)var_plan(seg, q); }
 
 std::unique_ptr<Result> execute_variance(Segment& seg, const pg_query& q, const CancelToken* cancel) {
   const double t0 = now_ms();
@@ -137,7 +101,7 @@ std::unique_ptr<Result> execute_variance(Segment& seg, const pg_query& q, const 
   const VarPlan P = var_plan(seg, q);
   const double t_plan = now_ms();
   SideBaseQuery B;
-  side_base_query(q, is_variance_agg, kBaseClears, B);
+  side_base_query(q, B);
   SidePass S = side_pass_begin(seg, q, B, P.groups, kWho, cancel);
   const int32_t n_rows = S.n_rows;
   const int64_t M = S.M, n_words = S.n_words;
@@ -159,7 +123,7 @@ std::unique_ptr<Result> execute_variance(Segment& seg, const pg_query& q, const 
     C.first_slot = vc.first_slot;
     C.q1 = pg_var_q1(vc.exp);
     C.q2 = pg_var_q2(vc.exp);
-    doc_bits += vc.col->col_kind == PG_COL_FIXED_BIT ? vc.col->bits : (vc.col->col_kind == PG_COL_RAW32 ? 32 : 64);
+    doc_bits += value_src_bits(*vc.col);
   }
   DeviceBuffer table((size_t)P.n_slots * 8);
   A.table = table.as<int64_t>();
@@ -168,23 +132,13 @@ std::unique_ptr<Result> execute_variance(Segment& seg, const pg_query& q, const 
   timer.start(stream);
   PG_HIP(hipMemsetAsync(table.ptr, 0, (size_t)P.n_slots * 8, stream));
   if (M > 0 && n_words > 0) {
-    const int64_t words_per_wg = P.tier == TIER_LDS ? 32 : 16;
-    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(P.tier == TIER_LDS ? cus : cus * 8, (n_words + words_per_wg - 1) / words_per_wg));
-    pg_var_launch_pass(&A, P.tier, grid, stream);
+    pg_var_launch_pass(&A, P.tier, side_pass_grid(P.tier, cus, n_words), stream);
     PG_HIP(hipGetLastError());
   }
   std::vector<int64_t> got((size_t)n_rows * (size_t)P.slots);
-  if (n_rows > 0) {
-    DeviceBuffer d_rows((size_t)n_rows * 4), d_out(got.size() * 8);
-    PG_HIP(hipMemcpyAsync(d_rows.ptr, S.rows.data(), (size_t)n_rows * 4, hipMemcpyHostToDevice, stream));
-    pg_expr_launch_gather(table.as<int64_t>(), d_rows.as<uint32_t>(), n_rows, P.slots, P.groups.G, d_out.as<int64_t>(),
-                          (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)cus * 8, ((int64_t)got.size() + 255) / 256)), stream);
-    PG_HIP(hipGetLastError());
-    PG_HIP(hipMemcpyAsync(got.data(), d_out.ptr, got.size() * 8, hipMemcpyDeviceToHost, stream));
-    wait_stream(stream, cancel);   // d_rows and d_out go out of scope
-  } else {
-    wait_stream(stream, cancel);
-  }
+  side_gather_rows(S, got, cancel, [&](const uint32_t* rows, int64_t* out) {
+    pg_expr_launch_gather(table.as<int64_t>(), rows, n_rows, P.slots, P.groups.G, out, side_flat_grid(cus, (int64_t)got.size()), stream);
+  });
   const float pass_ms = timer.stop_ms();
   if (q.n_group_by == 0 && got[0] != M)
     fail(PG_ERR_INTERNAL, "variance: %lld docs counted for %lld matching docs", (long long)got[0], (long long)M);
@@ -210,8 +164,7 @@ std::unique_ptr<Result> execute_variance(Segment& seg, const pg_query& q, const 
     for (size_t k = 0; k + 1 < vc.aggs.size(); k++) out[(size_t)vc.aggs[k]] = r;
     out[(size_t)vc.aggs.back()] = std::move(r);
   }
-  const int64_t pass_bytes = ((int64_t)seg.total_docs * doc_bits + 7) / 8 + (S.ds ? n_words * 8 : 0);
-  std::unique_ptr<Result> res = side_pass_finish(seg, q, B, S, out, {kTierKernel[P.tier], pass_bytes, P.n_columns_read, pass_ms, t0, t_plan});
+  std::unique_ptr<Result> res = side_pass_finish(seg, q, B, S, out, {kTierKernel[P.tier], side_pass_bytes(seg, S, 1, doc_bits), P.n_columns_read, pass_ms, t0, t_plan});
   res->variance = true;
   return res;
 }

@@ -32,11 +32,8 @@ namespace {
 
 const char* kWho = "FIRSTWITHTIME / LASTWITHTIME";
 const char* kSubject = "FIRSTWITHTIME / LASTWITHTIME";
-enum Tier { TIER_REG = 0, TIER_LDS = 1, TIER_HBM = 2 };
 const char* const kTierKernel[3] = {"pg_wt_reg", "pg_wt_lds", "pg_wt_hbm"};
 
-bool is_with_time_agg(const pg_agg_spec& s) { return is_with_time_function(s.function); }
-const char* function_text(int32_t fn) { return fn == PG_AGG_FIRSTWITHTIME ? "FIRSTWITHTIME" : "LASTWITHTIME"; }
 
 // the argument list of pg_agg_spec.column: x, t, 'TYPE' (include/pinot_gpu.h: the general form of aggregations with more than one argument)
 struct WtArguments {
@@ -44,7 +41,7 @@ struct WtArguments {
   int32_t type = -1;   // pg_data_type of the declared type
 };
 WtArguments parse_arguments(const pg_agg_spec& s) {
-  const char* fn = function_text(s.function);
+  const char* fn = agg_function_text(s.function);
   if (!s.column) fail(PG_ERR_INVALID_ARGUMENT, "%s needs its argument list: column, time column, 'data type'", fn);
   std::vector<ExprArgument> args;
   std::string error;
@@ -96,19 +93,6 @@ struct WtPlan {
   int n_columns_read = 0;       // distinct columns the query projects (ProjectOperator#getNumColumnsProjected)
 };
 
-// a single-value INT / LONG / FLOAT / DOUBLE column the kernels can read: fixed-bit dictIds with a dictionary on the device, or raw values
-Column* argument_column(Segment& seg, const std::string& name, const char* fn, const char* role, bool null_handling) {
-  Column* c = seg.find(name.c_str());
-  if (!c) fail(PG_ERR_NOT_FOUND, "column not found: %s", name.c_str());
-  if (c->is_mv || c->raw_mv) fail(PG_ERR_UNSUPPORTED, "%s over the multi-value %s %s", fn, role, c->name.c_str());
-  if (c->data_type > PG_TYPE_DOUBLE) fail(PG_ERR_UNSUPPORTED, "%s over the %s %s %s", fn, c->data_type == PG_TYPE_STRING ? "STRING" : "BYTES", role, c->name.c_str());
-  if (null_handling && column_has_nulls(seg, c->name)) fail(PG_ERR_UNSUPPORTED, "enableNullHandling: %s over %s, which holds nulls", fn, c->name.c_str());
-  const bool dict_ok = c->has_dictionary && c->col_kind == PG_COL_FIXED_BIT && c->bits >= 1 && c->bits <= 31 && c->cardinality >= 1 && c->dict_dev.ptr;
-  const bool raw_ok = !c->has_dictionary && (c->col_kind == PG_COL_RAW32 || c->col_kind == PG_COL_RAW64);
-  if (!dict_ok && !raw_ok) fail(PG_ERR_UNSUPPORTED, "%s: %s %s (layout %d, %d bits)", fn, role, c->name.c_str(), c->col_kind, c->bits);
-  return c;
-}
-
 int64_t dict_entry(const Column& c, int32_t id) {   // an INT / LONG dictionary's value (big-endian on the host)
   const uint8_t* p = c.dict_host.data() + (size_t)id * (size_t)c.dict_bytes_per_value;
   uint64_t v = 0;
@@ -144,14 +128,14 @@ WtPlan wt_plan(Segment& seg, const pg_query& q) {
       if (s.column && strcmp(s.column, "*") != 0) read.insert(s.column);
       continue;
     }
-    const char* fn = function_text(s.function);
+    const char* fn = agg_function_text(s.function);
     const WtArguments A = parse_arguments(s);
     WtAgg g;
     g.index = a;
     g.type = A.type;
     g.first = s.function == PG_AGG_FIRSTWITHTIME;
-    g.value = argument_column(seg, A.x, fn, "column", null_handling);
-    Column* t = argument_column(seg, A.t, fn, "time column", null_handling);
+    g.value = side_argument_column(seg, A.x.c_str(), fn, "column", "column", "", null_handling);
+    Column* t = side_argument_column(seg, A.t.c_str(), fn, "time column", "time column", "", null_handling);
     if (t->val_type != PG_V_I32 && t->val_type != PG_V_I64)
       fail(PG_ERR_UNSUPPORTED, "%s with the %s time column %s: an INT or LONG time column runs on the GPU path", fn, t->data_type == PG_TYPE_FLOAT ? "FLOAT" : "DOUBLE", t->name.c_str());
     read.insert(g.value->name);
@@ -181,17 +165,12 @@ WtPlan wt_plan(Segment& seg, const pg_query& q) {
   P.n_slots = P.groups.G * (uint64_t)P.slots.size();   // < 2^35
   const uint64_t bytes = P.n_slots * 8 * (P.any_wide ? 2 : 1);
   const Knobs& K = knobs();
-  if (q.n_group_by == 0) P.tier = TIER_REG;
-  else if (P.n_slots <= (uint64_t)PG_WT_LDS_SLOTS) P.tier = TIER_LDS;
-  else if (bytes <= (uint64_t)K.wt_hbm_max_bytes) P.tier = TIER_HBM;
-  else
+  P.tier = side_tier(q.n_group_by, P.n_slots, PG_WT_LDS_SLOTS, bytes, K.wt_hbm_max_bytes);
+  if (P.tier == TIER_REFUSED)
     fail(PG_ERR_UNSUPPORTED, "FIRSTWITHTIME / LASTWITHTIME: %llu groups x %d slots need a table of %llu bytes, more than PG_WT_HBM_MAX_BYTES (%lld)",
          (unsigned long long)P.groups.G, (int)P.slots.size(), (unsigned long long)bytes, (long long)K.wt_hbm_max_bytes);
   return P;
 }
-
-// the ordinary part may hold a PERCENTILE, which reads PG_QUERY_FLAG_FINAL_PERCENTILE; it does not keep its table (the result is not merged in the library)
-constexpr int32_t kBaseClears = PG_QUERY_FLAG_KEEP_DEVICE_TABLE;
 
 // ---- the Java primitive conversions of get<T>ValuesSV over a column of another stored type (JLS 5.1.2, 5.1.3) -----------------------------------
 int64_t java_d2l(double d) {
@@ -238,13 +217,6 @@ int64_t convert_value(int64_t bits, int32_t stored, int32_t declared) {
 
 bool is_with_time_function(int32_t fn) { return fn == PG_AGG_FIRSTWITHTIME || fn == PG_AGG_LASTWITHTIME; }
 
-bool has_with_time(const pg_query& q) {
-  if (q.flags & (PG_QUERY_FLAG_DISTINCT | PG_QUERY_FLAG_SELECTION)) return false;
-  if (!q.aggregations) return false;
-  for (int a = 0; a < q.n_aggregations; a++) if (is_with_time_agg(q.aggregations[a])) return true;
-  return false;
-}
-
 void with_time_columns_read(const pg_agg_spec& s, std::set<std::string>& read) {
   std::vector<ExprArgument> args;
   std::string error;
@@ -252,15 +224,8 @@ void with_time_columns_read(const pg_agg_spec& s, std::set<std::string>& read) {
   for (int k = 0; k < 2; k++) if (!args[(size_t)k].quoted) read.insert(args[(size_t)k].text);
 }
 
-void with_time_check(Segment& seg, const pg_query& q) {
-  (void)wt_plan(seg, q);
-  SideBaseQuery B;   // ... and what the ordinary part refuses
-  side_base_query(q, is_with_time_agg, kBaseClears, B);
-  if (has_variance(B.q)) { variance_check(seg, B.q); return; }
-  if (has_percentile(B.q)) { percentile_check(seg, B.q); return; }
-  check_null_handling(seg, B.q);
-  (void)get_plan(seg, B.q.filter, &B.q);
-}
+bool is_with_time_agg(const pg_agg_spec& s) { return is_with_time_function(s.function); }
+void with_time_plan_check(Segment& seg, const pg_query& q) { (void)wt_plan(seg, q); }
 
 std::unique_ptr<Result> execute_with_time(Segment& seg, const pg_query& q, const CancelToken* cancel) {
   const double t0 = now_ms();
@@ -268,7 +233,7 @@ std::unique_ptr<Result> execute_with_time(Segment& seg, const pg_query& q, const
   const WtPlan P = wt_plan(seg, q);
   const double t_plan = now_ms();
   SideBaseQuery B;
-  side_base_query(q, is_with_time_agg, kBaseClears, B);
+  side_base_query(q, B);
   SidePass S = side_pass_begin(seg, q, B, P.groups, kWho, cancel);
   const int32_t n_rows = S.n_rows;
   const int64_t M = S.M, n_words = S.n_words;
@@ -291,7 +256,7 @@ std::unique_ptr<Result> execute_with_time(Segment& seg, const pg_query& q, const
     A.slot[s].base = W.base;
     bool counted = false;   // FIRST and LAST over one time column read it once per pass
     for (int k = 0; k < s; k++) counted = counted || P.slots[(size_t)k].time == W.time;
-    if (!counted) doc_bits += W.time->col_kind == PG_COL_FIXED_BIT ? W.time->bits : (W.time->col_kind == PG_COL_RAW32 ? 32 : 64);
+    if (!counted) doc_bits += value_src_bits(*W.time);
   }
   const size_t plane_bytes = (size_t)P.n_slots * 8;
   DeviceBuffer keys(plane_bytes), docs(P.any_wide ? plane_bytes : 8);
@@ -304,11 +269,10 @@ std::unique_ptr<Result> execute_with_time(Segment& seg, const pg_query& q, const
   PG_HIP(hipMemsetAsync(keys.ptr, 0, plane_bytes, stream));
   if (P.any_wide) PG_HIP(hipMemsetAsync(docs.ptr, 0, plane_bytes, stream));
   if (M > 0 && n_words > 0) {
-    const int64_t words_per_wg = P.tier == TIER_LDS ? 32 : 16;
     // the LDS tier's workgroups are persistent: one per CU for a full table, up to four (32 waves) where the tables are small enough to
     // share the CU's LDS — the loop keeps one load per wave in flight, so the waves per CU decide how much of the bandwidth it reaches
     const int64_t lds_wgs = std::max<int64_t>(1, std::min<int64_t>(4, (int64_t)PG_WT_LDS_SLOTS / (int64_t)std::max<uint64_t>(1, P.n_slots)));
-    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(P.tier == TIER_LDS ? cus * lds_wgs : cus * 8, (n_words + words_per_wg - 1) / words_per_wg));
+    const int grid = side_pass_grid(P.tier, cus, n_words, lds_wgs);
     for (int pass = 0; pass < passes; pass++) {   // the second pass reads the first one's maxima: stream order
       A.pass = pass;
       pg_wt_launch_pass(&A, P.tier, grid, stream);
@@ -317,33 +281,25 @@ std::unique_ptr<Result> execute_with_time(Segment& seg, const pg_query& q, const
   }
   const int width = 2 * n_slots + n_aggs;
   std::vector<int64_t> got((size_t)n_rows * (size_t)width);
-  if (n_rows > 0) {
+  side_gather_rows(S, got, cancel, [&](const uint32_t* rows, int64_t* d_out) {
     PgWtGatherArgs Gt;
     memset(&Gt, 0, sizeof(Gt));
-    DeviceBuffer d_rows((size_t)n_rows * 4), d_out(got.size() * 8);
-    PG_HIP(hipMemcpyAsync(d_rows.ptr, S.rows.data(), (size_t)n_rows * 4, hipMemcpyHostToDevice, stream));
     Gt.keys = A.keys;
     Gt.docs = A.docs;
-    Gt.rows = d_rows.as<uint32_t>();
+    Gt.rows = rows;
     Gt.n_rows = n_rows;
     Gt.slots = n_slots;
     Gt.n_aggs = n_aggs;
     Gt.doc_bits = P.doc_bits;
     Gt.n_docs = seg.total_docs;
-    Gt.out = d_out.as<int64_t>();
+    Gt.out = d_out;
     for (int s = 0; s < n_slots; s++) Gt.slot[s] = A.slot[s];
     for (int k = 0; k < n_aggs; k++) {
       expr_fill_src(Gt.value[k], *P.aggs[(size_t)k].value);
       Gt.value_slot[k] = P.aggs[(size_t)k].slot;
     }
-    const int64_t items = (int64_t)n_rows * (n_slots + n_aggs);
-    pg_wt_launch_gather(&Gt, (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)cus * 8, (items + 255) / 256)), stream);
-    PG_HIP(hipGetLastError());
-    PG_HIP(hipMemcpyAsync(got.data(), d_out.ptr, got.size() * 8, hipMemcpyDeviceToHost, stream));
-    wait_stream(stream, cancel);   // d_rows and d_out go out of scope
-  } else {
-    wait_stream(stream, cancel);
-  }
+    pg_wt_launch_gather(&Gt, side_flat_grid(cus, (int64_t)n_rows * (n_slots + n_aggs)), stream);
+  });
   const float pass_ms = timer.stop_ms();
   // ---- the pairs: (value, time) of the winner doc; the function's default pair over no doc (a query without GROUP BY only) ---------------------------
   const bool empty_ok = q.n_group_by == 0 && M == 0;
@@ -388,7 +344,7 @@ std::unique_ptr<Result> execute_with_time(Segment& seg, const pg_query& q, const
     out[(size_t)g.index] = std::move(r);
   }
   // the match words and the time and group columns once per pass, the gathered docs, times and values
-  const int64_t pass_bytes = passes * (((int64_t)seg.total_docs * doc_bits + 7) / 8 + (S.ds ? n_words * 8 : 0)) + (int64_t)got.size() * 8;
+  const int64_t pass_bytes = side_pass_bytes(seg, S, passes, doc_bits, (int64_t)got.size() * 8);
   std::unique_ptr<Result> res = side_pass_finish(seg, q, B, S, out, {kTierKernel[P.tier], pass_bytes, P.n_columns_read, pass_ms, t0, t_plan});
   res->with_time = true;
   return res;

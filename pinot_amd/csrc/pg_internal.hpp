@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -573,7 +574,6 @@ struct SideGroups {
   std::vector<std::shared_ptr<Column>> keep;    // the derived columns among group_cols (expression keys)
 };
 SideGroups side_groups(Segment& seg, const pg_query& q, const char* subject, const char* who, std::set<std::string>& read);   // seg.mu held; adds the columns' names to `read`
-void side_base_query(const pg_query& q, bool (*is_side)(const pg_agg_spec&), int32_t clear_flags, SideBaseQuery& out);   // pg_side_query.h, failing through fail()
 // the ordinary part's result, the filter's match words and the admitted groups' rows (rows[i]: the mixed-radix key of group i)
 struct SidePass {
   std::unique_ptr<Result> res;
@@ -610,10 +610,34 @@ struct SidePassStats {
 // the ordinary part's columns and null vectors moved to their places in `out` (through B.base_index), `out` made the result's aggregations,
 // every statistic of the query written, the schema filled
 std::unique_ptr<Result> side_pass_finish(Segment& seg, const pg_query& q, const SideBaseQuery& B, SidePass& S, std::vector<AggResult>& out, const SidePassStats& P);
-// Queries with a PERCENTILE aggregation (pg_exec_percentile.hip): percentile_check are the checks of the path (pg_query_supported);
-// execute_percentile runs the ordinary part and one counting pass per distinct percentile column.
-bool has_percentile(const pg_query& q);
-void percentile_check(Segment& seg, const pg_query& q);
+// ---- the slot-table paths (expressions, the variance family, FIRSTWITHTIME / LASTWITHTIME): a table [G][slots] of 64-bit slots, filled over
+// the match words by one of three tiers (side_tier, pg_side_query.h; the kernels' half is pg_side_scan.h) and gathered for the admitted rows
+int side_pass_grid(int tier, int cus, int64_t n_words, int64_t lds_wgs_per_cu = 1);   // workgroups of a tier's pass: persistent ones in the LDS tier
+int side_flat_grid(int cus, int64_t items);                                           // ... of a kernel with one thread per item (256 per workgroup)
+int64_t value_src_bits(const Column& c);                                              // bits a kernel reads per doc of a value column
+// S.rows uploaded, launch(rows on the device, out on the device) run, `got` copied back from `out`, the stream drained (also without rows)
+void side_gather_rows(const SidePass& S, std::vector<int64_t>& got, const CancelToken* cancel, const std::function<void(const uint32_t*, int64_t*)>& launch);
+// the algorithmic bytes of `passes` passes over `doc_bits` bits per doc and the match words, plus `extra`
+int64_t side_pass_bytes(const Segment& seg, const SidePass& S, int passes, int64_t doc_bits, int64_t extra = 0);
+// The admission of an aggregation's argument column (seg.mu held): found, single-value, numeric, without nulls under null handling and — with
+// `layout_role` — readable by the kernels: fixed-bit dictIds with a dictionary on the device, or raw values.  `fn` names the function, `role` and
+// `layout_role` the column ("column", "time column", "argument column") and `mv_note` ends the multi-value refusal, as the paths' messages differ.
+Column* side_argument_column(Segment& seg, const char* name, const char* fn, const char* role, const char* layout_role, const char* mv_note, bool null_handling);
+const char* agg_function_text(int32_t fn);   // "VAR_POP", "FIRSTWITHTIME", ...: the functions the side paths name in messages
+// ---- the side paths: one entry per family in kSidePaths (pg_exec_sidepass.hip), in nesting order — the only statement of that order.  A new
+// family declares its three functions below and adds its entry; pg_query_supported (side_check) and pg_query_exec (execute_query) follow the table.
+struct SidePath {
+  bool (*is_side)(const pg_agg_spec&);            // is this aggregation answered by the path?
+  void (*plan_check)(Segment&, const pg_query&);  // plans the path's aggregations and group-by columns and drops the plan: its refusals
+  std::unique_ptr<Result> (*execute)(Segment&, const pg_query&, const CancelToken*);
+  int32_t base_clears;                            // PG_QUERY_FLAG_* bits its ordinary part must not see
+};
+const SidePath* side_path_of(const pg_query& q);     // the outermost path with an aggregation in `q`; null: none, or a DISTINCT / selection query
+void side_check(Segment& seg, const pg_query& q);    // every nested path's plan_check, then the checks and the cached plan of the innermost ordinary part
+void side_base_query(const pg_query& q, SideBaseQuery& out);   // `q` without the aggregations of its outermost path (pg_side_query.h), failing through fail()
+// exact PERCENTILE (pg_exec_percentile.hip): the ordinary part and one counting pass per distinct percentile column
+bool is_percentile_agg(const pg_agg_spec& s);
+void percentile_plan_check(Segment& seg, const pg_query& q);
 std::unique_ptr<Result> execute_percentile(Segment& seg, const pg_query& q, const CancelToken* cancel);
 // ... its sort tier's runs (pg_kernels_percentile.hip): the matching docs' keys written compacted, sorted over their significant bits and
 // run-length encoded on `stream`; returns after the stream drained (the number of runs is read back)
@@ -624,27 +648,24 @@ struct PctlSortRuns {
 };
 size_t pctl_sort_bytes(int64_t n_matches);   // bytes of the work area (keys in and out, runs, rocprim's temporaries)
 void pctl_sort_build(const PgPctlArgs& A, int64_t n_matches, int key_bits, hipStream_t stream, PctlSortRuns& out);
-// Queries with an aggregation over an arithmetic expression (pg_exec_expr.hip): SUM / MIN / MAX / AVG / MINMAXRANGE whose pg_agg_spec.column
-// is an expression text (pg_expr.h).  A bounds pass per (segment, expression), one accumulation pass for all expressions of the query.
-// expression_check: the checks of the path (pg_query_supported); the bounds are answered from the segment's cache when it is filled, else
-// the shape is let through.
-bool has_expression(const pg_query& q);
-void expression_check(Segment& seg, const pg_query& q);
+// aggregations over an arithmetic expression (pg_exec_expr.hip): SUM / MIN / MAX / AVG / MINMAXRANGE whose pg_agg_spec.column is an expression
+// text (pg_expr.h).  A bounds pass per (segment, expression), one accumulation pass for all expressions of the query.  Its plan_check answers
+// the bounds from the segment's cache when it is filled, else the shape is let through.
+bool is_expression_agg(const pg_agg_spec& s);
+void expression_plan_check(Segment& seg, const pg_query& q);
 std::unique_ptr<Result> execute_expression(Segment& seg, const pg_query& q, const CancelToken* cancel);
-// Queries with a VAR_POP / VAR_SAMP / STDDEV_POP / STDDEV_SAMP aggregation (pg_exec_var.hip): one accumulation pass of exact power sums
-// (pg_moments.h) for all of them.  variance_check: the checks of the path (pg_query_supported).
-bool has_variance(const pg_query& q);
-void variance_check(Segment& seg, const pg_query& q);
+// VAR_POP / VAR_SAMP / STDDEV_POP / STDDEV_SAMP (pg_exec_var.hip): one accumulation pass of exact power sums (pg_moments.h) for all of them
+bool is_variance_agg(const pg_agg_spec& s);
+void variance_plan_check(Segment& seg, const pg_query& q);
 std::unique_ptr<Result> execute_variance(Segment& seg, const pg_query& q, const CancelToken* cancel);
-// Queries with a FIRSTWITHTIME / LASTWITHTIME aggregation (pg_exec_withtime.hip): one arg-max pass (two in wide mode, pg_with_time.h) for
-// all of them and a gather of the winners' values.  with_time_check: the checks of the path (pg_query_supported).  with_time_columns_read:
-// the argument columns of such an aggregation, whose pg_agg_spec.column is an argument list, added to `read` (an outer side pass counts
-// them; a malformed list adds nothing — the path's own checks refuse it).
+// FIRSTWITHTIME / LASTWITHTIME (pg_exec_withtime.hip): one arg-max pass (two in wide mode, pg_with_time.h) for all of them and a gather of the
+// winners' values.  with_time_columns_read: the argument columns of such an aggregation, whose pg_agg_spec.column is an argument list, added
+// to `read` (an outer side pass counts them; a malformed list adds nothing — the path's own checks refuse it).
 bool is_with_time_function(int32_t fn);
-bool has_with_time(const pg_query& q);
-void with_time_check(Segment& seg, const pg_query& q);
-void with_time_columns_read(const pg_agg_spec& s, std::set<std::string>& read);
+bool is_with_time_agg(const pg_agg_spec& s);
+void with_time_plan_check(Segment& seg, const pg_query& q);
 std::unique_ptr<Result> execute_with_time(Segment& seg, const pg_query& q, const CancelToken* cancel);
+void with_time_columns_read(const pg_agg_spec& s, std::set<std::string>& read);
 std::unique_ptr<Result> execute_query_plain(Segment& seg, const pg_query& q, const CancelToken* cancel);   // ... the executor proper (pg_exec.hip)
 void fill_result_schema(Segment& seg, const pg_query& q, Result& r);
 int64_t hll_cardinality(const uint8_t* regs, int log2m);   // HyperLogLog#cardinality of one register row (pg_exec.hip)

@@ -9,10 +9,10 @@
 //                   wavefront and slot at the end
 //   pg_expr_lds     up to PG_EXPR_LDS_SLOTS slots: one persistent workgroup per CU, 64-bit LDS atomics, one flush of the touched slots
 //   pg_expr_hbm     beyond that: global 64-bit atomics
-// All three walk the filter's match words (none: every doc) as pg_pctl_* do: a wavefront takes kWordsPerWave 64-doc words per iteration, lane =
-// doc.  The program is wave-uniform (kernel arguments): its branches are scalar, the operands and intermediate results live in vector
-// registers indexed through the scalar index — no scratch (the resource log of this file is checked by tests/test_gpu_expressions.py).
-// A plain tile loop, not a software pipeline.  Kernel names are stable; the executor reports the tier's (pg_exec_expr.hip).
+// All three walk the filter's match words (none: every doc) with side_scan_walk of pg_side_scan.h, which also holds the table tiers'
+// skeleton, the wavefront reductions and the launcher.  The program is wave-uniform (kernel arguments): its branches are scalar, the
+// operands and intermediate results live in vector registers indexed through the scalar index — no scratch (the resource log of this file
+// is checked by tests/test_gpu_expressions.py).  Kernel names are stable; the executor reports the tier's (pg_exec_expr.hip).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -21,6 +21,8 @@
 #include "pg_expr_device.h"
 
 #pragma clang fp contract(off)
+
+#include "pg_side_scan.h"   // after the pragma: what is instantiated from it is not contracted either
 
 #define DEVFN __device__ __forceinline__
 
@@ -34,21 +36,6 @@ DEVFN int64_t expr_order_key(double v) {   // order-preserving map double -> int
   const int64_t b = __double_as_longlong(v);
   return b ^ ((b >> 63) & 0x7FFFFFFFFFFFFFFFLL);
 }
-
-DEVFN int64_t wave_sum_i64(int64_t v) {
-  for (int off = 32; off > 0; off >>= 1) v += (int64_t)__shfl_xor((long long)v, off);
-  return v;
-}
-DEVFN int64_t wave_min_i64(int64_t v) {
-  for (int off = 32; off > 0; off >>= 1) { const int64_t o = (int64_t)__shfl_xor((long long)v, off); v = o < v ? o : v; }
-  return v;
-}
-DEVFN int64_t wave_max_i64(int64_t v) {
-  for (int off = 32; off > 0; off >>= 1) { const int64_t o = (int64_t)__shfl_xor((long long)v, off); v = o > v ? o : v; }
-  return v;
-}
-
-constexpr int kWordsPerWave = 4;
 
 // the tiers with a table: `row0` is the table's first slot — the workgroup's copy in LDS, or the table in HBM
 template <typename Ptr>
@@ -79,38 +66,16 @@ DEVFN void expr_update(const PgExprArgs& a, Ptr row0, uint32_t doc) {
 
 template <bool LDS>
 DEVFN void expr_table_body(const PgExprArgs& a) {
-  extern __shared__ int64_t s_tab[];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int waves = blockDim.x >> 6;
-  if (LDS) {
-    for (uint32_t i = threadIdx.x; i < (uint32_t)a.n_slots; i += blockDim.x) s_tab[i] = a.ident[i % (uint32_t)a.slots];
-    __syncthreads();
-  }
-  const int64_t stride = (int64_t)gridDim.x * waves * kWordsPerWave;
-  for (int64_t w0 = ((int64_t)blockIdx.x * waves + wave) * kWordsPerWave; w0 < a.scan.n_words; w0 += stride) {
-#pragma unroll 1
-    for (int u = 0; u < kWordsPerWave; u++) {
-      const int64_t w = w0 + u;
-      if (w >= a.scan.n_words) break;
-      const uint64_t m = pg_scan_match_word(a.scan, w);
-      if (m == 0) continue;   // a word without a match costs one scalar load
-      if ((m >> lane) & 1) {
-        if (LDS) expr_update(a, s_tab, (uint32_t)(w * 64 + lane));
-        else expr_update(a, a.table, (uint32_t)(w * 64 + lane));
-      }
-    }
-  }
-  if (LDS) {
-    __syncthreads();
-    for (uint32_t i = threadIdx.x; i < (uint32_t)a.n_slots; i += blockDim.x) {   // only the touched slots
-      const int64_t v = s_tab[i], id = a.ident[i % (uint32_t)a.slots];
-      if (v == id) continue;
-      if (id == 0) atomicAdd(reinterpret_cast<unsigned long long*>(a.table + i), (unsigned long long)v);
-      else if (id > 0) atomicMin(reinterpret_cast<long long*>(a.table + i), (long long)v);
-      else atomicMax(reinterpret_cast<long long*>(a.table + i), (long long)v);
-    }
-  }
+  side_table_pass<LDS>(
+      a.scan, a.n_slots, a.table, [&](uint32_t i) PG_SIDE_INLINE { return a.ident[i % (uint32_t)a.slots]; },
+      [&](int64_t* tab, uint32_t doc) PG_SIDE_INLINE { expr_update(a, tab, doc); },
+      [&](uint32_t i, int64_t v) PG_SIDE_INLINE {   // only the touched slots
+        const int64_t id = a.ident[i % (uint32_t)a.slots];
+        if (v == id) return;
+        if (id == 0) atomicAdd(reinterpret_cast<unsigned long long*>(a.table + i), (unsigned long long)v);
+        else if (id > 0) atomicMin(reinterpret_cast<long long*>(a.table + i), (long long)v);
+        else atomicMax(reinterpret_cast<long long*>(a.table + i), (long long)v);
+      });
 }
 
 }  // namespace
@@ -122,8 +87,6 @@ extern "C" __global__ void __launch_bounds__(256) pg_expr_hbm(const PgExprArgs a
 // docs: no int64 overflows); one reduction across the wavefront and one global atomic per slot at the end.
 extern "C" __global__ void __launch_bounds__(256) pg_expr_reg(const PgExprArgs a) {
   const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int waves = blockDim.x >> 6;
   int64_t sum[PG_EXPR_MAX_EXPRS][PG_EXPR_SUM_LIMBS], mn[PG_EXPR_MAX_EXPRS], mx[PG_EXPR_MAX_EXPRS], count = 0;
 #pragma unroll
   for (int e = 0; e < PG_EXPR_MAX_EXPRS; e++) {
@@ -132,36 +95,27 @@ extern "C" __global__ void __launch_bounds__(256) pg_expr_reg(const PgExprArgs a
 #pragma unroll
     for (int l = 0; l < PG_EXPR_SUM_LIMBS; l++) sum[e][l] = 0;
   }
-  const int64_t stride = (int64_t)gridDim.x * waves * kWordsPerWave;
-  for (int64_t w0 = ((int64_t)blockIdx.x * waves + wave) * kWordsPerWave; w0 < a.scan.n_words; w0 += stride) {
+  side_scan_walk(a.scan, [&](uint32_t doc) PG_SIDE_INLINE {
+    const d8 s = expr_load_all(a, doc);
+    count++;
+    d4 vals = {0, 0, 0, 0};
 #pragma unroll 1
-    for (int u = 0; u < kWordsPerWave; u++) {
-      const int64_t w = w0 + u;
-      if (w >= a.scan.n_words) break;
-      const uint64_t m = pg_scan_match_word(a.scan, w);
-      if (m == 0) continue;
-      if (!((m >> lane) & 1)) continue;
-      const d8 s = expr_load_all(a, (uint32_t)(w * 64 + lane));
-      count++;
-      d4 vals = {0, 0, 0, 0};
-#pragma unroll 1
-      for (int e = 0; e < a.n_exprs; e++) vals[e & 3] = expr_eval(a, e, s);   // wave-uniform; the accumulators below are indexed statically
+    for (int e = 0; e < a.n_exprs; e++) vals[e & 3] = expr_eval(a, e, s);   // wave-uniform; the accumulators below are indexed statically
 #pragma unroll
-      for (int e = 0; e < PG_EXPR_MAX_EXPRS; e++) {
-        if (e < a.n_exprs) {
-          const PgExprDesc& X = a.exprs[e];
-          const double v = vals[e];
-          if (X.acc & PG_EXPR_ACC_SUM) {
+    for (int e = 0; e < PG_EXPR_MAX_EXPRS; e++) {
+      if (e < a.n_exprs) {
+        const PgExprDesc& X = a.exprs[e];
+        const double v = vals[e];
+        if (X.acc & PG_EXPR_ACC_SUM) {
 #pragma unroll
-            for (int l = 0; l < PG_EXPR_SUM_LIMBS; l++) sum[e][l] += pg_fx_digit(v, X.q, l);
-          }
-          const int64_t key = expr_order_key(v);
-          mn[e] = key < mn[e] ? key : mn[e];
-          mx[e] = key > mx[e] ? key : mx[e];
+          for (int l = 0; l < PG_EXPR_SUM_LIMBS; l++) sum[e][l] += pg_fx_digit(v, X.q, l);
         }
+        const int64_t key = expr_order_key(v);
+        mn[e] = key < mn[e] ? key : mn[e];
+        mx[e] = key > mx[e] ? key : mx[e];
       }
     }
-  }
+  });
 #pragma unroll
   for (int e = 0; e < PG_EXPR_MAX_EXPRS; e++) {
     if (e < a.n_exprs) {
@@ -234,17 +188,8 @@ void pg_expr_launch_init(const PgExprArgs* args, int grid, hipStream_t stream) {
   const PgExprArgs a = *args;
   hipLaunchKernelGGL(pg_expr_init, dim3(grid), dim3(256), 0, stream, a);
 }
-// tier: 0 pg_expr_reg, 1 pg_expr_lds, 2 pg_expr_hbm
 void pg_expr_launch_pass(const PgExprArgs* args, int tier, int grid, hipStream_t stream) {
-  const PgExprArgs a = *args;
-  if (tier == 1) {
-    PG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(pg_expr_lds), hipFuncAttributeMaxDynamicSharedMemorySize, PG_EXPR_LDS_SLOTS * 8));
-    hipLaunchKernelGGL(pg_expr_lds, dim3(grid), dim3(512), (size_t)a.n_slots * 8, stream, a);
-  } else if (tier == 2) {
-    hipLaunchKernelGGL(pg_expr_hbm, dim3(grid), dim3(256), 0, stream, a);
-  } else {
-    hipLaunchKernelGGL(pg_expr_reg, dim3(grid), dim3(256), 0, stream, a);
-  }
+  side_launch_pass(pg_expr_reg, pg_expr_lds, pg_expr_hbm, PG_EXPR_LDS_SLOTS * 8, *args, (size_t)args->n_slots * 8, tier, grid, stream);
 }
 void pg_expr_launch_gather(const int64_t* table, const uint32_t* rows, int32_t n_rows, int32_t slots, uint64_t n_groups, int64_t* out, int grid, hipStream_t stream) {
   hipLaunchKernelGGL(pg_expr_gather, dim3(grid), dim3(256), 0, stream, table, rows, n_rows, slots, n_groups, out);

@@ -8,11 +8,11 @@
 //   pg_var_lds   up to PG_VAR_LDS_SLOTS slots: one persistent workgroup per CU, 64-bit LDS atomics, zero digits skipped, one flush of the
 //                touched slots
 //   pg_var_hbm   beyond that: global 64-bit atomics
-// All three walk the filter's match words (none: every doc) as pg_expr_* / pg_pctl_* do: a wavefront takes kWordsPerWave 64-doc words per
-// iteration, lane = doc.  The columns and their type split (integer path or digits of a double) are kernel arguments: wave-uniform, scalar
-// branches; the register tier indexes its accumulators statically — no scratch (the resource log of this file is checked by
-// tests/test_gpu_variance.py).  A plain tile loop, not a software pipeline.  The table is zeroed by a memset and its admitted rows are
-// gathered by pg_expr_gather (pg_kernels_expr.hip).  Kernel names are stable; the executor reports the tier's (pg_exec_var.hip).
+// All three walk the filter's match words (none: every doc) with side_scan_walk of pg_side_scan.h, which also holds the table tiers'
+// skeleton, the wavefront sum and the launcher.  The columns and their type split (integer path or digits of a double) are kernel
+// arguments: wave-uniform, scalar branches; the register tier indexes its accumulators statically — no scratch (the resource log of this
+// file is checked by tests/test_gpu_variance.py).  The table is zeroed by a memset and its admitted rows are gathered by pg_expr_gather
+// (pg_kernels_expr.hip).  Kernel names are stable; the executor reports the tier's (pg_exec_var.hip).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -20,17 +20,11 @@
 #include "pg_fixed_point.h"
 #include "pg_moments.h"
 #include "pg_expr_device.h"
+#include "pg_side_scan.h"
 
 #define DEVFN __device__ __forceinline__
 
 namespace {
-
-constexpr int kWordsPerWave = 4;
-
-DEVFN int64_t wave_sum_i64(int64_t v) {
-  for (int off = 32; off > 0; off >>= 1) v += (int64_t)__shfl_xor((long long)v, off);
-  return v;
-}
 
 // an INT column's value: raw big-endian, or through its INT dictionary
 DEVFN int64_t var_load_int(const PgValueSrc& S, uint32_t doc) {
@@ -72,35 +66,11 @@ DEVFN void var_update(const PgVarArgs& a, Ptr row0, uint32_t doc) {
 
 template <bool LDS>
 DEVFN void var_table_body(const PgVarArgs& a) {
-  extern __shared__ int64_t s_tab[];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int waves = blockDim.x >> 6;
-  if (LDS) {
-    for (uint32_t i = threadIdx.x; i < (uint32_t)a.n_slots; i += blockDim.x) s_tab[i] = 0;
-    __syncthreads();
-  }
-  const int64_t stride = (int64_t)gridDim.x * waves * kWordsPerWave;
-  for (int64_t w0 = ((int64_t)blockIdx.x * waves + wave) * kWordsPerWave; w0 < a.scan.n_words; w0 += stride) {
-#pragma unroll 1
-    for (int u = 0; u < kWordsPerWave; u++) {
-      const int64_t w = w0 + u;
-      if (w >= a.scan.n_words) break;
-      const uint64_t m = pg_scan_match_word(a.scan, w);
-      if (m == 0) continue;   // a word without a match costs one scalar load
-      if ((m >> lane) & 1) {
-        if (LDS) var_update(a, s_tab, (uint32_t)(w * 64 + lane));
-        else var_update(a, a.table, (uint32_t)(w * 64 + lane));
-      }
-    }
-  }
-  if (LDS) {
-    __syncthreads();
-    for (uint32_t i = threadIdx.x; i < (uint32_t)a.n_slots; i += blockDim.x) {   // only the touched slots
-      const int64_t v = s_tab[i];
-      if (v) atomicAdd(reinterpret_cast<unsigned long long*>(a.table + i), (unsigned long long)v);
-    }
-  }
+  side_table_pass<LDS>(
+      a.scan, a.n_slots, a.table, [](uint32_t) PG_SIDE_INLINE { return (int64_t)0; }, [&](int64_t* tab, uint32_t doc) PG_SIDE_INLINE { var_update(a, tab, doc); },
+      [&](uint32_t i, int64_t v) PG_SIDE_INLINE {   // only the touched slots
+        if (v) atomicAdd(reinterpret_cast<unsigned long long*>(a.table + i), (unsigned long long)v);
+      });
 }
 
 }  // namespace
@@ -112,46 +82,43 @@ extern "C" __global__ void __launch_bounds__(256) pg_var_hbm(const PgVarArgs a) 
 // per slot at the end.
 extern "C" __global__ void __launch_bounds__(256) pg_var_reg(const PgVarArgs a) {
   const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int waves = blockDim.x >> 6;
   int64_t acc[PG_VAR_MAX_COLS][PG_VAR_DBL_SLOTS], count = 0;
 #pragma unroll
   for (int c = 0; c < PG_VAR_MAX_COLS; c++) {
 #pragma unroll
     for (int l = 0; l < PG_VAR_DBL_SLOTS; l++) acc[c][l] = 0;
   }
-  const int64_t stride = (int64_t)gridDim.x * waves * kWordsPerWave;
-  for (int64_t w0 = ((int64_t)blockIdx.x * waves + wave) * kWordsPerWave; w0 < a.scan.n_words; w0 += stride) {
-#pragma unroll 1
-    for (int u = 0; u < kWordsPerWave; u++) {
-      const int64_t w = w0 + u;
-      if (w >= a.scan.n_words) break;
-      const uint64_t m = pg_scan_match_word(a.scan, w);
-      if (m == 0) continue;
-      if (!((m >> lane) & 1)) continue;
-      const uint32_t doc = (uint32_t)(w * 64 + lane);
-      count++;
+  side_scan_walk(a.scan, [&](uint32_t doc) PG_SIDE_INLINE {
+    count++;
 #pragma unroll
-      for (int c = 0; c < PG_VAR_MAX_COLS; c++) {
-        if (c < a.n_cols) {   // wave-uniform
-          const PgVarCol& C = a.cols[c];
-          if (C.is_int) {
-            const int64_t x = var_load_int(C.src, doc);
-            const int64_t sq = x * x;
-            acc[c][0] += x;
-            acc[c][1] += pg_long_digit(sq, 0);
-            acc[c][2] += pg_long_digit(sq, 1);
-          } else {
-            const double v = expr_load(C.src, doc);
+    for (int c = 0; c < PG_VAR_MAX_COLS; c++) {
+      if (c < a.n_cols) {   // wave-uniform
+        const PgVarCol& C = a.cols[c];
+        // What the doc adds to the slots both paths have is added after the branch that tells the paths apart, as values: additions at
+        // the end of both of its arms would be merged into one through a pointer, and the accumulator behind it would leave its register
+        // (seen as scratch in the resource log).
+        static_assert(PG_VAR_INT_SLOTS <= PG_VAR_SUM_LIMBS, "the double path's first digits are digits of the sum");
+        int64_t d[PG_VAR_INT_SLOTS];
+        if (C.is_int) {
+          const int64_t x = var_load_int(C.src, doc);
+          const int64_t sq = x * x;
+          d[0] = x;
+          d[1] = pg_long_digit(sq, 0);
+          d[2] = pg_long_digit(sq, 1);
+        } else {
+          const double v = expr_load(C.src, doc);
 #pragma unroll
-            for (int l = 0; l < PG_VAR_SUM_LIMBS; l++) acc[c][l] += pg_fx_digit(v, C.q1, l);
+          for (int l = 0; l < PG_VAR_INT_SLOTS; l++) d[l] = pg_fx_digit(v, C.q1, l);
 #pragma unroll
-            for (int l = 0; l < PG_VAR_SQ_LIMBS; l++) acc[c][PG_VAR_SUM_LIMBS + l] += (int64_t)pg_sq_digit(v, C.q2, l);
-          }
+          for (int l = PG_VAR_INT_SLOTS; l < PG_VAR_SUM_LIMBS; l++) acc[c][l] += pg_fx_digit(v, C.q1, l);
+#pragma unroll
+          for (int l = 0; l < PG_VAR_SQ_LIMBS; l++) acc[c][PG_VAR_SUM_LIMBS + l] += (int64_t)pg_sq_digit(v, C.q2, l);
         }
+#pragma unroll
+        for (int l = 0; l < PG_VAR_INT_SLOTS; l++) acc[c][l] += d[l];
       }
     }
-  }
+  });
   {
     const int64_t v = wave_sum_i64(count);
     if (lane == 0 && v) atomicAdd(reinterpret_cast<unsigned long long*>(a.table), (unsigned long long)v);
@@ -171,15 +138,6 @@ extern "C" __global__ void __launch_bounds__(256) pg_var_reg(const PgVarArgs a) 
 }
 
 // ---- launcher (pg_exec_var.hip) ---------------------------------------------------------------------------------------------------------------
-// tier: 0 pg_var_reg, 1 pg_var_lds, 2 pg_var_hbm
 void pg_var_launch_pass(const PgVarArgs* args, int tier, int grid, hipStream_t stream) {
-  const PgVarArgs a = *args;
-  if (tier == 1) {
-    PG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(pg_var_lds), hipFuncAttributeMaxDynamicSharedMemorySize, PG_VAR_LDS_SLOTS * 8));
-    hipLaunchKernelGGL(pg_var_lds, dim3(grid), dim3(512), (size_t)a.n_slots * 8, stream, a);
-  } else if (tier == 2) {
-    hipLaunchKernelGGL(pg_var_hbm, dim3(grid), dim3(256), 0, stream, a);
-  } else {
-    hipLaunchKernelGGL(pg_var_reg, dim3(grid), dim3(256), 0, stream, a);
-  }
+  side_launch_pass(pg_var_reg, pg_var_lds, pg_var_hbm, PG_VAR_LDS_SLOTS * 8, *args, (size_t)args->n_slots * 8, tier, grid, stream);
 }

@@ -10,29 +10,21 @@
 //                LDS atomic max, one flush of the non-empty slots
 //   pg_wt_hbm    beyond that: global 64-bit atomic max
 //   pg_wt_gather per admitted row the winner doc of every slot, its time and the value columns read at it
-// All three passes walk the filter's match words (none: every doc) as pg_var_* do: a wavefront takes kWordsPerWave 64-doc words per
-// iteration, lane = doc.  The time columns' kinds and the slots' modes are kernel arguments: wave-uniform, scalar branches; the register tier
-// indexes its keys statically — no scratch (the resource log of this file is checked by tests/test_gpu_with_time.py).  A plain tile loop, not
-// a software pipeline.  Both planes are zeroed by a memset.  Kernel names are stable; the executor reports the tier's (pg_exec_withtime.hip).
+// All three passes walk the filter's match words (none: every doc) with side_scan_walk of pg_side_scan.h, which also holds the table tiers'
+// skeleton, the wavefront maximum and the launcher.  The time columns' kinds and the slots' modes are kernel arguments: wave-uniform, scalar
+// branches; the register tier indexes its keys statically — no scratch (the resource log of this file is checked by
+// tests/test_gpu_with_time.py).  Both planes are zeroed by a memset.  Kernel names are stable; the executor reports the tier's
+// (pg_exec_withtime.hip).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "pg_internal.hpp"
 #include "pg_with_time.h"
+#include "pg_side_scan.h"
 
 #define DEVFN __device__ __forceinline__
 
 namespace {
-
-constexpr int kWordsPerWave = 4;
-
-DEVFN unsigned long long wave_max_u64(unsigned long long v) {
-  for (int off = 32; off > 0; off >>= 1) {
-    const unsigned long long o = (unsigned long long)__shfl_xor((long long)v, off);
-    v = o > v ? o : v;
-  }
-  return v;
-}
 
 // a time column's value as getLongValuesSV gives it: INT sign-extended, LONG as it is; raw big-endian, or through the dictionary
 DEVFN int64_t wt_load_time(const PgValueSrc& S, uint32_t doc) {
@@ -87,36 +79,12 @@ DEVFN void wt_update(const PgWtArgs& a, Ptr tab, uint32_t doc) {
 
 template <bool LDS>
 DEVFN void wt_table_body(const PgWtArgs& a) {
-  extern __shared__ unsigned long long s_wt[];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int waves = blockDim.x >> 6;
   unsigned long long* plane = a.pass == 0 ? a.keys : a.docs;
-  if (LDS) {
-    for (uint32_t i = threadIdx.x; i < (uint32_t)a.n_slots; i += blockDim.x) s_wt[i] = 0;
-    __syncthreads();
-  }
-  const int64_t stride = (int64_t)gridDim.x * waves * kWordsPerWave;
-  for (int64_t w0 = ((int64_t)blockIdx.x * waves + wave) * kWordsPerWave; w0 < a.scan.n_words; w0 += stride) {
-#pragma unroll 1
-    for (int u = 0; u < kWordsPerWave; u++) {
-      const int64_t w = w0 + u;
-      if (w >= a.scan.n_words) break;
-      const uint64_t m = pg_scan_match_word(a.scan, w);
-      if (m == 0) continue;   // a word without a match costs one scalar load
-      if ((m >> lane) & 1) {
-        if (LDS) wt_update(a, s_wt, (uint32_t)(w * 64 + lane));
-        else wt_update(a, plane, (uint32_t)(w * 64 + lane));
-      }
-    }
-  }
-  if (LDS) {
-    __syncthreads();
-    for (uint32_t i = threadIdx.x; i < (uint32_t)a.n_slots; i += blockDim.x) {   // only the non-empty slots
-      const unsigned long long v = s_wt[i];
-      if (v) atomicMax(&plane[i], v);
-    }
-  }
+  side_table_pass<LDS>(
+      a.scan, a.n_slots, plane, [](uint32_t) PG_SIDE_INLINE { return 0ULL; }, [&](unsigned long long* tab, uint32_t doc) PG_SIDE_INLINE { wt_update(a, tab, doc); },
+      [&](uint32_t i, unsigned long long v) PG_SIDE_INLINE {   // only the non-empty slots
+        if (v) atomicMax(&plane[i], v);
+      });
 }
 
 }  // namespace
@@ -128,8 +96,6 @@ extern "C" __global__ void __launch_bounds__(256) pg_wt_hbm(const PgWtArgs a) { 
 // global atomic per slot at the end.
 extern "C" __global__ void __launch_bounds__(256) pg_wt_reg(const PgWtArgs a) {
   const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int waves = blockDim.x >> 6;
   unsigned long long* plane = a.pass == 0 ? a.keys : a.docs;
   unsigned long long best[PG_WT_MAX_SLOTS], top[PG_WT_MAX_SLOTS];
 #pragma unroll
@@ -137,25 +103,15 @@ extern "C" __global__ void __launch_bounds__(256) pg_wt_reg(const PgWtArgs a) {
     best[s] = 0;
     top[s] = (a.pass == 1 && s < a.slots) ? a.keys[s] : 0ULL;   // wave-uniform
   }
-  const int64_t stride = (int64_t)gridDim.x * waves * kWordsPerWave;
-  for (int64_t w0 = ((int64_t)blockIdx.x * waves + wave) * kWordsPerWave; w0 < a.scan.n_words; w0 += stride) {
-#pragma unroll 1
-    for (int u = 0; u < kWordsPerWave; u++) {
-      const int64_t w = w0 + u;
-      if (w >= a.scan.n_words) break;
-      const uint64_t m = pg_scan_match_word(a.scan, w);
-      if (m == 0) continue;
-      if (!((m >> lane) & 1)) continue;
-      const uint32_t doc = (uint32_t)(w * 64 + lane);
+  side_scan_walk(a.scan, [&](uint32_t doc) PG_SIDE_INLINE {
 #pragma unroll
-      for (int s = 0; s < PG_WT_MAX_SLOTS; s++) {
-        if (s < a.slots && !(a.pass == 1 && a.slot[s].packed)) {   // wave-uniform
-          const unsigned long long v = wt_offer(a, a.slot[s], doc, top[s]);
-          best[s] = v > best[s] ? v : best[s];
-        }
+    for (int s = 0; s < PG_WT_MAX_SLOTS; s++) {
+      if (s < a.slots && !(a.pass == 1 && a.slot[s].packed)) {   // wave-uniform
+        const unsigned long long v = wt_offer(a, a.slot[s], doc, top[s]);
+        best[s] = v > best[s] ? v : best[s];
       }
     }
-  }
+  });
 #pragma unroll
   for (int s = 0; s < PG_WT_MAX_SLOTS; s++) {
     if (s < a.slots && !(a.pass == 1 && a.slot[s].packed)) {
@@ -195,17 +151,8 @@ extern "C" __global__ void __launch_bounds__(256) pg_wt_gather(const PgWtGatherA
 }
 
 // ---- launchers (pg_exec_withtime.hip) -----------------------------------------------------------------------------------------------------------
-// tier: 0 pg_wt_reg, 1 pg_wt_lds, 2 pg_wt_hbm
 void pg_wt_launch_pass(const PgWtArgs* args, int tier, int grid, hipStream_t stream) {
-  const PgWtArgs a = *args;
-  if (tier == 1) {
-    PG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(pg_wt_lds), hipFuncAttributeMaxDynamicSharedMemorySize, PG_WT_LDS_SLOTS * 8));
-    hipLaunchKernelGGL(pg_wt_lds, dim3(grid), dim3(512), (size_t)a.n_slots * 8, stream, a);
-  } else if (tier == 2) {
-    hipLaunchKernelGGL(pg_wt_hbm, dim3(grid), dim3(256), 0, stream, a);
-  } else {
-    hipLaunchKernelGGL(pg_wt_reg, dim3(grid), dim3(256), 0, stream, a);
-  }
+  side_launch_pass(pg_wt_reg, pg_wt_lds, pg_wt_hbm, PG_WT_LDS_SLOTS * 8, *args, (size_t)args->n_slots * 8, tier, grid, stream);
 }
 void pg_wt_launch_gather(const PgWtGatherArgs* args, int grid, hipStream_t stream) {
   const PgWtGatherArgs a = *args;

@@ -492,12 +492,7 @@ std::unique_ptr<Result> execute_query(Segment& seg, const pg_query& q_in, const 
   const ExprKeyScope expr_keys(seg, q);   // expressions among the group-by / DISTINCT keys: checked, their derived columns built and held
   if (q.flags & PG_QUERY_FLAG_SELECTION) return execute_selection(seg, q, cancel);   // its columns' nulls are refused (selection_shape)
   if (q.flags & PG_QUERY_FLAG_DISTINCT) return execute_distinct(seg, q, cancel);   // its columns' nulls are refused (distinct_shape)
-  // aggregations over expressions: before the PERCENTILE check, so that the expression pass is the outer one of a query that carries both —
-  // its statistics count the operand columns, and its ordinary part (PERCENTILEs included) comes back through here
-  if (has_expression(q)) return execute_expression(seg, q, cancel);
-  if (has_with_time(q)) return execute_with_time(seg, q, cancel);   // inside the expression pass, outside the variance's and the PERCENTILE's: its statistics count its two argument columns
-  if (has_variance(q)) return execute_variance(seg, q, cancel);   // inside the expression pass, outside the PERCENTILE's: its ordinary part comes back through here
-  if (has_percentile(q)) return execute_percentile(seg, q, cancel);   // its ordinary part comes back through here; nulls in its columns are refused (percentile_check)
+  if (const SidePath* side = side_path_of(q)) return side->execute(seg, q, cancel);   // the outermost side path (kSidePaths, pg_exec_sidepass.hip); its ordinary part comes back through here
   if (!(q.flags & PG_QUERY_FLAG_NULL_HANDLING)) return execute_query_plain(seg, q, cancel);
   if (q.n_aggregations <= 0 || !q.aggregations) fail(PG_ERR_INVALID_ARGUMENT, "query has no aggregation");
   check_null_handling(seg, q);

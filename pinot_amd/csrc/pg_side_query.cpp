@@ -50,4 +50,11 @@ int32_t side_base_query(const pg_query& q, bool (*is_side)(const pg_agg_spec&), 
   return PG_OK;
 }
 
+Tier side_tier(int32_t n_group_by, uint64_t n_slots, uint64_t lds_max_slots, uint64_t table_bytes, int64_t hbm_max_bytes) {
+  if (n_group_by == 0) return TIER_REG;
+  if (n_slots <= lds_max_slots) return TIER_LDS;
+  if (table_bytes <= (uint64_t)hbm_max_bytes) return TIER_HBM;
+  return TIER_REFUSED;
+}
+
 }  // namespace pg

@@ -1,6 +1,7 @@
 // Stand-alone driver of the query splitter of the side passes (pinot_amd/csrc/pg_side_query.cpp), built with -fsanitize=address,undefined by
 // tests/test_side_query.py: every shape of aggregation list, ORDER BY, agg_params and flags the two paths hand over, each in heap arrays of
-// exactly its length so that a read past them is caught.  Prints one line per case and "side query ok" at the end.
+// exactly its length so that a read past them is caught; and the tier choice of the slot-table paths (pg::side_tier) at both sides of every
+// boundary.  Prints one line per case and "side query ok" at the end.
 #include <stdio.h>
 #include <string.h>
 
@@ -122,7 +123,34 @@ static void run(const Case& c) {
   delete[] order;
 }
 
+// The tier of a slot-table path's table (pg::side_tier), at both sides of every boundary.  A table has `planes` 8-byte planes per slot:
+// 1, or 2 in the wide mode of FIRSTWITHTIME / LASTWITHTIME.
+static void tier_case(const char* what, int32_t n_group_by, uint64_t n_slots, int planes, uint64_t lds_max_slots, int64_t hbm_max_bytes, pg::Tier want) {
+  const pg::Tier got = pg::side_tier(n_group_by, n_slots, lds_max_slots, n_slots * 8 * (uint64_t)planes, hbm_max_bytes);
+  printf("%s tier: %s: %d (want %d)\n", got == want ? "ok  " : "FAIL", what, (int)got, (int)want);
+  if (got != want) failures++;
+}
+static void tier_cases() {
+  const uint64_t ceiling = 16384;        // PG_EXPR_LDS_SLOTS / PG_VAR_LDS_SLOTS / PG_WT_LDS_SLOTS
+  const int64_t limit = 8 * 100000;      // an HBM knob: room for 100 000 slots
+  tier_case("no GROUP BY, one slot", 0, 1, 1, ceiling, limit, pg::TIER_REG);
+  tier_case("no GROUP BY, more slots than any limit", 0, 100001, 1, ceiling, limit, pg::TIER_REG);
+  tier_case("GROUP BY, one slot", 1, 1, 1, ceiling, limit, pg::TIER_LDS);
+  tier_case("slots == LDS ceiling", 2, ceiling, 1, ceiling, limit, pg::TIER_LDS);
+  tier_case("slots == LDS ceiling + 1", 2, ceiling + 1, 1, ceiling, limit, pg::TIER_HBM);
+  tier_case("a lowered LDS knob: slots == knob", 1, 64, 1, 64, limit, pg::TIER_LDS);
+  tier_case("a lowered LDS knob: slots == knob + 1", 1, 65, 1, 64, limit, pg::TIER_HBM);
+  tier_case("bytes == HBM limit", 1, 100000, 1, ceiling, limit, pg::TIER_HBM);
+  tier_case("bytes == HBM limit + 8", 1, 100001, 1, ceiling, limit, pg::TIER_REFUSED);
+  tier_case("double width: bytes == HBM limit at half the slots", 1, 50000, 2, ceiling, limit, pg::TIER_HBM);
+  tier_case("double width: refused at half the slots + 1", 1, 50001, 2, ceiling, limit, pg::TIER_REFUSED);
+  tier_case("double width below the LDS ceiling: the slot count decides", 1, ceiling, 2, ceiling, limit, pg::TIER_LDS);
+  tier_case("an HBM limit below the LDS ceiling: LDS is asked first", 1, ceiling, 1, ceiling, 8, pg::TIER_LDS);
+  static_assert(pg::TIER_REG == 0 && pg::TIER_LDS == 1 && pg::TIER_HBM == 2, "the tiers index the paths' kernel names");
+}
+
 int main() {
+  tier_cases();
   const Agg P50{PG_AGG_PERCENTILE, "v", 50.0}, P99{PG_AGG_PERCENTILE, "w", 99.0}, SUM{PG_AGG_SUM, "s", 1.5}, MAX{PG_AGG_MAX, "m", 2.5}, COUNT{PG_AGG_COUNT, "*", 3.5};
   const Agg XSUM{PG_AGG_SUM, "add(a,b)", 4.5}, XMIN{PG_AGG_MIN, "mult(a,'2')", 5.5};
   const int32_t every_flag = PG_QUERY_FLAG_PROFILE | PG_QUERY_FLAG_NULL_HANDLING | PG_QUERY_FLAG_FINAL_PERCENTILE | PG_QUERY_FLAG_KEEP_DEVICE_TABLE | PG_QUERY_FLAG_FINAL_DISTINCT;

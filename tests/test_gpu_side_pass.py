@@ -1,15 +1,18 @@
 """What the two side passes — exact PERCENTILE (pg_exec_percentile.hip) and aggregations over an expression (pg_exec_expr.hip) — share: the
 split of the query, the filter's match words, the join by group key and the statistics written at the end (pg_exec_sidepass.hip).  Both paths
 run the same shapes over the segments of tests/test_gpu_percentile.py at 1, 64 and 1 003 docs (the last match word of 1 003 docs is partial:
-with a filter the word comes from the filter, without one it is made up in the kernel), and are held to the models of the two modules."""
+with a filter the word comes from the filter, without one it is made up in the kernel), and are held to the models of the two modules.
+The last test nests all four side paths of the frame's table in one query."""
 import numpy as np
 import pytest
 
 from pinot_amd import capi
 from pinot_amd.executor import CancelToken, NativeSegment
-from pinot_amd.query import parse_sql
+from pinot_amd.query import CQuery, parse_sql, with_time_arguments
 from tests import expression_model as em
 from tests import percentile_model as pm
+from tests import variance_model as vm
+from tests import with_time_model as wm
 from tests import test_gpu_expressions as te
 from tests import test_gpu_percentile as tp
 
@@ -155,3 +158,45 @@ def test_all_three_kinds_with_order_by_and_limit(segments):
     finally:
         a.free()
         b.free()
+
+
+def test_all_four_kinds_nested_in_one_query(gpu_api, segments):
+    """the table of side paths end to end: the expression pass outside, the FIRSTWITHTIME pass inside it, the variance's inside that, the
+    PERCENTILE's innermost, a plain SUM in the ordinary part at the bottom — and pg_query_supported walking the same nesting"""
+    seg = segments(1003)
+    host, data, schema, gpu, oracle = seg
+    sql = "SELECT g7, SUM(add(v7,v3)), FIRSTWITHTIME(v3, ld, 'INT'), VAR_POP(v7), PERCENTILE(v3, 95), SUM(s) FROM t" + WHERE + " GROUP BY g7"
+    qc = parse_sql(sql)
+    gpu_api.call("query_supported", gpu.handle, CQuery(qc).ptr())   # PG_OK: anything else raises
+    b = gpu.execute(qc)
+    assert b.stats.kernel.decode() == "pg_expr_lds" and b.stats.percentile_passes == 1 and b.stats.star_tree_index == -1
+    docs, in_filter = tp._filter(oracle, "SELECT COUNT(*) FROM t" + WHERE)
+    assert b.stats.num_entries_scanned_in_filter == in_filter
+    assert (b.stats.num_docs_scanned, b.stats.num_entries_scanned_post_filter) == pm.statistics(len(docs), {"g7", "v7", "v3", "ld", "s"})
+    groups = pm.group_docs([data["g7"]], docs)
+    rows = b.rows()
+    assert set(rows) == set(groups) and len(rows) == 7
+    v = em.evaluate("add(v7,v3)", data, schema)
+    x, t, declared = with_time_arguments(qc.aggregations[1].column)
+    assert (x, t, declared) == ("v3", "ld", "INT")
+    for key, gdocs in groups.items():
+        total, first, var, runs, plain = rows[key]
+        gdocs = np.sort(np.asarray(gdocs, dtype=np.int64))
+        assert pm.same_double(total, em.agg_sum(v[gdocs])), key
+        assert wm.pair_bits(declared, *first) == wm.aggregate("FIRSTWITHTIME", schema[x], data[x], data[t], gdocs, declared), key
+        want = vm.exact_tuple(vm.as_doubles(np.asarray(data["v7"])[gdocs], "INT"))
+        assert var[0] == want[0] and vm.same_bits(var[1], want[1]) and vm.same_bits(var[2], want[2]), key
+        assert pm.same_runs(runs, pm.runs(pm.as_doubles(np.asarray(data["v3"])[gdocs], "INT"))), key
+        assert plain == float(np.sum(np.asarray(data["s"], dtype=np.int64)[gdocs])), key
+    # a refusal of the innermost path comes up through every level, from the check and from the execution alike
+    qc.aggregations[3].percentile = 101.0
+    statuses = []
+    for call in ("query_supported", "query_exec"):
+        with pytest.raises(capi.NativeError) as e:
+            if call == "query_supported":
+                gpu_api.call(call, gpu.handle, CQuery(qc).ptr())
+            else:
+                gpu_api.call(call, gpu.handle, CQuery(qc).ptr(), capi.C.byref(capi.C.c_void_p()))
+        assert "the percentile must be in [0, 100]" in e.value.message, (call, e.value.message)
+        statuses.append(e.value.status)
+    assert statuses == [capi.PG_ERR_INVALID_ARGUMENT] * 2

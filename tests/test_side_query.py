@@ -1,7 +1,8 @@
 """The query splitter of the side passes (pinot_amd/csrc/pg_side_query.cpp) as a stand-alone program under AddressSanitizer and
 UndefinedBehaviorSanitizer: tests/side_query_main.cpp splits queries with side aggregations first, in the middle, last, everywhere and
 nowhere, with every kind of ORDER BY, with and without agg_params and under both paths' flag sets, and checks base_index, the kept
-specs, params, order and flags field by field.  (The library loaded into Python is not run under a sanitizer.)"""
+specs, params, order and flags field by field; and asks pg::side_tier — where a slot-table path keeps its table — at both sides of every
+boundary.  (The library loaded into Python is not run under a sanitizer.)"""
 import os
 import subprocess
 
@@ -24,3 +25,10 @@ def test_splitter_under_sanitizers(tmp_path):
                  "the percentile path's flags: FINAL_PERCENTILE and KEEP_DEVICE_TABLE cleared",
                  "the expression path: a PERCENTILE stays with its param and FINAL_PERCENTILE, KEEP_DEVICE_TABLE is cleared"):
         assert "ok   " + what in out.stdout, what
+    # the tier choice: REG 0, LDS 1, HBM 2, refused -1
+    for what, tier in (("no GROUP BY, one slot", 0), ("no GROUP BY, more slots than any limit", 0), ("GROUP BY, one slot", 1),
+                       ("slots == LDS ceiling", 1), ("slots == LDS ceiling + 1", 2), ("a lowered LDS knob: slots == knob", 1),
+                       ("a lowered LDS knob: slots == knob + 1", 2), ("bytes == HBM limit", 2), ("bytes == HBM limit + 8", -1),
+                       ("double width: bytes == HBM limit at half the slots", 2), ("double width: refused at half the slots + 1", -1),
+                       ("double width below the LDS ceiling: the slot count decides", 1), ("an HBM limit below the LDS ceiling: LDS is asked first", 1)):
+        assert f"ok   tier: {what}: {tier} (want {tier})" in out.stdout, what
