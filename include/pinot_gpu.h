@@ -247,7 +247,31 @@ typedef enum pg_agg_function {   /* AggregationFunctionType (subset named by nor
    * never taken for such a query; pg_result_merge / pg_result_all_reduce refuse its results (the Java side merges with the functions' own
    * merge). */
   PG_AGG_FIRSTWITHTIME = 21,
-  PG_AGG_LASTWITHTIME = 22
+  PG_AGG_LASTWITHTIME = 22,
+  /* COVAR_POP(x, y) / COVAR_SAMP(x, y) (CovarianceAggregationFunction.java; intermediate CovarianceTuple(sumX, sumY, sumXY, count)) over two
+   * single-value INT / LONG / FLOAT / DOUBLE columns, dictionary-encoded or raw, each read as getDoubleValuesSV reads it (an INT exact, a LONG
+   * (double) rounded first, a FLOAT widened exactly).  pg_agg_spec.column carries the argument list "x,y" (the general form above; blanks
+   * ignored).  Both produce the same intermediate, PG_RESULT_COVARIANCE_TUPLE; they differ in the final value —
+   * sumXY / count - (sumX * sumY) / (count * count) (POP) or sumXY / (count - 1) - (sumX * sumY) / (count * (count - 1)) (SAMP), in double
+   * in that operation order, Double.NEGATIVE_INFINITY for count 0 and, for SAMP, count 1 — and in the result column's name.  The per-doc
+   * addends are the reference's: x, y and the ROUNDED double product fl(x * y) (one multiply, never the exact product: two INTs whose
+   * product passes 2^53 add the rounded value; an underflowing product adds its subnormal or 0.0).  The sums are NOT the reference's
+   * docId-order doubles: count is exact and each of sumX, sumY, sumXY is the exact sum of its addends rounded once to nearest-even, +0.0 for
+   * a zero sum — order-free, bit-reproducible; sumX and sumY are what SUM(x) and SUM(y) return.  Products are held in a 160-bit window below
+   * the bound 2^Ep, Ep the sum of the two columns' bound exponents (a FLOAT / DOUBLE column's largest exponent rounded up to a multiple of
+   * 16, 32 for an INT, 64 for a LONG column): every product of magnitude >= 2^(Ep - 107) is exact — at least 75 binary orders below the
+   * largest product the segment can hold —, smaller ones are truncated toward zero below 2^(Ep - 159), which leaves |sumXY - exact| <
+   * n 2^(Ep - 159) before the rounding (pg_covar.h); integer-valued products are always exact.  A query without GROUP BY whose filter
+   * matches no doc returns (0.0, 0.0, 0.0, 0).
+   * Two arguments are required (PG_ERR_INVALID_ARGUMENT otherwise, also for a quoted literal); an unknown column is PG_ERR_NOT_FOUND.
+   * Refused (PG_ERR_UNSUPPORTED, the Java plan answers): a STRING / BYTES or multi-value argument, an expression argument, a multi-value
+   * group-by column next to it, under PG_QUERY_FLAG_NULL_HANDLING an argument or group-by column that holds nulls, a group key space over
+   * 2^32, a FLOAT / DOUBLE argument that holds a NaN or an infinity, a pair whose Ep reaches 1024 (the bounds admit a product that
+   * overflows), more than 8 distinct argument columns or 8 distinct ordered pairs in one query, a slot table beyond
+   * PG_COVAR_HBM_MAX_BYTES (default 256 MiB).  The star-tree route is never taken for such a query; pg_result_merge /
+   * pg_result_all_reduce refuse its results (the Java side merges with CovarianceTuple#apply). */
+  PG_AGG_COVARPOP = 23,
+  PG_AGG_COVARSAMP = 24
 } pg_agg_function;
 
 typedef struct pg_agg_spec {
@@ -260,7 +284,8 @@ typedef struct pg_agg_spec {
                              an expression.  At most 15 operations and 8 distinct columns per expression, 4 distinct expressions per query
                              (PG_ERR_UNSUPPORTED beyond); malformed text is PG_ERR_INVALID_ARGUMENT.  Evaluated in IEEE double, one rounded
                              operation at a time in the reference's argument order; results that carry one are not merged in the library.
-                             FIRSTWITHTIME / LASTWITHTIME: the argument list, "x,t,'DOUBLE'" (see PG_AGG_FIRSTWITHTIME). */
+                             FIRSTWITHTIME / LASTWITHTIME: the argument list, "x,t,'DOUBLE'" (see PG_AGG_FIRSTWITHTIME); COVAR_POP / COVAR_SAMP:
+                             the argument list "x,y" (see PG_AGG_COVARPOP). */
 } pg_agg_spec;
 
 /* One ORDER BY expression of a group-by query, as TableResizer resolves it (pinot-core/.../core/data/table/TableResizer.java:129-161):
@@ -436,6 +461,8 @@ typedef enum pg_result_kind {
   PG_RESULT_VALUE_TIME_PAIR = 9, /* FIRSTWITHTIME / LASTWITHTIME: ValueLongPair — pg_result_longs(r, agg, 0) the time; pg_result_longs(r, agg, 1)
                               the value of a declared INT / LONG (for a declared FLOAT / DOUBLE: its raw IEEE bits, a FLOAT's 32 zero-extended);
                               pg_result_doubles(r, agg, 0) the value of a declared FLOAT / DOUBLE (a FLOAT widened exactly) */
+  PG_RESULT_COVARIANCE_TUPLE = 10, /* COVAR_POP / COVAR_SAMP: CovarianceTuple — pg_result_doubles(r, agg, 0) sumX, pg_result_doubles(r, agg, 1) sumY,
+                              pg_result_doubles(r, agg, 2) sumXY (component 2 exists for this kind only), pg_result_longs(r, agg, 0) the count */
   PG_RESULT_VALUE_COUNTS = 7 /* PERCENTILE: the group's DoubleArrayList as runs — pg_result_set_sizes gives the runs per group, pg_result_set_values_double
                               the runs' values (ascending under Double.compare within a group), pg_result_set_counts how often each occurs */
 } pg_result_kind;

@@ -316,6 +316,8 @@ public class GpuGroupByOperator extends BaseOperator<BaseResultsBlock> {
         return GpuResultObjects.doubleLists(result, a, n);                       // PERCENTILE: (value, count) runs -> DoubleArrayList (PercentileAggregationFunction.java:77-100)
       case PinotGpu.RESULT_VARIANCE_TUPLE:
         return GpuResultObjects.varianceTuples(result, a, n);                    // (count, sum, m2) -> VarianceTuple, the holder's value and the intermediate alike (VarianceAggregationFunction.java:66-74)
+      case PinotGpu.RESULT_COVARIANCE_TUPLE:
+        return GpuResultObjects.covarianceTuples(result, a, n);                  // (sumX, sumY, sumXY, count) -> CovarianceTuple, the holder's value and the intermediate alike (CovarianceAggregationFunction.java:112-130)
       case PinotGpu.RESULT_VALUE_TIME_PAIR:
         return GpuResultObjects.valueTimePairs(result, a, n, function);          // (value, time) -> IntLongPair / LongLongPair / FloatLongPair / DoubleLongPair, the holder's value and the intermediate alike
       default:

@@ -242,6 +242,25 @@ public final class GpuResultObjects {
     return out;
   }
 
+  /** COVAR_POP / COVAR_SAMP (pg_result_kind PG_RESULT_COVARIANCE_TUPLE): per group the function's CovarianceTuple from the library's four
+   *  components — the exact sums of x, of y and of the rounded products, each rounded once, and the count.  Tuples of several segments merge
+   *  with CovarianceTuple#apply (CovarianceAggregationFunction#merge), as the reference's own do. */
+  public static Object[] covarianceTuples(long result, int aggregation, int numGroups) {
+    double[] sumX = new double[numGroups];
+    double[] sumY = new double[numGroups];
+    double[] sumXY = new double[numGroups];
+    long[] count = new long[numGroups];
+    PinotGpu.resultDoubles(result, aggregation, 0, sumX);
+    PinotGpu.resultDoubles(result, aggregation, 1, sumY);
+    PinotGpu.resultDoubles(result, aggregation, 2, sumXY);
+    PinotGpu.resultLongs(result, aggregation, 0, count);
+    Object[] out = new Object[numGroups];
+    for (int g = 0; g < numGroups; g++) {
+      out[g] = new org.apache.pinot.segment.local.customobject.CovarianceTuple(sumX[g], sumY[g], sumXY[g], count[g]);
+    }
+    return out;
+  }
+
   /** FIRSTWITHTIME / LASTWITHTIME (pg_result_kind PG_RESULT_VALUE_TIME_PAIR): per group the function's ValueLongPair of the declared type —
    *  the concrete subclass tells it — from the library's (value, time).  Pairs of several segments merge with the functions' own merge. */
   public static Object[] valueTimePairs(long result, int aggregation, int numGroups, AggregationFunction function) {

@@ -103,6 +103,15 @@ public final class NativeQuery implements AutoCloseable {
         putString(b, list);
         continue;
       }
+      if (fn == 23 || fn == 24) {   // PG_AGG_COVARPOP / PG_AGG_COVARSAMP: the argument list "x,y" in pg_agg_spec.column, two identifiers
+        if (args.size() != 2 || args.get(0).getType() != ExpressionContext.Type.IDENTIFIER
+            || args.get(1).getType() != ExpressionContext.Type.IDENTIFIER) {
+          return null;
+        }
+        b.putInt(fn).putInt(0);
+        putString(b, args.get(0).getIdentifier() + "," + args.get(1).getIdentifier());
+        continue;
+      }
       if (fn < 0 || args.size() > 1) {
         return null;
       }
@@ -339,6 +348,9 @@ public final class NativeQuery implements AutoCloseable {
       case STDDEVPOP: return f instanceof org.apache.pinot.core.query.aggregation.function.VarianceAggregationFunction ? 19 : -1;
       case STDDEVSAMP: return f instanceof org.apache.pinot.core.query.aggregation.function.VarianceAggregationFunction ? 20 : -1;
       // the latest / earliest value per key (pg_agg_function 21 / 22): INT / LONG / FLOAT / DOUBLE variants only (withTimeType)
+      // the covariances (pg_agg_function 23 / 24): one intermediate (CovarianceTuple), two final values
+      case COVARPOP: return f instanceof org.apache.pinot.core.query.aggregation.function.CovarianceAggregationFunction ? 23 : -1;
+      case COVARSAMP: return f instanceof org.apache.pinot.core.query.aggregation.function.CovarianceAggregationFunction ? 24 : -1;
       case FIRSTWITHTIME:
         return f instanceof org.apache.pinot.core.query.aggregation.function.FirstWithTimeAggregationFunction && withTimeType(f) != null ? 21 : -1;
       case LASTWITHTIME:

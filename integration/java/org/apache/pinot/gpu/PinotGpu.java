@@ -23,7 +23,8 @@ public final class PinotGpu {
   public static final int RESULT_LONG = 0, RESULT_DOUBLE = 1, RESULT_AVG_PAIR = 2, RESULT_MINMAX_PAIR = 3, RESULT_DICTID_SET = 4,
       RESULT_HLL = 5, RESULT_VALUE_SET = 6, RESULT_VALUE_COUNTS = 7,
       RESULT_VALUE_TIME_PAIR = 9,   // FIRSTWITHTIME / LASTWITHTIME: resultLongs(.., 0) the time, resultLongs(.., 1) an INT / LONG value, resultDoubles(.., 0) a FLOAT / DOUBLE value
-      RESULT_VARIANCE_TUPLE = 8;   // VAR_POP / VAR_SAMP / STDDEV_POP / STDDEV_SAMP: resultLongs(.., 0) the count, resultDoubles(.., 0) the sum, resultDoubles(.., 1) m2
+      RESULT_VARIANCE_TUPLE = 8,   // VAR_POP / VAR_SAMP / STDDEV_POP / STDDEV_SAMP: resultLongs(.., 0) the count, resultDoubles(.., 0) the sum, resultDoubles(.., 1) m2
+      RESULT_COVARIANCE_TUPLE = 10;   // COVAR_POP / COVAR_SAMP: resultDoubles(.., 0) sumX, (.., 1) sumY, (.., 2) sumXY, resultLongs(.., 0) the count
   public static final int GROUP_KEY_DICT_IDS = 0, GROUP_KEY_LONG_VALUES = 1, GROUP_KEY_DOUBLE_VALUES = 2, GROUP_KEY_BYTES_VALUES = 3;
 
   public static native int abiVersion();

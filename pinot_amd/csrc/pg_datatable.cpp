@@ -24,6 +24,7 @@
 // values ascending by dictId, and the metadata section is empty (the server fills ExecutionStatistics in after the block is built).  Every
 // reader of the format rebuilds maps / sets from them.  No JVM exists in this image: the bytes are checked against an independent Python
 // restatement of builder AND reader (oracle/po_datatable.py) — parity unpinned against the reference itself.
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -83,6 +84,8 @@ const char* function_name(int32_t fn) {   // AggregationFunctionType#getName().t
     case PG_AGG_VARSAMP: return "varsamp";
     case PG_AGG_STDDEVPOP: return "stddevpop";
     case PG_AGG_STDDEVSAMP: return "stddevsamp";
+    case PG_AGG_COVARPOP: return "covarpop";   // getResultColumnName: the lower-case name + "(" + the arguments joined by "," + ")"
+    case PG_AGG_COVARSAMP: return "covarsamp";
     case PG_AGG_FIRSTWITHTIME: return "firstwithtime";   // getResultColumnName: the lower-case name + "(" + the argument list as given + ")"
     case PG_AGG_LASTWITHTIME: return "lastwithtime";
     default: fail(PG_ERR_INTERNAL, "aggregation function %d has no name", fn);
@@ -148,7 +151,10 @@ std::vector<uint8_t> result_data_table_v4(const Result& r) {
       types.push_back(C_OBJECT);
       continue;
     }
-    names.push_back(count_star ? std::string("count(*)") : std::string(function_name(c.function)) + "(" + c.name + ")");
+    std::string arguments = c.name;
+    if (c.function == PG_AGG_COVARPOP || c.function == PG_AGG_COVARSAMP)   // the argument list without its blanks: "covarpop(x,y)"
+      arguments.erase(std::remove_if(arguments.begin(), arguments.end(), [](char ch) { return ch == ' ' || ch == '\t' || ch == '\n' || ch == '\r'; }), arguments.end());
+    names.push_back(count_star ? std::string("count(*)") : std::string(function_name(c.function)) + "(" + arguments + ")");
     switch (r.aggs[(size_t)a].kind) {
       case PG_RESULT_LONG:
         if (c.function != PG_AGG_COUNT && c.function != PG_AGG_COUNTMV)
@@ -323,6 +329,15 @@ std::vector<uint8_t> result_data_table_v4(const Result& r) {
           p.f64(ar.d[0][(size_t)i]);
           p.f64(ar.d[1][(size_t)i]);
           object(33, p);
+          break;
+        }
+        case PG_RESULT_COVARIANCE_TUPLE: {   // CovarianceTuple#toBytes: double sumX, double sumY, double sumXY, long count (ObjectSerDeUtils type 32)
+          Out p;
+          p.f64(ar.d[0][(size_t)i]);
+          p.f64(ar.d[1][(size_t)i]);
+          p.f64(ar.d[2][(size_t)i]);
+          p.i64(ar.l[0][(size_t)i]);
+          object(32, p);
           break;
         }
         case PG_RESULT_VALUE_TIME_PAIR: {   // ValueLongPair#toBytes: the value big-endian (4 or 8 bytes), then the time as a big-endian long

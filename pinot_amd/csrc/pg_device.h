@@ -684,6 +684,38 @@ struct PgWtGatherArgs {
   PgValueSrc value[PG_WT_MAX_AGGS];
   int32_t value_slot[PG_WT_MAX_AGGS];
 };
+// ---- COVAR_POP / COVAR_SAMP (pg_kernels_covar.hip) ----------------------------------------------------------------------------------
+// One accumulation pass for all covariance aggregations of a query: per matching doc the group key, then the group's 64-bit slots — a table
+// [G][slots] of int64, every slot a sum (identity 0).  Slot 0 is the doc count; every distinct argument column follows with the digits of its
+// sum (one slot for an INT column, PG_COVAR_DBL_SLOTS else), then every distinct ordered pair with the PG_COVAR_PROD_LIMBS digits of its
+// rounded products (pg_covar.h).
+#include "pg_covar.h"
+#define PG_COVAR_LDS_SLOTS 16384   // 128 KiB of the CU's 160 KiB: one persistent workgroup per CU, as pg_var_lds
+#define PG_COVAR_REG_COLS 2        // what pg_covar_reg holds in registers (one pair: COVAR_POP(x,y), COVAR_SAMP(x,y)); a larger query
+#define PG_COVAR_REG_PAIRS 1       // without GROUP BY runs pg_covar_reg_wide, which holds the full limits at a quarter of the waves per SIMD
+struct PgCovarCol {
+  PgValueSrc src;
+  int32_t is_int;                // one integer slot (wave-uniform)
+  int32_t first_slot;            // the column's first slot within the group's row
+  int32_t q1;                    // else: the scale of the sum's digits
+  int32_t pad;
+};
+struct PgCovarPair {
+  int32_t x, y;                  // indexes into cols
+  int32_t first_slot;            // the pair's first slot within the group's row
+  int32_t qp;                    // the scale of the products' digits
+};
+struct PgCovarArgs {
+  PgGroupScan scan;            // match words and group columns
+  int32_t n_cols, n_pairs;
+  int32_t slots;               // slots per group
+  int32_t pad;
+  uint64_t n_groups;           // G (<= 2^32)
+  uint64_t n_slots;            // G x slots
+  int64_t* table;              // [G][slots] in HBM, zeroed by the caller
+  PgCovarCol cols[PG_COVAR_MAX_COLS];
+  PgCovarPair pairs[PG_COVAR_MAX_PAIRS];
+};
 // a time-bucket transform as a key (pg_kernels_timekey.hip): the value column and the normal form, wave-uniform kernel arguments
 struct PgTimeKeyArgs {
   PgValueSrc src;

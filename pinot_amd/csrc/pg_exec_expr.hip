@@ -110,6 +110,7 @@ ExprPlan expr_plan(Segment& seg, const pg_query& q, bool compute_bounds) {
     const pg_agg_spec& s = q.aggregations[a];
     if (!is_expression_agg(s)) {
       if (is_with_time_function(s.function)) with_time_columns_read(s, read);   // its column is an argument list
+      else if (is_covariance_function(s.function)) covariance_columns_read(s, read);
       else if (s.column && strcmp(s.column, "*") != 0) read.insert(s.column);
       continue;
     }

@@ -125,7 +125,8 @@ WtPlan wt_plan(Segment& seg, const pg_query& q) {
   for (int a = 0; a < q.n_aggregations; a++) {
     const pg_agg_spec& s = q.aggregations[a];
     if (!is_with_time_agg(s)) {
-      if (s.column && strcmp(s.column, "*") != 0) read.insert(s.column);
+      if (is_covariance_function(s.function)) covariance_columns_read(s, read);   // its column is an argument list
+      else if (s.column && strcmp(s.column, "*") != 0) read.insert(s.column);
       continue;
     }
     const char* fn = agg_function_text(s.function);

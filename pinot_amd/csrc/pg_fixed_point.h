@@ -39,7 +39,8 @@ PG_FX_HD int64_t pg_long_digit(int64_t v, int limb) { return limb ? (v >> 32) : 
 #include <math.h>
 // sum_j limbs[j] * 2^(32 j + q) rounded to nearest-even once: two's-complement base-2^32 digits -> magnitude -> top 53 bits + round + sticky
 static inline double pg_limbs_to_double(const int64_t* limbs, int n_limbs, int q) {
-  uint32_t dig[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // n_limbs <= 4 digits + carries + sign extension
+  // n_limbs <= 5 (five: pg_covar.h): |limb| < 2^63 keeps |sum| below 2^(32 n_limbs + 32) <= 2^192 — digits 0..5 —, the sign extension above
+  uint32_t dig[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   __int128 carry = 0;
   for (int j = 0; j < 7; j++) {
     const __int128 t = carry + (j < n_limbs ? (__int128)limbs[j] : 0);

@@ -445,6 +445,13 @@ class ResultsBlock:
                 api.call("result_doubles", h, a, 0, s.ctypes.data, ng)
                 api.call("result_doubles", h, a, 1, m2.ctypes.data, ng)
                 rb.arrays.append((k, n, s, m2))
+            elif k == capi.RESULT_COVARIANCE_TUPLE:   # COVAR_POP / COVAR_SAMP: CovarianceTuple(sumX, sumY, sumXY, count)
+                sums = [np.zeros(ng, dtype=np.float64) for _ in range(3)]
+                n = np.zeros(ng, dtype=np.int64)
+                for c in range(3):
+                    api.call("result_doubles", h, a, c, sums[c].ctypes.data, ng)
+                api.call("result_longs", h, a, 0, n.ctypes.data, ng)
+                rb.arrays.append((k, sums[0], sums[1], sums[2], n))
             elif k == capi.RESULT_VALUE_TIME_PAIR:   # FIRSTWITHTIME / LASTWITHTIME: ValueLongPair(value, time), the value in its declared type
                 floating = with_time_arguments(spec.column)[2] in ("FLOAT", "DOUBLE")
                 t = np.zeros(ng, dtype=np.int64)
@@ -548,6 +555,8 @@ class ResultsBlock:
                     cols.append(col)
                 elif k == capi.RESULT_VARIANCE_TUPLE:   # (count, sum, m2) per group
                     cols.append([(int(n), float(s), float(m2)) for n, s, m2 in zip(arr[1], arr[2], arr[3])])
+                elif k == capi.RESULT_COVARIANCE_TUPLE:   # (sumX, sumY, sumXY, count) per group
+                    cols.append([(float(sx), float(sy), float(sxy), int(n)) for sx, sy, sxy, n in zip(arr[1], arr[2], arr[3], arr[4])])
                 elif k == capi.RESULT_VALUE_TIME_PAIR:   # (value, time) per group; a FLOAT / DOUBLE value keeps its bits (NaN payloads, -0.0)
                     cols.append([(v.item(), int(t)) for v, t in zip(arr[1], arr[2])])
                 elif k == capi.RESULT_VALUE_COUNTS:   # (values, counts) per group
@@ -643,6 +652,26 @@ def variance_merge(a, b):
     return (n + b[0], s + b[1], m2 + (b[2] + delta * delta * b[0] * n / (b[0] + n)))
 
 
+def covariance_final(function: str, t) -> float:
+    """CovarianceAggregationFunction#extractFinalResult over the tuple (sumX, sumY, sumXY, count), in its operation order:
+    sumXY / count - (sumX * sumY) / (count * count) for COVAR_POP, sumXY / (count - 1) - (sumX * sumY) / (count * (count - 1)) for
+    COVAR_SAMP; Double.NEGATIVE_INFINITY for count 0 and, for COVAR_SAMP, count 1."""
+    sx, sy, sxy, n = t
+    sample = function == "COVARSAMP"
+    if n == 0 or (sample and n == 1):
+        return float("-inf")
+    with np.errstate(all="ignore"):   # Java double arithmetic: overflow gives an infinity, never an exception
+        sx, sy, sxy, c = np.float64(sx), np.float64(sy), np.float64(sxy), np.float64(n)
+        if sample:
+            return float(sxy / (c - 1) - (sx * sy) / (c * (c - 1)))
+        return float(sxy / c - (sx * sy) / (c * c))
+
+
+def covariance_merge(a, b):
+    """CovarianceTuple#apply(CovarianceTuple): `b` added to `a` member by member (what the Java side does with the tuples of two segments)."""
+    return (a[0] + b[0], a[1] + b[1], a[2] + b[2], a[3] + b[3])
+
+
 def with_time_merge(function: str, a, b):
     """FirstWithTimeAggregationFunction#merge / LastWithTimeAggregationFunction#merge over two (value, time) pairs, what the Java side does
     with the pairs of two segments: LAST keeps `a` where a.time >= b.time, FIRST where a.time <= b.time — the first argument wins a tie."""
@@ -678,6 +707,8 @@ def merge_intermediate(function: str, a, b):
         return hll_merge(a, b)
     if function in capi.VARIANCE_FUNCTIONS:
         return variance_merge(a, b)
+    if function in capi.COVARIANCE_FUNCTIONS:
+        return covariance_merge(a, b)
     if function in capi.WITH_TIME_FUNCTIONS:
         return with_time_merge(function, a, b)
     raise ValueError(function)
@@ -696,6 +727,8 @@ def extract_final(function: str, v):
         return hll_cardinality(v)
     if function in capi.VARIANCE_FUNCTIONS:
         return variance_final(function, v)
+    if function in capi.COVARIANCE_FUNCTIONS:
+        return covariance_final(function, v)
     if function in capi.WITH_TIME_FUNCTIONS:   # the pair's value
         return v[0]
     return v

@@ -132,6 +132,8 @@ class QueryContext:
             head, paren, rest = t.partition("(")   # VAR_POP(x) names the aggregation VARPOP(x): AggregationFunctionType strips underscores
             if paren and with_time_function_name(head):   # ... and LAST_WITH_TIME(x, t, 'int') names LASTWITHTIME(X,T,INT): the type literal with or without its quotes
                 return with_time_function_name(head) + paren + rest.replace("'", "")
+            if paren and covariance_function_name(head):   # ... and covar_pop(x, y) names COVARPOP(X,Y)
+                return covariance_function_name(head) + paren + rest
             return variance_function_name(head) + paren + rest if paren and variance_function_name(head) else t
         aggs = [norm(f"{a.function}({a.column or '*'}{',' + str(a.log2m) if a.log2m else ''})") for a in self.aggregations]
         pctl = [(a.column, a.percentile) if a.function == "PERCENTILE" else None for a in self.aggregations]
@@ -163,6 +165,12 @@ def variance_function_name(fn: str):
     strips underscores and ignores case), else None."""
     name = fn.replace("_", "").upper()
     return name if name in capi.VARIANCE_FUNCTIONS else None
+
+
+def covariance_function_name(fn: str):
+    """COVARPOP / COVARSAMP for any spelling of them (COVAR_POP, covarSamp), else None."""
+    name = fn.replace("_", "").upper()
+    return name if name in capi.COVARIANCE_FUNCTIONS else None
 
 
 def with_time_function_name(fn: str):
@@ -526,8 +534,17 @@ class _Parser:
         if t[0] != "id":
             raise SqlError(f"bad select item {t}")
         if self.peek() == ("op", "("):
-            fn = variance_function_name(t[1]) or with_time_function_name(t[1]) or t[1].upper()
+            fn = variance_function_name(t[1]) or with_time_function_name(t[1]) or covariance_function_name(t[1]) or t[1].upper()
             self.i += 1
+            if fn in capi.COVARIANCE_FUNCTIONS:   # COVAR_POP(x, y): the argument list "x,y", as getResultColumnName joins it
+                args = [self.aggregation_argument()]
+                self.expect_op(",")
+                args.append(self.aggregation_argument())
+                self.expect_op(")")
+                q.aggregations.append(AggregationSpec(fn, f"{args[0]},{args[1]}"))
+                if self.kw("AS"):
+                    self.i += 2
+                return
             if fn in capi.WITH_TIME_FUNCTIONS:   # FIRSTWITHTIME(x, t, 'TYPE'): the argument list travels as getResultColumnName prints it
                 args = [self.aggregation_argument()]
                 self.expect_op(",")
