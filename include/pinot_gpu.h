@@ -271,7 +271,29 @@ typedef enum pg_agg_function {   /* AggregationFunctionType (subset named by nor
    * PG_COVAR_HBM_MAX_BYTES (default 256 MiB).  The star-tree route is never taken for such a query; pg_result_merge /
    * pg_result_all_reduce refuse its results (the Java side merges with CovarianceTuple#apply). */
   PG_AGG_COVARPOP = 23,
-  PG_AGG_COVARSAMP = 24
+  PG_AGG_COVARSAMP = 24,
+  /* SKEWNESS / KURTOSIS (FourthMomentAggregationFunction.java; intermediate PinotFourthMoment(n, m1, m2, m3, m4): m1 the mean, m_k the sum of
+   * (x - mean)^k) over one single-value INT / LONG / FLOAT / DOUBLE column, dictionary-encoded or raw, read as getDoubleValuesSV reads it (an
+   * INT exact, a LONG (double) rounded first, a FLOAT widened exactly).  Both produce the same intermediate, PG_RESULT_FOURTH_MOMENT; they
+   * differ in the final value (Commons Math Skewness / Kurtosis#getResult: NaN for n < 3 / n <= 3, 0.0 for a variance m2 / (n - 1) below
+   * 10E-20, else n m3 / ((n - 1)(n - 2) sqrt(v) v) and (n (n + 1) m4 - 3 m2 m2 (n - 1)) / ((n - 1)(n - 2)(n - 3) v v)) and in the result
+   * column's name.  The values are NOT the reference's docId-order doubles: n is exact, and with the exact power sums S1 .. S4 of x .. x^4
+   * m1 = S1 / n, m2 = S2 - S1^2 / n, m3 = S3 - 3 S1 S2 / n + 2 S1^3 / n^2, m4 = S4 - 4 S1 S3 / n + 6 S1^2 S2 / n^2 - 3 S1^4 / n^3 are formed
+   * in exact integer arithmetic and each rounded once to nearest-even — order-free, bit-reproducible; m2 and m4 never negative and never
+   * -0.0, an exact zero m3 +0.0, (1, x, 0.0, 0.0, 0.0) for n = 1.  The powers are held in windows of 128, 192, 288 and 384 bits below the
+   * column's bound 2^E (a FLOAT / DOUBLE column's largest exponent rounded up to a multiple of 16, 64 for a LONG column; INT columns are
+   * always exact): every value of magnitude >= 2^(E - 43) has all four powers exact; smaller ones are truncated toward zero, which leaves
+   * before the roundings |m2 - exact| < n (2^(2E - 191) + 2^(2E - 126)), |m3 - exact| < n (2^(3E - 287) + 3 * 2^(3E - 191) + 9 * 2^(3E - 127)),
+   * |m4 - exact| < n (2^(4E - 383) + 4 * 2^(4E - 287) + 6 * 2^(4E - 191) + 28 * 2^(4E - 127)) (pg_moment4.h).  A query without GROUP BY whose
+   * filter matches no doc returns the reference's fresh tuple, (0, NaN, NaN, NaN, NaN).
+   * Refused (PG_ERR_UNSUPPORTED, the Java plan answers): a STRING / BYTES or multi-value argument, an expression argument, a multi-value
+   * group-by column next to it, under PG_QUERY_FLAG_NULL_HANDLING an argument or group-by column that holds nulls, a group key space over
+   * 2^32, a FLOAT / DOUBLE column that holds a NaN or an infinity or whose bound admits an x^4 that overflows a double (4 E >= 1024), more
+   * than 3 distinct argument columns in one query, a slot table beyond PG_MOMENT_HBM_MAX_BYTES (default 256 MiB).  The star-tree route is
+   * never taken for such a query; pg_result_merge / pg_result_all_reduce refuse its results (the Java side merges with
+   * PinotFourthMoment#combine). */
+  PG_AGG_SKEWNESS = 25,
+  PG_AGG_KURTOSIS = 26
 } pg_agg_function;
 
 typedef struct pg_agg_spec {
@@ -463,6 +485,8 @@ typedef enum pg_result_kind {
                               pg_result_doubles(r, agg, 0) the value of a declared FLOAT / DOUBLE (a FLOAT widened exactly) */
   PG_RESULT_COVARIANCE_TUPLE = 10, /* COVAR_POP / COVAR_SAMP: CovarianceTuple — pg_result_doubles(r, agg, 0) sumX, pg_result_doubles(r, agg, 1) sumY,
                               pg_result_doubles(r, agg, 2) sumXY (component 2 exists for this kind only), pg_result_longs(r, agg, 0) the count */
+  PG_RESULT_FOURTH_MOMENT = 11, /* SKEWNESS / KURTOSIS: PinotFourthMoment — pg_result_longs(r, agg, 0) n, pg_result_doubles(r, agg, 0 .. 3) m1 .. m4
+                              (components 2 and 3 exist for this kind; 2 also for PG_RESULT_COVARIANCE_TUPLE) */
   PG_RESULT_VALUE_COUNTS = 7 /* PERCENTILE: the group's DoubleArrayList as runs — pg_result_set_sizes gives the runs per group, pg_result_set_values_double
                               the runs' values (ascending under Double.compare within a group), pg_result_set_counts how often each occurs */
 } pg_result_kind;

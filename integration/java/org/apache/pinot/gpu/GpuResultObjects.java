@@ -242,6 +242,26 @@ public final class GpuResultObjects {
     return out;
   }
 
+  /** SKEWNESS / KURTOSIS (pg_result_kind PG_RESULT_FOURTH_MOMENT): per group the function's PinotFourthMoment from the library's five
+   *  components — n and the exact m1 .. m4, each rounded once.  The object's fields are inherited and protected: it is built from its own
+   *  serialized form (PinotFourthMoment#serialize: long n, doubles m1 .. m4, big-endian).  Moments of several segments merge with
+   *  PinotFourthMoment#combine (FourthMomentAggregationFunction#merge), as the reference's own do. */
+  public static Object[] fourthMoments(long result, int aggregation, int numGroups) {
+    long[] n = new long[numGroups];
+    double[][] m = new double[4][numGroups];
+    PinotGpu.resultLongs(result, aggregation, 0, n);
+    for (int k = 0; k < 4; k++) {
+      PinotGpu.resultDoubles(result, aggregation, k, m[k]);
+    }
+    Object[] out = new Object[numGroups];
+    for (int g = 0; g < numGroups; g++) {
+      java.nio.ByteBuffer bytes = java.nio.ByteBuffer.allocate(Long.BYTES + 4 * Double.BYTES);
+      bytes.putLong(n[g]).putDouble(m[0][g]).putDouble(m[1][g]).putDouble(m[2][g]).putDouble(m[3][g]);
+      out[g] = org.apache.pinot.segment.local.customobject.PinotFourthMoment.fromBytes(bytes.array());
+    }
+    return out;
+  }
+
   /** COVAR_POP / COVAR_SAMP (pg_result_kind PG_RESULT_COVARIANCE_TUPLE): per group the function's CovarianceTuple from the library's four
    *  components — the exact sums of x, of y and of the rounded products, each rounded once, and the count.  Tuples of several segments merge
    *  with CovarianceTuple#apply (CovarianceAggregationFunction#merge), as the reference's own do. */

@@ -351,6 +351,10 @@ public final class NativeQuery implements AutoCloseable {
       // the covariances (pg_agg_function 23 / 24): one intermediate (CovarianceTuple), two final values
       case COVARPOP: return f instanceof org.apache.pinot.core.query.aggregation.function.CovarianceAggregationFunction ? 23 : -1;
       case COVARSAMP: return f instanceof org.apache.pinot.core.query.aggregation.function.CovarianceAggregationFunction ? 24 : -1;
+      // the third and fourth moments (pg_agg_function 25 / 26): one intermediate (PinotFourthMoment), two final values; the class's third
+      // type, FOURTHMOMENT, has no final result and stays with the Java plan
+      case SKEWNESS: return f instanceof org.apache.pinot.core.query.aggregation.function.FourthMomentAggregationFunction ? 25 : -1;
+      case KURTOSIS: return f instanceof org.apache.pinot.core.query.aggregation.function.FourthMomentAggregationFunction ? 26 : -1;
       case FIRSTWITHTIME:
         return f instanceof org.apache.pinot.core.query.aggregation.function.FirstWithTimeAggregationFunction && withTimeType(f) != null ? 21 : -1;
       case LASTWITHTIME:

@@ -46,6 +46,7 @@ static void knobs_read(Knobs& k) {
   k.expr_lds_max_slots = std::max<int64_t>(1, std::min<int64_t>(PG_EXPR_LDS_SLOTS, num("PG_EXPR_LDS_MAX_SLOTS", PG_EXPR_LDS_SLOTS)));
   k.expr_hbm_max_bytes = std::max<int64_t>(8, num("PG_EXPR_HBM_MAX_BYTES", (int64_t)256 << 20));
   k.var_hbm_max_bytes = std::max<int64_t>(8, num("PG_VAR_HBM_MAX_BYTES", (int64_t)256 << 20));
+  k.moment_hbm_max_bytes = std::max<int64_t>(8, num("PG_MOMENT_HBM_MAX_BYTES", (int64_t)256 << 20));
   k.covar_hbm_max_bytes = std::max<int64_t>(8, num("PG_COVAR_HBM_MAX_BYTES", (int64_t)256 << 20));
   k.wt_hbm_max_bytes = std::max<int64_t>(8, num("PG_WT_HBM_MAX_BYTES", (int64_t)256 << 20));
   k.limit_prefix_min_docs = std::max<int64_t>(PG_WAVE_DOCS, num("PG_LIMIT_PREFIX_MIN_DOCS", (int64_t)1 << 20));
@@ -317,6 +318,7 @@ int32_t pg_result_merge(pg_result_t dst, pg_result_t src) {
     if (dst->r->percentile || src->r->percentile) fail(PG_ERR_UNSUPPORTED, "PERCENTILE results are merged by value (DoubleArrayList#addAll on the Java side)");
     if (dst->r->expression || src->r->expression) fail(PG_ERR_UNSUPPORTED, "results of aggregations over expressions are merged by value on the Java side (the scale of their exact sums differs per segment)");
     if (dst->r->variance || src->r->variance) fail(PG_ERR_UNSUPPORTED, "results of variance aggregations are merged on the Java side (VarianceTuple#apply)");
+    if (dst->r->fourth_moment || src->r->fourth_moment) fail(PG_ERR_UNSUPPORTED, "results of SKEWNESS / KURTOSIS aggregations are merged on the Java side (PinotFourthMoment#combine)");
     if (dst->r->covariance || src->r->covariance) fail(PG_ERR_UNSUPPORTED, "results of covariance aggregations are merged on the Java side (CovarianceTuple#apply)");
     if (dst->r->with_time || src->r->with_time) fail(PG_ERR_UNSUPPORTED, "results of FIRSTWITHTIME / LASTWITHTIME are merged on the Java side (the functions' own merge of ValueLongPair)");
     result_merge(*dst->r, *src->r);
@@ -330,6 +332,7 @@ int32_t pg_result_all_reduce(pg_result_t result, pg_comm_t comm) {
     if (result->r->percentile) fail(PG_ERR_UNSUPPORTED, "PERCENTILE results are merged by value (DoubleArrayList#addAll on the Java side)");
     if (result->r->expression) fail(PG_ERR_UNSUPPORTED, "results of aggregations over expressions are merged by value on the Java side (the scale of their exact sums differs per segment)");
     if (result->r->variance) fail(PG_ERR_UNSUPPORTED, "results of variance aggregations are merged on the Java side (VarianceTuple#apply)");
+    if (result->r->fourth_moment) fail(PG_ERR_UNSUPPORTED, "results of SKEWNESS / KURTOSIS aggregations are merged on the Java side (PinotFourthMoment#combine)");
     if (result->r->covariance) fail(PG_ERR_UNSUPPORTED, "results of covariance aggregations are merged on the Java side (CovarianceTuple#apply)");
     if (result->r->with_time) fail(PG_ERR_UNSUPPORTED, "results of FIRSTWITHTIME / LASTWITHTIME are merged on the Java side (the functions' own merge of ValueLongPair)");
     result_all_reduce(*result->r, *comm->c);
@@ -442,7 +445,7 @@ int32_t pg_result_kind_of(pg_result_t result, int32_t agg, int32_t* out_kind) {
 int32_t pg_result_doubles(pg_result_t result, int32_t agg, int32_t component, double* out, int32_t capacity) {
   return guarded([&] {
     AggResult& a = agg_of(result, agg);
-    REQUIRE(component >= 0 && component < (a.kind == PG_RESULT_COVARIANCE_TUPLE ? 3 : 2), "component out of range");   // sumXY: the covariance tuple's third double
+    REQUIRE(component >= 0 && component < (a.kind == PG_RESULT_FOURTH_MOMENT ? 4 : a.kind == PG_RESULT_COVARIANCE_TUPLE ? 3 : 2), "component out of range");   // sumXY: the covariance tuple's third double; m3, m4: the fourth moment's third and fourth
     REQUIRE(capacity >= result->r->num_groups, "capacity too small");
     if (!a.d[component].empty()) memcpy(out, a.d[component].data(), a.d[component].size() * 8);
     else if (result->r->num_groups > 0) memset(out, 0, (size_t)result->r->num_groups * 8);   // a component the result kind does not have

@@ -84,6 +84,8 @@ const char* function_name(int32_t fn) {   // AggregationFunctionType#getName().t
     case PG_AGG_VARSAMP: return "varsamp";
     case PG_AGG_STDDEVPOP: return "stddevpop";
     case PG_AGG_STDDEVSAMP: return "stddevsamp";
+    case PG_AGG_SKEWNESS: return "skewness";
+    case PG_AGG_KURTOSIS: return "kurtosis";
     case PG_AGG_COVARPOP: return "covarpop";   // getResultColumnName: the lower-case name + "(" + the arguments joined by "," + ")"
     case PG_AGG_COVARSAMP: return "covarsamp";
     case PG_AGG_FIRSTWITHTIME: return "firstwithtime";   // getResultColumnName: the lower-case name + "(" + the argument list as given + ")"
@@ -338,6 +340,13 @@ std::vector<uint8_t> result_data_table_v4(const Result& r) {
           p.f64(ar.d[2][(size_t)i]);
           p.i64(ar.l[0][(size_t)i]);
           object(32, p);
+          break;
+        }
+        case PG_RESULT_FOURTH_MOMENT: {   // PinotFourthMoment#serialize: long n, doubles m1, m2, m3, m4 (ObjectSerDeUtils type 34)
+          Out p;
+          p.i64(ar.l[0][(size_t)i]);
+          for (int k = 0; k < 4; k++) p.f64(ar.d[k][(size_t)i]);
+          object(34, p);
           break;
         }
         case PG_RESULT_VALUE_TIME_PAIR: {   // ValueLongPair#toBytes: the value big-endian (4 or 8 bytes), then the time as a big-endian long

@@ -716,6 +716,26 @@ struct PgCovarArgs {
   PgCovarCol cols[PG_COVAR_MAX_COLS];
   PgCovarPair pairs[PG_COVAR_MAX_PAIRS];
 };
+// ---- SKEWNESS / KURTOSIS (pg_kernels_moment.hip) --------------------------------------------------------------------------------------
+// One accumulation pass for all such aggregations of a query: per matching doc the group key, then the group's 64-bit slots — a table
+// [G][slots] of int64, every slot a sum (identity 0).  Slot 0 is the doc count; every distinct argument column (at most PG_MOMENT_MAX_COLS)
+// follows with the exact power sums of pg_moment4.h: PG_M4_INT_SLOTS slots on the integer path (INT columns), PG_M4_DBL_SLOTS on the double path.
+#include "pg_moment4.h"
+struct PgMomentCol {
+  PgValueSrc src;
+  int32_t is_int;                // the integer path (wave-uniform)
+  int32_t first_slot;            // the column's first slot within the group's row
+  int32_t q1, q2, q3, q4;        // double path: the scales of the digits of x, x^2, x^3, x^4
+};
+struct PgMomentArgs {
+  PgGroupScan scan;            // match words and group columns
+  int32_t n_cols;
+  int32_t slots;               // slots per group
+  uint64_t n_groups;           // G (<= 2^32)
+  uint64_t n_slots;            // G x slots
+  int64_t* table;              // [G][slots] in HBM, zeroed by the caller
+  PgMomentCol cols[PG_MOMENT_MAX_COLS];
+};
 // a time-bucket transform as a key (pg_kernels_timekey.hip): the value column and the normal form, wave-uniform kernel arguments
 struct PgTimeKeyArgs {
   PgValueSrc src;

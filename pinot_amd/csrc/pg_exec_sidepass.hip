@@ -1,5 +1,5 @@
 // The frame of the side passes: aggregations answered by a pass of their own and joined to the ordinary plan by group key (exact PERCENTILE:
-// pg_exec_percentile.hip; aggregations over an expression: pg_exec_expr.hip; the variance family: pg_exec_var.hip; COVAR_POP / COVAR_SAMP: pg_exec_covar.hip; FIRSTWITHTIME / LASTWITHTIME: pg_exec_withtime.hip).
+// pg_exec_percentile.hip; aggregations over an expression: pg_exec_expr.hip; the variance family: pg_exec_var.hip; COVAR_POP / COVAR_SAMP: pg_exec_covar.hip; SKEWNESS / KURTOSIS: pg_exec_moment.hip; FIRSTWITHTIME / LASTWITHTIME: pg_exec_withtime.hip).
 // The paths are the entries of kSidePaths below, in nesting order; side_path_of, side_check and execute_query (pg_nullaware.cpp) follow that list.  A path plans its aggregations and its group-by
 // columns (side_groups, side_argument_column), splits the query (side_base_query), and then
 //   1. side_pass_begin runs the ordinary part through execute_query — it decides the groups, the numGroupsLimit admission and the other
@@ -128,6 +128,8 @@ const SidePath kSidePaths[] = {
     {is_with_time_agg, with_time_plan_check, execute_with_time, kSideBaseClears},
     // inside the FIRSTWITHTIME / LASTWITHTIME pass (which counts its argument columns, covariance_columns_read), outside the variance's
     {is_covariance_agg, covariance_plan_check, execute_covariance, kSideBaseClears},
+    // inside the covariance pass, outside the variance's: SKEWNESS / KURTOSIS next to VAR_POP and PERCENTILE leave those to the passes below
+    {is_moment_agg, moment_plan_check, execute_moment, kSideBaseClears},
     // inside the expression pass, outside the PERCENTILE's: its ordinary part comes back through execute_query
     {is_variance_agg, variance_plan_check, execute_variance, kSideBaseClears},
     // its ordinary part comes back through execute_query; nulls in its columns are refused (percentile_plan_check)
@@ -223,6 +225,8 @@ const char* agg_function_text(int32_t fn) {
     case PG_AGG_STDDEVSAMP: return "STDDEV_SAMP";
     case PG_AGG_COVARPOP: return "COVAR_POP";
     case PG_AGG_COVARSAMP: return "COVAR_SAMP";
+    case PG_AGG_SKEWNESS: return "SKEWNESS";
+    case PG_AGG_KURTOSIS: return "KURTOSIS";
     case PG_AGG_FIRSTWITHTIME: return "FIRSTWITHTIME";
     case PG_AGG_LASTWITHTIME: return "LASTWITHTIME";
     default: return "this aggregation function";

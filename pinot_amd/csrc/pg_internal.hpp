@@ -450,7 +450,7 @@ struct PinnedBlock {
 std::shared_ptr<PinnedBlock> acquire_pinned(size_t bytes);
 struct AggResult {
   int32_t kind = PG_RESULT_DOUBLE;
-  std::vector<double> d[3];   // the third plane: PG_RESULT_COVARIANCE_TUPLE only
+  std::vector<double> d[4];   // the third plane: PG_RESULT_COVARIANCE_TUPLE and PG_RESULT_FOURTH_MOMENT, the fourth: PG_RESULT_FOURTH_MOMENT only
   std::vector<int64_t> l[2];
   std::vector<int32_t> set_sizes, set_ids;   // PG_RESULT_DICTID_SET: per group sizes, concatenated ascending dictIds
   int32_t set_value_kind = -1;               // PG_RESULT_VALUE_SET (a raw column through its virtual dictionary): 0 INT, 1 LONG (values in l[0]), 2 FLOAT, 3 DOUBLE (in d[0]; l[0] the IEEE bits), parallel to set_ids
@@ -464,6 +464,7 @@ struct AggResult {
   int32_t log2m = 0;
   // PG_RESULT_VARIANCE_TUPLE (VAR_POP / VAR_SAMP / STDDEV_POP / STDDEV_SAMP): l[0] = count, d[0] = sum, d[1] = m2
   // PG_RESULT_COVARIANCE_TUPLE (COVAR_POP / COVAR_SAMP): d[0] = sumX, d[1] = sumY, d[2] = sumXY, l[0] = count
+  // PG_RESULT_FOURTH_MOMENT (SKEWNESS / KURTOSIS): l[0] = n, d[0] .. d[3] = m1 .. m4
   // PG_RESULT_VALUE_TIME_PAIR (FIRSTWITHTIME / LASTWITHTIME): l[0] = time; l[1] = the value in its declared type — an INT / LONG value, or the
   // raw IEEE bits of a FLOAT (32, zero-extended) / DOUBLE —, d[0] = a FLOAT / DOUBLE value (the FLOAT widened exactly); `value_type` the
   // declared type (pg_data_type: the data table's object type and the width of its value)
@@ -532,6 +533,7 @@ struct Result {
   bool percentile = false;      // the query carried a PERCENTILE: its lists merge by value on the Java side (never merged in the library)
   bool expression = false;      // the query carried an aggregation over an expression: the scale of its sums differs per segment (never merged in the library)
   bool variance = false;        // the query carried a variance aggregation: its tuples merge on the Java side, VarianceTuple#apply (never merged in the library)
+  bool fourth_moment = false;   // the query carried a SKEWNESS / KURTOSIS: its tuples merge on the Java side, PinotFourthMoment#combine (never merged in the library)
   bool covariance = false;      // the query carried a COVAR_POP / COVAR_SAMP: its tuples merge on the Java side, CovarianceTuple#apply (never merged in the library)
   bool with_time = false;       // the query carried a FIRSTWITHTIME / LASTWITHTIME: its pairs merge on the Java side with the functions' own merge (never merged in the library)
   pg_exec_stats stats{};
@@ -561,7 +563,7 @@ constexpr int32_t kQueryFlagNullPartition = 0x40000000;
 std::unique_ptr<Result> execute_distinct(Segment& seg, const pg_query& q, const CancelToken* cancel);   // PG_QUERY_FLAG_DISTINCT (pg_exec.hip)
 std::unique_ptr<Result> execute_selection(Segment& seg, const pg_query& q, const CancelToken* cancel);  // PG_QUERY_FLAG_SELECTION (pg_exec.hip)
 // ---- side passes: aggregations answered by a pass of their own and joined to the ordinary plan by group key -------------------------------
-// The frame they share (pg_exec_sidepass.hip; `who` names the path in messages — "PERCENTILE" / "expression" / "variance" / "covariance" / "FIRSTWITHTIME / LASTWITHTIME" —,
+// The frame they share (pg_exec_sidepass.hip; `who` names the path in messages — "PERCENTILE" / "expression" / "variance" / "covariance" / "fourth-moment" / "FIRSTWITHTIME / LASTWITHTIME" —,
 // `subject` is how a refusal names its aggregation: "PERCENTILE" / "an aggregation over an expression" / "a variance aggregation" /
 // "FIRSTWITHTIME / LASTWITHTIME").
 bool column_has_nulls(Segment& seg, const std::string& name);   // seg.mu held
@@ -612,7 +614,7 @@ struct SidePassStats {
 // the ordinary part's columns and null vectors moved to their places in `out` (through B.base_index), `out` made the result's aggregations,
 // every statistic of the query written, the schema filled
 std::unique_ptr<Result> side_pass_finish(Segment& seg, const pg_query& q, const SideBaseQuery& B, SidePass& S, std::vector<AggResult>& out, const SidePassStats& P);
-// ---- the slot-table paths (expressions, the variance family, COVAR_POP / COVAR_SAMP, FIRSTWITHTIME / LASTWITHTIME): a table [G][slots] of 64-bit slots, filled over
+// ---- the slot-table paths (expressions, the variance family, COVAR_POP / COVAR_SAMP, SKEWNESS / KURTOSIS, FIRSTWITHTIME / LASTWITHTIME): a table [G][slots] of 64-bit slots, filled over
 // the match words by one of three tiers (side_tier, pg_side_query.h; the kernels' half is pg_side_scan.h) and gathered for the admitted rows
 int side_pass_grid(int tier, int cus, int64_t n_words, int64_t lds_wgs_per_cu = 1);   // workgroups of a tier's pass: persistent ones in the LDS tier
 int side_flat_grid(int cus, int64_t items);                                           // ... of a kernel with one thread per item (256 per workgroup)
@@ -676,6 +678,11 @@ bool is_covariance_agg(const pg_agg_spec& s);
 void covariance_plan_check(Segment& seg, const pg_query& q);
 std::unique_ptr<Result> execute_covariance(Segment& seg, const pg_query& q, const CancelToken* cancel);
 void covariance_columns_read(const pg_agg_spec& s, std::set<std::string>& read);
+// SKEWNESS / KURTOSIS (pg_exec_moment.hip): one accumulation pass of the exact power sums up to x^4 (pg_moment4.h) for all of them
+bool is_moment_function(int32_t fn);
+bool is_moment_agg(const pg_agg_spec& s);
+void moment_plan_check(Segment& seg, const pg_query& q);
+std::unique_ptr<Result> execute_moment(Segment& seg, const pg_query& q, const CancelToken* cancel);
 std::unique_ptr<Result> execute_query_plain(Segment& seg, const pg_query& q, const CancelToken* cancel);   // ... the executor proper (pg_exec.hip)
 void fill_result_schema(Segment& seg, const pg_query& q, Result& r);
 int64_t hll_cardinality(const uint8_t* regs, int log2m);   // HyperLogLog#cardinality of one register row (pg_exec.hip)
@@ -749,6 +756,7 @@ struct Knobs {
   int64_t expr_lds_max_slots = 16384;                // PG_EXPR_LDS_MAX_SLOTS
   int64_t expr_hbm_max_bytes = (int64_t)256 << 20;   // PG_EXPR_HBM_MAX_BYTES
   int64_t var_hbm_max_bytes = (int64_t)256 << 20;    // PG_VAR_HBM_MAX_BYTES: the slot table of the variance aggregations (pg_exec_var.hip) beyond its LDS tier; larger ones are refused
+  int64_t moment_hbm_max_bytes = (int64_t)256 << 20; // PG_MOMENT_HBM_MAX_BYTES: the slot table of the SKEWNESS / KURTOSIS aggregations (pg_exec_moment.hip) beyond its LDS tier; larger ones are refused
   int64_t covar_hbm_max_bytes = (int64_t)256 << 20;  // PG_COVAR_HBM_MAX_BYTES: the slot table of the covariance aggregations (pg_exec_covar.hip) beyond its LDS tier; larger ones are refused
   int64_t wt_hbm_max_bytes = (int64_t)256 << 20;     // PG_WT_HBM_MAX_BYTES: the planes of FIRSTWITHTIME / LASTWITHTIME (pg_exec_withtime.hip) beyond their LDS tier; larger ones are refused
   int64_t limit_prefix_min_docs = (int64_t)1 << 20;   // PG_LIMIT_PREFIX_MIN_DOCS: smallest doc prefix of the numGroupsLimit admission pass (tests lower it)

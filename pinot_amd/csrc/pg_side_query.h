@@ -1,6 +1,6 @@
 // The ordinary part of a query that carries side aggregations — aggregations answered by a pass of their own and joined to the ordinary plan
 // by group key (exact PERCENTILE: pg_exec_percentile.hip; aggregations over an expression: pg_exec_expr.hip; VAR_POP / VAR_SAMP /
-// STDDEV_POP / STDDEV_SAMP: pg_exec_var.hip; FIRSTWITHTIME / LASTWITHTIME: pg_exec_withtime.hip; the frame they share:
+// STDDEV_POP / STDDEV_SAMP: pg_exec_var.hip; FIRSTWITHTIME / LASTWITHTIME: pg_exec_withtime.hip; SKEWNESS / KURTOSIS: pg_exec_moment.hip; the frame they share:
 // pg_exec_sidepass.hip).  Plain C++ over include/pinot_gpu.h without HIP types: it compiles stand-alone (tests/side_query_main.cpp).
 #pragma once
 #include "../../include/pinot_gpu.h"

@@ -452,6 +452,13 @@ class ResultsBlock:
                     api.call("result_doubles", h, a, c, sums[c].ctypes.data, ng)
                 api.call("result_longs", h, a, 0, n.ctypes.data, ng)
                 rb.arrays.append((k, sums[0], sums[1], sums[2], n))
+            elif k == capi.RESULT_FOURTH_MOMENT:   # SKEWNESS / KURTOSIS: PinotFourthMoment(n, m1, m2, m3, m4)
+                n = np.zeros(ng, dtype=np.int64)
+                m = [np.zeros(ng, dtype=np.float64) for _ in range(4)]
+                api.call("result_longs", h, a, 0, n.ctypes.data, ng)
+                for c in range(4):
+                    api.call("result_doubles", h, a, c, m[c].ctypes.data, ng)
+                rb.arrays.append((k, n, m[0], m[1], m[2], m[3]))
             elif k == capi.RESULT_VALUE_TIME_PAIR:   # FIRSTWITHTIME / LASTWITHTIME: ValueLongPair(value, time), the value in its declared type
                 floating = with_time_arguments(spec.column)[2] in ("FLOAT", "DOUBLE")
                 t = np.zeros(ng, dtype=np.int64)
@@ -557,6 +564,8 @@ class ResultsBlock:
                     cols.append([(int(n), float(s), float(m2)) for n, s, m2 in zip(arr[1], arr[2], arr[3])])
                 elif k == capi.RESULT_COVARIANCE_TUPLE:   # (sumX, sumY, sumXY, count) per group
                     cols.append([(float(sx), float(sy), float(sxy), int(n)) for sx, sy, sxy, n in zip(arr[1], arr[2], arr[3], arr[4])])
+                elif k == capi.RESULT_FOURTH_MOMENT:   # (n, m1, m2, m3, m4) per group
+                    cols.append([(int(n), float(m1), float(m2), float(m3), float(m4)) for n, m1, m2, m3, m4 in zip(*arr[1:6])])
                 elif k == capi.RESULT_VALUE_TIME_PAIR:   # (value, time) per group; a FLOAT / DOUBLE value keeps its bits (NaN payloads, -0.0)
                     cols.append([(v.item(), int(t)) for v, t in zip(arr[1], arr[2])])
                 elif k == capi.RESULT_VALUE_COUNTS:   # (values, counts) per group
@@ -672,6 +681,57 @@ def covariance_merge(a, b):
     return (a[0] + b[0], a[1] + b[1], a[2] + b[2], a[3] + b[3])
 
 
+def skewness_final(t) -> float:
+    """FourthMomentAggregationFunction#extractFinalResult for SKEWNESS over the tuple (n, m1, m2, m3, m4) — Commons Math Skewness#getResult:
+    NaN for n < 3; with the variance v = m2 / (n - 1), 0.0 for v < 10E-20; else n m3 / ((n - 1)(n - 2) sqrt(v) v)."""
+    n, _, m2, m3, _ = t
+    if n < 3:
+        return float("nan")
+    with np.errstate(all="ignore"):   # Java double arithmetic: never an exception
+        n0, v = np.float64(n), np.float64(m2) / np.float64(n - 1)
+        if v < 10E-20:
+            return 0.0
+        return float((n0 * np.float64(m3)) / ((n0 - 1) * (n0 - 2) * np.sqrt(v) * v))
+
+
+def kurtosis_final(t) -> float:
+    """... for KURTOSIS — Commons Math Kurtosis#getResult: NaN for n <= 3; 0.0 for a variance v = m2 / (n - 1) below 10E-20; else
+    (n (n + 1) m4 - 3 m2 m2 (n - 1)) / ((n - 1)(n - 2)(n - 3) v v)."""
+    n, _, m2, _, m4 = t
+    if n <= 3:
+        return float("nan")
+    with np.errstate(all="ignore"):
+        n0, m2, m4 = np.float64(n), np.float64(m2), np.float64(m4)
+        v = m2 / (n0 - 1)
+        if v < 10E-20:
+            return 0.0
+        return float((n0 * (n0 + 1) * m4 - 3 * m2 * m2 * (n0 - 1)) / ((n0 - 1) * (n0 - 2) * (n0 - 3) * v * v))
+
+
+def fourth_moment_merge(a, b):
+    """PinotFourthMoment#combine: `b` merged into `a` (what the Java side does with the tuples of two segments) — the pairwise update of the
+    mean and the central sums, in double; an empty side leaves the other as it is."""
+    if b[0] == 0:
+        return a
+    if a[0] == 0:
+        return b
+    with np.errstate(all="ignore"):
+        an, a1, a2, a3, a4 = a[0], *(np.float64(x) for x in a[1:])
+        bn, b1, b2, b3, b4 = b[0], *(np.float64(x) for x in b[1:])
+        n = an + bn
+        fa, fb, fn = np.float64(an), np.float64(bn), np.float64(n)
+        m1 = (fa * a1 + fb * b1) / fn
+        d = b1 - a1
+        d2 = d * d
+        m2 = a2 + b2 + d2 * fa * fb / fn
+        d3 = d2 * d
+        m3 = a3 + b3 + d3 * fa * fb * np.float64(an - bn) / np.float64(n * n) + 3.0 * d * (fa * b2 - fb * a2) / fn
+        d4 = d3 * d
+        m4 = (a4 + b4 + d4 * fa * fb * np.float64(an * an - an * bn + bn * bn) / (fn * fn * fn)
+              + 6.0 * d2 * (np.float64(an * an) * b2 + np.float64(bn * bn) * a2) / np.float64(n * n) + 4.0 * d * (fa * b3 - fb * a3) / fn)
+    return (n, float(m1), float(m2), float(m3), float(m4))
+
+
 def with_time_merge(function: str, a, b):
     """FirstWithTimeAggregationFunction#merge / LastWithTimeAggregationFunction#merge over two (value, time) pairs, what the Java side does
     with the pairs of two segments: LAST keeps `a` where a.time >= b.time, FIRST where a.time <= b.time — the first argument wins a tie."""
@@ -709,6 +769,8 @@ def merge_intermediate(function: str, a, b):
         return variance_merge(a, b)
     if function in capi.COVARIANCE_FUNCTIONS:
         return covariance_merge(a, b)
+    if function in capi.FOURTH_MOMENT_FUNCTIONS:
+        return fourth_moment_merge(a, b)
     if function in capi.WITH_TIME_FUNCTIONS:
         return with_time_merge(function, a, b)
     raise ValueError(function)
@@ -729,6 +791,8 @@ def extract_final(function: str, v):
         return variance_final(function, v)
     if function in capi.COVARIANCE_FUNCTIONS:
         return covariance_final(function, v)
+    if function in capi.FOURTH_MOMENT_FUNCTIONS:
+        return skewness_final(v) if function == "SKEWNESS" else kurtosis_final(v)
     if function in capi.WITH_TIME_FUNCTIONS:   # the pair's value
         return v[0]
     return v

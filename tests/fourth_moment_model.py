@@ -1,0 +1,219 @@
+"""An independent model of SKEWNESS / KURTOSIS over decoded columns (FourthMomentAggregationFunction and its intermediate
+PinotFourthMoment(n, m1, m2, m3, m4): m1 the mean, m_k the sum of (x - mean)^k).
+
+  exact_tuple       what the GPU path returns: n exact, each of m1 .. m4 the exact value rounded once (nearest-even), from fractions.Fraction
+                    over the power sums (the identities of pinot_amd/csrc/pg_moment4.h; direct_moments is the definition they are checked
+                    against); (0, NaN, NaN, NaN, NaN) over no doc, (1, x, 0.0, 0.0, 0.0) over one
+  reference_tuple   a restatement of what the reference computes in docId order in IEEE double — the one-pass update of the mean and the
+                    central sums per doc (Commons Math FourthMoment#increment, from its documented recurrences), block tuples merged with
+                    combine() — which gives its drift from the exact value
+  combine           PinotFourthMoment#combine
+  skewness, kurtosis   the final values (Commons Math Skewness / Kurtosis#getResult, from their documented formulas)
+
+and the vectors the host harness (tests/test_moment4_host.py) and the GPU tests (tests/test_gpu_moments.py) share."""
+import math
+import os
+import re
+import struct
+from fractions import Fraction
+
+import numpy as np
+
+from tests.variance_model import as_doubles, fx_exp_of, round_fraction, same_bits, ulp  # noqa: F401  (shared with the variance model)
+
+NAN = float("nan")
+FUNCTIONS = ("SKEWNESS", "KURTOSIS")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+MAX_DOC_PER_CALL = 10000   # DocIdSetPlanNode.MAX_DOC_PER_CALL: the reference aggregates block by block
+VARIANCE_THRESHOLD = 10E-20   # below it Skewness / Kurtosis#getResult return 0.0
+
+
+def power_sums(doubles):
+    """(n, S1, S2, S3, S4) as exact Fractions"""
+    n = len(doubles)
+    if n == 0:
+        return 0, Fraction(0), Fraction(0), Fraction(0), Fraction(0)
+    # every double is an integer times 2^-1074: integer sums, one Fraction each at the end
+    parts = [v.as_integer_ratio() for v in doubles]
+    scale = max(d for _, d in parts)   # a power of two
+    ints = [m * (scale // d) for m, d in parts]
+    return (n,) + tuple(Fraction(sum(i ** k for i in ints), scale ** k) for k in (1, 2, 3, 4))
+
+
+def exact_moments(doubles):
+    """(n, m1, m2, m3, m4) as exact Fractions through the power sums (n >= 1)"""
+    n, s1, s2, s3, s4 = power_sums(doubles)
+    return (n, s1 / n, s2 - s1 * s1 / n, s3 - 3 * s1 * s2 / n + 2 * s1 ** 3 / n ** 2,
+            s4 - 4 * s1 * s3 / n + 6 * s1 * s1 * s2 / n ** 2 - 3 * s1 ** 4 / n ** 3)
+
+
+def direct_moments(doubles):
+    """the definition: (n, mean, sum (x - mean)^2, sum (x - mean)^3, sum (x - mean)^4) as exact Fractions (n >= 1)"""
+    xs = [Fraction(v) for v in doubles]
+    n = len(xs)
+    mean = sum(xs) / n
+    return (n, mean) + tuple(sum((x - mean) ** k for x in xs) for k in (2, 3, 4))
+
+
+def exact_tuple(doubles) -> tuple:
+    if not doubles:
+        return 0, NAN, NAN, NAN, NAN   # a fresh PinotFourthMoment
+    n, m1, m2, m3, m4 = exact_moments(doubles)
+    return n, round_fraction(m1), round_fraction(m2), round_fraction(m3), round_fraction(m4)
+
+
+def _increment(t, d):
+    """one doc into t = [n, m1, m2, m3, m4] (FirstMoment .. FourthMoment#increment)"""
+    if t[0] < 1:
+        t[1] = t[2] = t[3] = t[4] = 0.0
+    prev_m3, prev_m2 = t[3], t[2]
+    t[0] += 1
+    n0 = float(t[0])
+    dev = d - t[1]
+    n_dev = dev / n0
+    t[1] += n_dev
+    t[2] += (n0 - 1.0) * dev * n_dev
+    n_dev_sq = n_dev * n_dev
+    t[3] = t[3] - 3.0 * n_dev * prev_m2 + (n0 - 1.0) * (n0 - 2.0) * n_dev_sq * dev
+    t[4] = t[4] - 4.0 * n_dev * prev_m3 + 6.0 * n_dev_sq * prev_m2 + ((n0 * n0) - 3.0 * (n0 - 1.0)) * (n_dev_sq * n_dev_sq * (n0 - 1.0) * n0)
+
+
+def combine(a, b) -> tuple:
+    """PinotFourthMoment#combine: b merged into a; Java's operation order (longs promoted where a double meets them)"""
+    if b[0] == 0:
+        return tuple(a)
+    if a[0] == 0:
+        return tuple(b)
+    an, a1, a2, a3, a4 = a
+    bn, b1, b2, b3, b4 = b
+    n = an + bn
+    fa, fb, fn = float(an), float(bn), float(n)
+    m1 = (fa * a1 + fb * b1) / fn
+    d = b1 - a1
+    d2 = d * d
+    m2 = a2 + b2 + d2 * fa * fb / fn
+    d3 = d2 * d
+    m3 = a3 + b3 + d3 * fa * fb * float(an - bn) / float(n * n) + 3.0 * d * (fa * b2 - fb * a2) / fn
+    d4 = d3 * d
+    m4 = (a4 + b4 + d4 * fa * fb * float(an * an - an * bn + bn * bn) / (fn * fn * fn)
+          + 6.0 * d2 * (float(an * an) * b2 + float(bn * bn) * a2) / float(n * n) + 4.0 * d * (fa * b3 - fb * a3) / fn)
+    return n, m1, m2, m3, m4
+
+
+def reference_tuple(doubles) -> tuple:
+    """The reference's doubles in docId order: per block a fresh tuple incremented doc by doc, combined into the holder."""
+    holder = (0, NAN, NAN, NAN, NAN)
+    for b0 in range(0, len(doubles), MAX_DOC_PER_CALL):
+        t = [0, NAN, NAN, NAN, NAN]
+        for v in doubles[b0:b0 + MAX_DOC_PER_CALL]:
+            _increment(t, v)
+        holder = combine(holder, tuple(t))
+    return holder
+
+
+def skewness(t) -> float:
+    n, _, m2, m3, _ = t
+    if n < 3:
+        return NAN
+    variance = m2 / (n - 1)
+    if variance < VARIANCE_THRESHOLD:
+        return 0.0
+    n0 = float(n)
+    return (n0 * m3) / ((n0 - 1) * (n0 - 2) * math.sqrt(variance) * variance)
+
+
+def kurtosis(t) -> float:
+    n, _, m2, _, m4 = t
+    if n <= 3:
+        return NAN
+    variance = m2 / (n - 1)
+    if variance < VARIANCE_THRESHOLD:
+        return 0.0
+    n0 = float(n)
+    return (n0 * (n0 + 1) * m4 - 3 * m2 * m2 * (n0 - 1)) / ((n0 - 1) * (n0 - 2) * (n0 - 3) * variance * variance)
+
+
+def final(function: str, t) -> float:
+    return skewness(t) if function == "SKEWNESS" else kurtosis(t)
+
+
+def to_bytes(t) -> bytes:
+    """PinotFourthMoment#serialize: long n, doubles m1 .. m4, big-endian"""
+    return struct.pack(">qdddd", int(t[0]), *(float(x) for x in t[1:]))
+
+
+def same_tuple(a, b) -> bool:
+    """n equal and the four doubles equal bit for bit (a NaN equals a NaN)"""
+    return a[0] == b[0] and all((math.isnan(x) and math.isnan(y)) or same_bits(x, y) for x, y in zip(a[1:], b[1:]))
+
+
+# ---- the windows of pg_moment4.h, from the headers' own constants -----------------------------------------------------------------------------------
+_NAMES = ("PG_VAR_SUM_LIMBS", "PG_VAR_SQ_LIMBS", "PG_VAR_LONG_EXP", "PG_M4_CUBE_LIMBS", "PG_M4_QUAD_LIMBS", "PG_M4_INT_SLOTS", "PG_MOMENT_LDS_SLOTS",
+          "PG_MOMENT_MAX_COLS", "PG_WIDE_WORDS", "PG_WIDE_GUARD")
+
+
+def header_constants() -> dict:
+    text = "".join(open(os.path.join(ROOT, "pinot_amd", "csrc", f)).read() for f in ("pg_moments.h", "pg_moment4.h"))
+    k = {name: int(re.search(r"#define %s (\d+)" % name, text).group(1)) for name in _NAMES}
+    k["PG_M4_DBL_SLOTS"] = k["PG_VAR_SUM_LIMBS"] + k["PG_VAR_SQ_LIMBS"] + k["PG_M4_CUBE_LIMBS"] + k["PG_M4_QUAD_LIMBS"]
+    return k
+
+
+def limbs(k: dict = None) -> tuple:
+    k = k or header_constants()
+    return k["PG_VAR_SUM_LIMBS"], k["PG_VAR_SQ_LIMBS"], k["PG_M4_CUBE_LIMBS"], k["PG_M4_QUAD_LIMBS"]
+
+
+def scales(E: int, k: dict = None) -> tuple:
+    """(q1, q2, q3, q4): q_k = k E - 32 L_k + 1"""
+    return tuple(p * E - 32 * L + 1 for p, L in zip((1, 2, 3, 4), limbs(k)))
+
+
+def truncation_bounds(n: int, E: int, k: dict = None) -> tuple:
+    """how far m1 .. m4 may be from the exact values BEFORE their one rounding when values fall below the windows (pg_moment4.h)"""
+    q1, q2, q3, q4 = scales(E, k)
+    two = Fraction(2)
+    return (two ** q1,
+            n * (two ** q2 + 2 * two ** (E + q1)),
+            n * (two ** q3 + 3 * two ** (E + q2) + 9 * two ** (2 * E + q1)),
+            n * (two ** q4 + 4 * two ** (E + q3) + 6 * two ** (2 * E + q2) + 28 * two ** (3 * E + q1)))
+
+
+# ---- shared vectors: name -> (data type, values) ------------------------------------------------------------------------------------------------
+def _vectors():
+    rng = np.random.default_rng(20251)
+    v = {}
+    v["all_equal"] = ("DOUBLE", [0.1] * 100)
+    v["n1"] = ("DOUBLE", [3.5])
+    v["n2"] = ("DOUBLE", [1.5, 2.5])
+    v["n3"] = ("DOUBLE", [1.5, 2.5, 7.0])
+    v["n4"] = ("DOUBLE", [1.5, 2.5, 7.0, -3.25])
+    v["mean1e9_double"] = ("DOUBLE", (1e9 + rng.standard_normal(2000)).tolist())
+    v["mean1e9_int"] = ("INT", (10**9 + rng.integers(-3, 4, 2000)).tolist())
+    v["int_extremes"] = ("INT", [-2**31, 2**31 - 1, -2**31, 2**31 - 1, 0, -1, 1, -2**31])
+    big = [2**62, -2**62, 2**62 + 1, -(2**62) - 1, 2**62 - 1, 2**53 + 1, -(2**53) - 3, 2**63 - 1, -2**63]
+    v["long_2_62"] = ("LONG", big * 3)
+    v["long_2_62_same_sign"] = ("LONG", [2**62 + int(x) for x in rng.integers(0, 2**40, 500)])
+    v["floats"] = ("FLOAT", rng.uniform(1.0, 1000.0, 777).astype(np.float32).tolist())
+    v["subnormals"] = ("DOUBLE", [float(x) * 5e-324 for x in rng.integers(1, 1000, 300)])
+    v["tiny_m4"] = ("DOUBLE", (rng.uniform(1.0, 2.0, 100) * 2.0**-262).tolist())   # m4 is a subnormal: one rounding at 2^-1074
+    v["at_2_200"] = ("DOUBLE", (rng.uniform(1.0, 8.0, 400) * 2.0**200).tolist())
+    v["mean_2_200"] = ("DOUBLE", ((1e6 + rng.standard_normal(300)) * 2.0**200).tolist())
+    v["at_2_m200"] = ("DOUBLE", (rng.uniform(1.0, 900.0, 400) * 2.0**-200).tolist())
+    v["alternating"] = ("DOUBLE", [(-1.0) ** i * (1000.0 + i * 0.125) for i in range(1001)])
+    v["symmetric"] = ("DOUBLE", [5.0 + s * d for d in (0.25, 1.5, 3.0, 10.125) for s in (-1, 1)] + [5.0])   # m3 is exactly 0
+    v["zeros_and_values"] = ("DOUBLE", [0.0, -0.0, 7.25, 0.0, 7.5, -0.0])
+    v["negative_skew"] = ("DOUBLE", [-(x * x) for x in rng.uniform(1.0, 30.0, 500).tolist()])
+    return v
+
+
+VECTORS = _vectors()
+# magnitudes 2^-60 .. 2^60: most values fall below the windows; held to the documented bounds, not to exactness
+WIDE_RANGE = ("DOUBLE", [float(m) * 2.0**int(e) * (-1.0) ** i for i, (m, e) in enumerate(zip(np.random.default_rng(7).uniform(1, 2, 601), np.linspace(-60, 60, 601)))])
+
+
+def in_exact_window(doubles) -> bool:
+    """non-zero magnitudes span at most 2^10: with E up to 16 above the largest exponent every value is within 2^-26 of 2^E, well inside the
+    windows of pg_moment4.h (k (s + 53) <= 32 L_k - 1 holds up to s = 42)"""
+    mags = [abs(v) for v in doubles if v != 0]
+    return not mags or max(mags) <= min(mags) * 1024
