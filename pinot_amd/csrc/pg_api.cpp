@@ -310,17 +310,25 @@ int32_t pg_query_exec_cancellable(pg_segment_t segment, const pg_query* query, p
   });
 }
 
+// results that carry a side aggregation are never merged in the library: the first kind a result carries words the refusal
+static void refuse_merged_elsewhere(uint32_t kinds) {
+  static const struct { uint32_t bit; const char* text; } kRefusals[] = {
+      {MERGED_PERCENTILE, "PERCENTILE results are merged by value (DoubleArrayList#addAll on the Java side)"},
+      {MERGED_EXPRESSION, "results of aggregations over expressions are merged by value on the Java side (the scale of their exact sums differs per segment)"},
+      {MERGED_VARIANCE, "results of variance aggregations are merged on the Java side (VarianceTuple#apply)"},
+      {MERGED_FOURTH_MOMENT, "results of SKEWNESS / KURTOSIS aggregations are merged on the Java side (PinotFourthMoment#combine)"},
+      {MERGED_COVARIANCE, "results of covariance aggregations are merged on the Java side (CovarianceTuple#apply)"},
+      {MERGED_WITH_TIME, "results of FIRSTWITHTIME / LASTWITHTIME are merged on the Java side (the functions' own merge of ValueLongPair)"},
+  };
+  for (const auto& r : kRefusals) if (kinds & r.bit) fail(PG_ERR_UNSUPPORTED, "%s", r.text);
+}
+
 int32_t pg_result_merge(pg_result_t dst, pg_result_t src) {
   return guarded([&] {
     REQUIRE(dst && src && dst != src, "null or identical results");
     if (dst->r->distinct || src->r->distinct) fail(PG_ERR_UNSUPPORTED, "distinct results are merged by value (DistinctCombineOperator)");
     if (dst->r->selection || src->r->selection) fail(PG_ERR_UNSUPPORTED, "selection results are merged by value (SelectionCombineOperator)");
-    if (dst->r->percentile || src->r->percentile) fail(PG_ERR_UNSUPPORTED, "PERCENTILE results are merged by value (DoubleArrayList#addAll on the Java side)");
-    if (dst->r->expression || src->r->expression) fail(PG_ERR_UNSUPPORTED, "results of aggregations over expressions are merged by value on the Java side (the scale of their exact sums differs per segment)");
-    if (dst->r->variance || src->r->variance) fail(PG_ERR_UNSUPPORTED, "results of variance aggregations are merged on the Java side (VarianceTuple#apply)");
-    if (dst->r->fourth_moment || src->r->fourth_moment) fail(PG_ERR_UNSUPPORTED, "results of SKEWNESS / KURTOSIS aggregations are merged on the Java side (PinotFourthMoment#combine)");
-    if (dst->r->covariance || src->r->covariance) fail(PG_ERR_UNSUPPORTED, "results of covariance aggregations are merged on the Java side (CovarianceTuple#apply)");
-    if (dst->r->with_time || src->r->with_time) fail(PG_ERR_UNSUPPORTED, "results of FIRSTWITHTIME / LASTWITHTIME are merged on the Java side (the functions' own merge of ValueLongPair)");
+    refuse_merged_elsewhere(dst->r->merged_elsewhere | src->r->merged_elsewhere);
     result_merge(*dst->r, *src->r);
   });
 }
@@ -329,12 +337,7 @@ int32_t pg_result_all_reduce(pg_result_t result, pg_comm_t comm) {
     REQUIRE(result && comm && comm->c, "null argument");
     if (result->r->distinct) fail(PG_ERR_UNSUPPORTED, "distinct results are merged by value (DistinctCombineOperator)");
     if (result->r->selection) fail(PG_ERR_UNSUPPORTED, "selection results are merged by value (SelectionCombineOperator)");
-    if (result->r->percentile) fail(PG_ERR_UNSUPPORTED, "PERCENTILE results are merged by value (DoubleArrayList#addAll on the Java side)");
-    if (result->r->expression) fail(PG_ERR_UNSUPPORTED, "results of aggregations over expressions are merged by value on the Java side (the scale of their exact sums differs per segment)");
-    if (result->r->variance) fail(PG_ERR_UNSUPPORTED, "results of variance aggregations are merged on the Java side (VarianceTuple#apply)");
-    if (result->r->fourth_moment) fail(PG_ERR_UNSUPPORTED, "results of SKEWNESS / KURTOSIS aggregations are merged on the Java side (PinotFourthMoment#combine)");
-    if (result->r->covariance) fail(PG_ERR_UNSUPPORTED, "results of covariance aggregations are merged on the Java side (CovarianceTuple#apply)");
-    if (result->r->with_time) fail(PG_ERR_UNSUPPORTED, "results of FIRSTWITHTIME / LASTWITHTIME are merged on the Java side (the functions' own merge of ValueLongPair)");
+    refuse_merged_elsewhere(result->r->merged_elsewhere);
     result_all_reduce(*result->r, *comm->c);
   });
 }

@@ -1,17 +1,15 @@
 // Queries with a COVAR_POP / COVAR_SAMP aggregation (PG_AGG_COVARPOP, PG_AGG_COVARSAMP): a side pass joined to the ordinary plan by group
-// key, in the frame of pg_exec_sidepass.hip (which runs step 1 and the filter, maps the admitted groups to rows and joins the result,
-// step 4).
-//   1. The ordinary part — the query without its covariance aggregations (COUNT(*) if nothing else remains) — runs through execute_query
-//      unchanged, never on a star-tree: it decides the groups, the numGroupsLimit admission and the other aggregations' results (a variance
-//      or a PERCENTILE among them takes its own side pass from there).  An ORDER BY that names a covariance leaves the segment untrimmed.
-//   2. One fused accumulation pass for ALL covariance aggregations of the query over the filter's match words into a table [G][slots] of
-//      int64: slot 0 the doc count, then per distinct argument column (at most PG_COVAR_MAX_COLS) the digits of its sum, then per distinct
-//      ordered pair (at most PG_COVAR_MAX_PAIRS; COVAR_POP(x,y), COVAR_SAMP(x,y) share one) the digits of the rounded products
-//      (pg_covar.h).  pg_covar_reg without GROUP BY (pg_covar_reg_wide for more than one pair), pg_covar_lds up to PG_COVAR_LDS_SLOTS slots, pg_covar_hbm up to
-//      Knobs::covar_hbm_max_bytes; beyond that the query is refused.
-//   3. The rows of the admitted groups are gathered on the device (pg_expr_gather); the host rounds each of the three sums once.
-//   4. The tuples are joined to the ordinary part on the host.
-// The kernels are those of pg_kernels_covar.hip.
+// key.  The pass is the sum-table pass of pg_exec_sidepass.hip (SumTablePass: the ordinary part, the filter's match words, the table, the
+// timed accumulation and gather, the doc-count checks, the join and the statistics); this file holds what is the path's own:
+//   the plan     the argument lists, and one table [G][slots] of int64 for ALL covariance aggregations of the query, filled by one fused
+//                pass: slot 0 the doc count, then per distinct argument column (at most PG_COVAR_MAX_COLS) the digits of its sum, then per
+//                distinct ordered pair (at most PG_COVAR_MAX_PAIRS; COVAR_POP(x,y), COVAR_SAMP(x,y) share one) the digits of the rounded
+//                products (pg_covar.h).  pg_covar_reg without GROUP BY (pg_covar_reg_wide for more than one pair), pg_covar_lds up to
+//                PG_COVAR_LDS_SLOTS slots, pg_covar_hbm up to Knobs::covar_hbm_max_bytes; beyond that the query is refused.
+//   the kernels' arguments (PgCovarArgs; the kernels are those of pg_kernels_covar.hip) and the LDS tier's workgroups per CU
+//   the tuples   the host forms (sumX, sumY, sumXY, count) of every admitted group from its gathered row, each of the three sums rounded once.
+// The ordinary part is the query without its covariance aggregations (a variance or a PERCENTILE among the others takes its own side pass
+// from there); an ORDER BY that names a covariance leaves the segment untrimmed.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -24,7 +22,6 @@
 #include "pg_covar.h"
 
 void pg_covar_launch_pass(const PgCovarArgs* args, int tier, int grid, hipStream_t stream);
-void pg_expr_launch_gather(const int64_t* table, const uint32_t* rows, int32_t n_rows, int32_t slots, uint64_t n_groups, int64_t* out, int grid, hipStream_t stream);
 
 namespace pg {
 namespace {
@@ -64,13 +61,9 @@ struct CovarPair {
   std::vector<int> aggs;    // the covariance aggregations over it (indexes into the query's)
 };
 struct CovarPlan {
-  SideGroups groups;
+  SideTable table;
   std::vector<CovarColumn> cols;
   std::vector<CovarPair> pairs;
-  int32_t slots = 1;            // slot 0: the doc count
-  uint64_t n_slots = 0;
-  int tier = TIER_REG;
-  int n_columns_read = 0;       // distinct columns the query projects (ProjectOperator#getNumColumnsProjected)
 };
 
 CovarPlan covar_plan(Segment& seg, const pg_query& q) {
@@ -80,10 +73,7 @@ CovarPlan covar_plan(Segment& seg, const pg_query& q) {
   std::set<std::string> read;
   std::lock_guard<std::mutex> lock(seg.mu);   // virtual dictionaries are built under the segment's lock
   auto column_index = [&](const std::string& name, const char* fn) {
-    Column* c = side_argument_column(seg, name.c_str(), fn, "column", "argument column", "", null_handling);
-    // the registration pass (pg_segment.cpp) knows every FLOAT / DOUBLE column's non-finite values: the sums have no digits for them
-    if ((c->val_type == PG_V_F32 || c->val_type == PG_V_F64) && c->has_nonfinite)
-      fail(PG_ERR_UNSUPPORTED, "%s over %s, which holds a NaN or an infinity: the Java plan answers such a query", fn, c->name.c_str());
+    Column* c = side_value_column(seg, name.c_str(), fn, null_handling);
     size_t k = 0;
     while (k < P.cols.size() && P.cols[k].col != c) k++;
     if (k == P.cols.size()) {
@@ -100,7 +90,7 @@ CovarPlan covar_plan(Segment& seg, const pg_query& q) {
   for (int a = 0; a < q.n_aggregations; a++) {
     const pg_agg_spec& s = q.aggregations[a];
     if (!is_covariance_agg(s)) {
-      if (s.column && strcmp(s.column, "*") != 0) read.insert(s.column);
+      side_columns_read(s, read);
       continue;
     }
     const char* fn = agg_function_text(s.function);
@@ -123,53 +113,25 @@ CovarPlan covar_plan(Segment& seg, const pg_query& q) {
     }
     P.pairs[k].aggs.push_back(a);
   }
-  for (CovarColumn& cc : P.cols) { cc.first_slot = P.slots; P.slots += pg_covar_col_slots(cc.is_int); }
-  for (CovarPair& cp : P.pairs) { cp.first_slot = P.slots; P.slots += PG_COVAR_PROD_LIMBS; }
-  P.groups = side_groups(seg, q, kSubject, kWho, read);
-  P.n_columns_read = (int)read.size();
-  P.n_slots = P.groups.G * (uint64_t)P.slots;   // < 2^39
-  const Knobs& K = knobs();
-  P.tier = side_tier(q.n_group_by, P.n_slots, PG_COVAR_LDS_SLOTS, P.n_slots * 8, K.covar_hbm_max_bytes);
-  if (P.tier == TIER_REFUSED)
-    fail(PG_ERR_UNSUPPORTED, "covariance aggregations: %llu groups x %d slots need a table of %llu bytes, more than PG_COVAR_HBM_MAX_BYTES (%lld)",
-         (unsigned long long)P.groups.G, P.slots, (unsigned long long)(P.n_slots * 8), (long long)K.covar_hbm_max_bytes);
+  int32_t slots = 1;   // slot 0: the doc count
+  for (CovarColumn& cc : P.cols) { cc.first_slot = slots; slots += pg_covar_col_slots(cc.is_int); }
+  for (CovarPair& cp : P.pairs) { cp.first_slot = slots; slots += PG_COVAR_PROD_LIMBS; }
+  P.table = side_table_plan(seg, q, kSubject, kWho, read, slots, PG_COVAR_LDS_SLOTS, 8, knobs().covar_hbm_max_bytes, "covariance aggregations", "PG_COVAR_HBM_MAX_BYTES");
   return P;
 }
 
 }  // namespace
 
-bool is_covariance_function(int32_t fn) { return fn == PG_AGG_COVARPOP || fn == PG_AGG_COVARSAMP; }
-bool is_covariance_agg(const pg_agg_spec& s) { return is_covariance_function(s.function); }
+bool is_covariance_agg(const pg_agg_spec& s) { return s.function == PG_AGG_COVARPOP || s.function == PG_AGG_COVARSAMP; }
 void covariance_plan_check(Segment& seg, const pg_query& q) { (void)covar_plan(seg, q); }
 
-void covariance_columns_read(const pg_agg_spec& s, std::set<std::string>& read) {
-  std::vector<ExprArgument> args;
-  std::string error;
-  if (!s.column || expr_split_arguments(s.column, args, error) != PG_OK || args.size() != 2) return;
-  for (const ExprArgument& a : args) if (!a.quoted) read.insert(a.text);
-}
-
 std::unique_ptr<Result> execute_covariance(Segment& seg, const pg_query& q, const CancelToken* cancel) {
-  const double t0 = now_ms();
-  use_device(seg.device);
+  SumTablePass pass(seg, q, kWho, cancel);
   const CovarPlan P = covar_plan(seg, q);
-  const double t_plan = now_ms();
-  SideBaseQuery B;
-  side_base_query(q, B);
-  SidePass S = side_pass_begin(seg, q, B, P.groups, kWho, cancel);
-  const int32_t n_rows = S.n_rows;
-  const int64_t M = S.M, n_words = S.n_words;
-  const int cus = S.cus;
-  hipStream_t stream = S.stream;
-  // ---- the accumulation pass -------------------------------------------------------------------------------------------------------------------
   PgCovarArgs A;
-  memset(&A, 0, sizeof(A));
-  int64_t doc_bits = side_scan_fill(A.scan, seg, S, P.groups);
+  int64_t doc_bits = pass.begin(P.table, A);
   A.n_cols = (int32_t)P.cols.size();
   A.n_pairs = (int32_t)P.pairs.size();
-  A.slots = P.slots;
-  A.n_groups = P.groups.G;
-  A.n_slots = P.n_slots;
   for (size_t i = 0; i < P.cols.size(); i++) {
     const CovarColumn& cc = P.cols[i];
     PgCovarCol& C = A.cols[i];
@@ -187,28 +149,13 @@ std::unique_ptr<Result> execute_covariance(Segment& seg, const pg_query& q, cons
     C.first_slot = cp.first_slot;
     C.qp = pg_covar_qp(cp.exp);
   }
-  DeviceBuffer table((size_t)P.n_slots * 8);
-  A.table = table.as<int64_t>();
-  // PG_QUERY_FLAG_PROFILE: the pass (initialisation, accumulation, gather and its copy) between two events of its own
-  ProfileTimer timer(q.flags);
-  timer.start(stream);
-  PG_HIP(hipMemsetAsync(table.ptr, 0, (size_t)P.n_slots * 8, stream));
-  if (M > 0 && n_words > 0) {
-    // the LDS tier's workgroups are persistent: one per CU for a full table, up to four (32 waves) where the tables are small enough to
-    // share the CU's LDS — the plain loop keeps one load per wave in flight, so the waves per CU decide how much of the bandwidth it
-    // reaches (measured on the FIRSTWITHTIME / LASTWITHTIME pass)
-    const int64_t lds_wgs = std::max<int64_t>(1, std::min<int64_t>(4, (int64_t)PG_COVAR_LDS_SLOTS / (int64_t)std::max<uint64_t>(1, P.n_slots)));
-    pg_covar_launch_pass(&A, P.tier, side_pass_grid(P.tier, cus, n_words, lds_wgs), stream);
-    PG_HIP(hipGetLastError());
-  }
-  std::vector<int64_t> got((size_t)n_rows * (size_t)P.slots);
-  side_gather_rows(S, got, cancel, [&](const uint32_t* rows, int64_t* out) {
-    pg_expr_launch_gather(table.as<int64_t>(), rows, n_rows, P.slots, P.groups.G, out, side_flat_grid(cus, (int64_t)got.size()), stream);
-  });
-  const float pass_ms = timer.stop_ms();
-  if (q.n_group_by == 0 && got[0] != M)
-    fail(PG_ERR_INTERNAL, "covariance: %lld docs counted for %lld matching docs", (long long)got[0], (long long)M);
+  // the LDS tier's workgroups are persistent: one per CU for a full table, up to four (32 waves) where the tables are small enough to
+  // share the CU's LDS — the plain loop keeps one load per wave in flight, so the waves per CU decide how much of the bandwidth it
+  // reaches (measured on the FIRSTWITHTIME / LASTWITHTIME pass)
+  const int64_t lds_wgs = std::max<int64_t>(1, std::min<int64_t>(4, (int64_t)PG_COVAR_LDS_SLOTS / (int64_t)std::max<uint64_t>(1, P.table.n_slots)));
+  pass.accumulate([&](int tier, int grid, hipStream_t stream) { pg_covar_launch_pass(&A, tier, grid, stream); }, lds_wgs, 0);
   // ---- the tuples: (sumX, sumY, sumXY, count), each of the three doubles rounded once; (0.0, 0.0, 0.0, 0) over no doc ------------------------------
+  const int32_t n_rows = pass.n_rows();
   std::vector<AggResult> out((size_t)q.n_aggregations);
   for (const CovarPair& cp : P.pairs) {
     const CovarColumn& X = P.cols[(size_t)cp.x];
@@ -218,22 +165,17 @@ std::unique_ptr<Result> execute_covariance(Segment& seg, const pg_query& q, cons
     r.l[0].resize((size_t)n_rows);
     for (int k = 0; k < 3; k++) r.d[k].resize((size_t)n_rows);
     for (int32_t i = 0; i < n_rows; i++) {
-      const int64_t* row = &got[(size_t)i * (size_t)P.slots];
-      const int64_t n = row[0];
-      if (n < 0 || n > M) fail(PG_ERR_INTERNAL, "covariance: %lld docs counted in a group of %lld matching docs", (long long)n, (long long)M);
-      const pg_covar_tuple t = pg_covar_tuple_of(n, row + X.first_slot, X.is_int, X.exp, row + Y.first_slot, Y.is_int, Y.exp, row + cp.first_slot, cp.exp);
+      const int64_t* row = pass.row(i);
+      const pg_covar_tuple t = pg_covar_tuple_of(row[0], row + X.first_slot, X.is_int, X.exp, row + Y.first_slot, Y.is_int, Y.exp, row + cp.first_slot, cp.exp);
       r.l[0][(size_t)i] = t.count;
       r.d[0][(size_t)i] = t.sum_x;
       r.d[1][(size_t)i] = t.sum_y;
       r.d[2][(size_t)i] = t.sum_xy;
     }
-    for (size_t k = 0; k + 1 < cp.aggs.size(); k++) out[(size_t)cp.aggs[k]] = r;
-    out[(size_t)cp.aggs.back()] = std::move(r);
+    side_share_result(out, cp.aggs, std::move(r));
   }
-  const bool wide = P.tier == TIER_REG && ((int)P.cols.size() > PG_COVAR_REG_COLS || (int)P.pairs.size() > PG_COVAR_REG_PAIRS);
-  std::unique_ptr<Result> res = side_pass_finish(seg, q, B, S, out, {wide ? kWideRegKernel : kTierKernel[P.tier], side_pass_bytes(seg, S, 1, doc_bits), P.n_columns_read, pass_ms, t0, t_plan});
-  res->covariance = true;
-  return res;
+  const bool wide = P.table.tier == TIER_REG && ((int)P.cols.size() > PG_COVAR_REG_COLS || (int)P.pairs.size() > PG_COVAR_REG_PAIRS);
+  return pass.finish(out, wide ? kWideRegKernel : kTierKernel[P.table.tier], doc_bits, MERGED_COVARIANCE);
 }
 
 }  // namespace pg

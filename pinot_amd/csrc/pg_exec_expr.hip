@@ -1,16 +1,20 @@
 // Queries with an aggregation over an arithmetic expression — SUM / MIN / MAX / AVG / MINMAXRANGE whose pg_agg_spec.column is an expression
 // text (pg_expr.h: add / sub / mult / div over single-value numeric columns and literals): a side pass joined to the ordinary plan by group
-// key, in the frame of pg_exec_sidepass.hip (which runs step 1 and the filter, maps the admitted groups to rows and joins the result, step 4).
-//   1. The ordinary part — the query without its expression aggregations (COUNT(*) if nothing else remains) — runs through execute_query
-//      unchanged, never on a star-tree: it decides the groups, the numGroupsLimit admission and the other aggregations' results (a PERCENTILE
-//      among them takes its own side pass from there).  An ORDER BY that names an expression aggregation leaves the segment untrimmed.
-//   2. A bounds pass per (segment, expression text) over ALL docs (pg_expr_bounds): the largest finite |value| fixes the scale of the exact
-//      fixed-point SUM (pg_fixed_point.h, L = 4 limbs, q = E - 127 with every |value| < 2^E); an expression that yields a NaN / Inf anywhere in
-//      the segment is refused by pg_query_exec.  Cached in the segment (at most 256 texts, filled under its lock; the pass itself runs outside it).
-//   3. One accumulation pass for ALL expressions of the query over the filter's match words into a table [G][slots] of int64: pg_expr_reg without GROUP BY, pg_expr_lds up to
-//      Knobs::expr_lds_max_slots slots, pg_expr_hbm up to Knobs::expr_hbm_max_bytes; beyond that the query is refused.
-//   4. The rows of the admitted groups are gathered on the device and joined to the ordinary part on the host.
-// The kernels are those of pg_kernels_expr.hip.
+// key.  The pass is the sum-table pass of pg_exec_sidepass.hip (SumTablePass: the ordinary part, the filter's match words, the table, the
+// timed accumulation and gather, the doc-count check, the join and the statistics); this file holds what is the path's own:
+//   the bounds   a pass per (segment, expression text) over ALL docs (pg_expr_bounds): the largest finite |value| fixes the scale of the
+//                exact fixed-point SUM (pg_fixed_point.h, L = 4 limbs, q = E - 127 with every |value| < 2^E); an expression that yields a
+//                NaN / Inf anywhere in the segment is refused by pg_query_exec.  Cached in the segment (at most 256 texts, filled under its
+//                lock; the pass itself runs outside it).
+//   the plan     one table [G][slots] of int64 for ALL expressions of the query: per expression the SUM's limbs, the MIN, the MAX, as far
+//                as an aggregation asks for them, and one doc count for AVG.  pg_expr_reg without GROUP BY, pg_expr_lds up to
+//                Knobs::expr_lds_max_slots slots, pg_expr_hbm up to Knobs::expr_hbm_max_bytes; beyond that the query is refused.
+//   the kernels' arguments (PgExprArgs; the kernels are those of pg_kernels_expr.hip) and the table's initial values: the MIN / MAX
+//                identities (pg_expr_init)
+//   the results  SUM, MIN, MAX, AVG's pair and MINMAXRANGE's pair from the gathered rows; the reference's defaults over no doc fall out of
+//                the identities.
+// The ordinary part is the query without its expression aggregations (a PERCENTILE among the others takes its own side pass from there);
+// an ORDER BY that names an expression aggregation leaves the segment untrimmed.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -26,7 +30,6 @@
 void pg_expr_launch_bounds(const PgExprArgs* args, unsigned long long* out, int grid, hipStream_t stream);
 void pg_expr_launch_init(const PgExprArgs* args, int grid, hipStream_t stream);
 void pg_expr_launch_pass(const PgExprArgs* args, int tier, int grid, hipStream_t stream);
-void pg_expr_launch_gather(const int64_t* table, const uint32_t* rows, int32_t n_rows, int32_t slots, uint64_t n_groups, int64_t* out, int grid, hipStream_t stream);
 
 namespace pg {
 namespace {
@@ -47,13 +50,10 @@ struct ExprItem {
   Segment::ExprBounds bounds;
 };
 struct ExprPlan {
-  SideGroups groups;
+  SideTable table;
   std::vector<ExprItem> exprs;
   std::vector<Column*> srcs;    // the distinct operand columns of all expressions
-  int32_t slots = 0, count_slot = -1;
-  uint64_t n_slots = 0;
-  int tier = TIER_REG;
-  int n_columns_read = 0;       // distinct columns the query projects (ProjectOperator#getNumColumnsProjected)
+  int32_t count_slot = -1;
 };
 
 void fill_src(PgValueSrc& S, const Column& c) { expr_fill_src(S, c); }
@@ -109,9 +109,7 @@ ExprPlan expr_plan(Segment& seg, const pg_query& q, bool compute_bounds) {
   for (int a = 0; a < q.n_aggregations; a++) {
     const pg_agg_spec& s = q.aggregations[a];
     if (!is_expression_agg(s)) {
-      if (is_with_time_function(s.function)) with_time_columns_read(s, read);   // its column is an argument list
-      else if (is_covariance_function(s.function)) covariance_columns_read(s, read);
-      else if (s.column && strcmp(s.column, "*") != 0) read.insert(s.column);
+      side_columns_read(s, read);
       continue;
     }
     int32_t acc = 0;
@@ -167,21 +165,17 @@ ExprPlan expr_plan(Segment& seg, const pg_query& q, bool compute_bounds) {
     P.exprs[k].acc |= acc;
     P.exprs[k].aggs.push_back(a);
   }
-  P.groups = side_groups(seg, q, kSubject, kWho, read);
-  P.n_columns_read = (int)read.size();
   // the group's row: per expression the SUM's limbs, the MIN, the MAX, as far as an aggregation asks for them; one doc count for AVG
+  int32_t slots = 0;
   for (ExprItem& item : P.exprs) {
-    if (item.acc & PG_EXPR_ACC_SUM) { item.sum_slot = P.slots; P.slots += PG_EXPR_SUM_LIMBS; }
-    if (item.acc & PG_EXPR_ACC_MIN) item.min_slot = P.slots++;
-    if (item.acc & PG_EXPR_ACC_MAX) item.max_slot = P.slots++;
+    if (item.acc & PG_EXPR_ACC_SUM) { item.sum_slot = slots; slots += PG_EXPR_SUM_LIMBS; }
+    if (item.acc & PG_EXPR_ACC_MIN) item.min_slot = slots++;
+    if (item.acc & PG_EXPR_ACC_MAX) item.max_slot = slots++;
   }
-  if (need_count) P.count_slot = P.slots++;
-  P.n_slots = P.groups.G * (uint64_t)P.slots;   // < 2^37
+  if (need_count) P.count_slot = slots++;
   const Knobs& K = knobs();
-  P.tier = side_tier(q.n_group_by, P.n_slots, (uint64_t)std::min<int64_t>(K.expr_lds_max_slots, PG_EXPR_LDS_SLOTS), P.n_slots * 8, K.expr_hbm_max_bytes);
-  if (P.tier == TIER_REFUSED)
-    fail(PG_ERR_UNSUPPORTED, "aggregations over expressions: %llu groups x %d slots need a table of %llu bytes, more than PG_EXPR_HBM_MAX_BYTES (%lld)",
-         (unsigned long long)P.groups.G, P.slots, (unsigned long long)(P.n_slots * 8), (long long)K.expr_hbm_max_bytes);
+  P.table = side_table_plan(seg, q, kSubject, kWho, read, slots, (uint64_t)std::min<int64_t>(K.expr_lds_max_slots, PG_EXPR_LDS_SLOTS), 8, K.expr_hbm_max_bytes,
+                            "aggregations over expressions", "PG_EXPR_HBM_MAX_BYTES");
   return P;
 }
 
@@ -198,27 +192,13 @@ bool is_expression_agg(const pg_agg_spec& s) { return expr_is_expression(s.colum
 void expression_plan_check(Segment& seg, const pg_query& q) { (void)expr_plan(seg, q, false); }
 
 std::unique_ptr<Result> execute_expression(Segment& seg, const pg_query& q, const CancelToken* cancel) {
-  const double t0 = now_ms();
-  use_device(seg.device);
+  SumTablePass pass(seg, q, kWho, cancel);
   const ExprPlan P = expr_plan(seg, q, true);
-  const double t_plan = now_ms();
-  SideBaseQuery B;
-  side_base_query(q, B);
-  SidePass S = side_pass_begin(seg, q, B, P.groups, kWho, cancel);
-  const int32_t n_rows = S.n_rows;
-  const int64_t M = S.M, n_words = S.n_words;
-  const int cus = S.cus;
-  hipStream_t stream = S.stream;
-  // ---- the accumulation pass -------------------------------------------------------------------------------------------------------------------
   PgExprArgs A;
-  memset(&A, 0, sizeof(A));
-  int64_t doc_bits = side_scan_fill(A.scan, seg, S, P.groups);
+  int64_t doc_bits = pass.begin(P.table, A);
   A.n_srcs = (int32_t)P.srcs.size();
   A.n_exprs = (int32_t)P.exprs.size();
-  A.slots = P.slots;
   A.count_slot = P.count_slot;
-  A.n_groups = P.groups.G;
-  A.n_slots = P.n_slots;
   for (size_t i = 0; i < P.srcs.size(); i++) {
     fill_src(A.srcs[i], *P.srcs[i]);
     doc_bits += value_src_bits(*P.srcs[i]);
@@ -243,33 +223,20 @@ std::unique_ptr<Result> execute_expression(Segment& seg, const pg_query& q, cons
     if (item.min_slot >= 0) A.ident[item.min_slot] = INT64_MAX;
     if (item.max_slot >= 0) A.ident[item.max_slot] = INT64_MIN;
   }
-  DeviceBuffer table((size_t)P.n_slots * 8);
-  A.table = table.as<int64_t>();
-  // PG_QUERY_FLAG_PROFILE: the pass (initialisation, accumulation, gather and its copy) between two events of its own
-  ProfileTimer timer(q.flags);
-  timer.start(stream);
-  pg_expr_launch_init(&A, side_flat_grid(cus, (int64_t)P.n_slots), stream);
-  PG_HIP(hipGetLastError());
-  if (M > 0 && n_words > 0) {
-    pg_expr_launch_pass(&A, P.tier, side_pass_grid(P.tier, cus, n_words), stream);
-    PG_HIP(hipGetLastError());
-  }
-  std::vector<int64_t> got((size_t)n_rows * (size_t)P.slots);
-  side_gather_rows(S, got, cancel, [&](const uint32_t* rows, int64_t* out) {
-    pg_expr_launch_gather(table.as<int64_t>(), rows, n_rows, P.slots, P.groups.G, out, side_flat_grid(cus, (int64_t)got.size()), stream);
-  });
-  const float pass_ms = timer.stop_ms();
+  pass.accumulate([&](int tier, int grid, hipStream_t stream) { pg_expr_launch_pass(&A, tier, grid, stream); }, 1, P.count_slot,
+                  [&](int grid, hipStream_t stream) { pg_expr_launch_init(&A, grid, stream); });
   // ---- the expression aggregations' results: the reference's defaults over no doc fall out of the identities -----------------------------------
+  const int32_t n_rows = pass.n_rows();
   std::vector<AggResult> out((size_t)q.n_aggregations);
   for (const ExprItem& item : P.exprs) {
     const int fx_q = item.bounds.exp - (32 * PG_EXPR_SUM_LIMBS - 1);
-    auto sum_of = [&](int32_t i) { return pg_limbs_to_double(&got[(size_t)i * (size_t)P.slots + (size_t)item.sum_slot], PG_EXPR_SUM_LIMBS, fx_q); };
+    auto sum_of = [&](int32_t i) { return pg_limbs_to_double(pass.row(i) + item.sum_slot, PG_EXPR_SUM_LIMBS, fx_q); };
     auto min_of = [&](int32_t i) {
-      const int64_t k = got[(size_t)i * (size_t)P.slots + (size_t)item.min_slot];
+      const int64_t k = pass.row(i)[item.min_slot];
       return k == INT64_MAX ? std::numeric_limits<double>::infinity() : order_key_to_double(k);   // MinAggregationFunction's default
     };
     auto max_of = [&](int32_t i) {
-      const int64_t k = got[(size_t)i * (size_t)P.slots + (size_t)item.max_slot];
+      const int64_t k = pass.row(i)[item.max_slot];
       return k == INT64_MIN ? -std::numeric_limits<double>::infinity() : order_key_to_double(k);
     };
     for (int a : item.aggs) {
@@ -294,7 +261,7 @@ std::unique_ptr<Result> execute_expression(Segment& seg, const pg_query& q, cons
           r.kind = PG_RESULT_AVG_PAIR;
           r.d[0].resize((size_t)n_rows);
           r.l[0].resize((size_t)n_rows);
-          for (int32_t i = 0; i < n_rows; i++) { r.d[0][(size_t)i] = sum_of(i); r.l[0][(size_t)i] = got[(size_t)i * (size_t)P.slots + (size_t)P.count_slot]; }
+          for (int32_t i = 0; i < n_rows; i++) { r.d[0][(size_t)i] = sum_of(i); r.l[0][(size_t)i] = pass.row(i)[P.count_slot]; }
           break;
         default:   // PG_AGG_MINMAXRANGE
           r.kind = PG_RESULT_MINMAX_PAIR;
@@ -305,11 +272,7 @@ std::unique_ptr<Result> execute_expression(Segment& seg, const pg_query& q, cons
       }
     }
   }
-  if (q.n_group_by == 0 && P.count_slot >= 0 && got[(size_t)P.count_slot] != M)
-    fail(PG_ERR_INTERNAL, "expression: %lld docs counted for %lld matching docs", (long long)got[(size_t)P.count_slot], (long long)M);
-  std::unique_ptr<Result> res = side_pass_finish(seg, q, B, S, out, {kTierKernel[P.tier], side_pass_bytes(seg, S, 1, doc_bits), P.n_columns_read, pass_ms, t0, t_plan});
-  res->expression = true;
-  return res;
+  return pass.finish(out, kTierKernel[P.table.tier], doc_bits, MERGED_EXPRESSION);
 }
 
 }  // namespace pg

@@ -261,7 +261,7 @@ std::unique_ptr<Result> execute_percentile(Segment& seg, const pg_query& q, cons
   }
   const float pass_ms = timer.stop_ms();
   std::unique_ptr<Result> res = side_pass_finish(seg, q, B, S, out, {kernel, pass_bytes, P.n_columns_read, pass_ms, t0, t_plan});
-  res->percentile = true;
+  res->merged_elsewhere |= MERGED_PERCENTILE;
   res->stats.percentile_passes = passes;
   return res;
 }

@@ -1,20 +1,31 @@
 // The frame of the side passes: aggregations answered by a pass of their own and joined to the ordinary plan by group key (exact PERCENTILE:
 // pg_exec_percentile.hip; aggregations over an expression: pg_exec_expr.hip; the variance family: pg_exec_var.hip; COVAR_POP / COVAR_SAMP: pg_exec_covar.hip; SKEWNESS / KURTOSIS: pg_exec_moment.hip; FIRSTWITHTIME / LASTWITHTIME: pg_exec_withtime.hip).
 // The paths are the entries of kSidePaths below, in nesting order; side_path_of, side_check and execute_query (pg_nullaware.cpp) follow that list.  A path plans its aggregations and its group-by
-// columns (side_groups, side_argument_column), splits the query (side_base_query), and then
+// columns (side_groups, side_argument_column; side_columns_read for what the other paths' aggregations read), splits the query
+// (side_base_query), and then
 //   1. side_pass_begin runs the ordinary part through execute_query — it decides the groups, the numGroupsLimit admission and the other
 //      aggregations' results —, runs the filter again for its match words (the filter kernels and cached filter plan of the DISTINCT path; none
 //      without a filter and without an upsert snapshot) and maps the admitted groups to rows of the path's table;
 //   2. the path runs its own kernels over the match words (side_scan_fill: the head of their arguments) between a ProfileTimer's events;
 //   3. side_pass_finish joins the columns and writes the statistics.
-// The paths with a table [G][slots] of 64-bit slots share more: where the table lives (side_tier), the pass's grid (side_pass_grid), the gather of the
-// admitted rows (side_gather_rows) and the pass's bytes (side_pass_bytes, value_src_bits).
+// The paths with a table [G][slots] of 64-bit slots share more: the end of their plans (side_table_plan: the groups, where the table lives
+// — side_tier — and the refusal of a table over the path's knob), the pass's grid (side_pass_grid), the gather of the admitted rows
+// (side_gather_rows) and the pass's bytes (side_pass_bytes, value_src_bits).
+// The four of them whose slots are int64 sums (expressions, the variance family, covariance, SKEWNESS / KURTOSIS) share the whole sequence:
+// SumTablePass, at the end of this file, runs steps 1 to 3 with the table's allocation and initialisation, the launch, the gather through
+// pg_expr_gather and the doc-count checks.  Such a path supplies its plan, its kernel arguments, a launch callable, the LDS tier's
+// workgroups per CU, the kernel name to report, an initialiser where zero is not the identity, and the reading of the gathered rows into its
+// tuples.  PERCENTILE (counting passes and a sort tier) and FIRSTWITHTIME / LASTWITHTIME (two planes, up to two ordered passes, a gather
+// of its own) call the pieces directly.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <unordered_map>
 
 #include "pg_internal.hpp"
+#include "pg_expr.h"
+
+void pg_expr_launch_gather(const int64_t* table, const uint32_t* rows, int32_t n_rows, int32_t slots, uint64_t n_groups, int64_t* out, int grid, hipStream_t stream);
 
 namespace pg {
 
@@ -126,7 +137,7 @@ const SidePath kSidePaths[] = {
     {is_expression_agg, expression_plan_check, execute_expression, kSideBaseClears},
     // inside the expression pass, outside the variance's and the PERCENTILE's: its statistics count its two argument columns
     {is_with_time_agg, with_time_plan_check, execute_with_time, kSideBaseClears},
-    // inside the FIRSTWITHTIME / LASTWITHTIME pass (which counts its argument columns, covariance_columns_read), outside the variance's
+    // inside the FIRSTWITHTIME / LASTWITHTIME pass (which counts its argument columns, side_columns_read), outside the variance's
     {is_covariance_agg, covariance_plan_check, execute_covariance, kSideBaseClears},
     // inside the covariance pass, outside the variance's: SKEWNESS / KURTOSIS next to VAR_POP and PERCENTILE leave those to the passes below
     {is_moment_agg, moment_plan_check, execute_moment, kSideBaseClears},
@@ -203,6 +214,42 @@ Column* side_argument_column(Segment& seg, const char* name, const char* fn, con
   const bool raw_ok = !c->has_dictionary && (c->col_kind == PG_COL_RAW32 || c->col_kind == PG_COL_RAW64);
   if (!dict_ok && !raw_ok) fail(PG_ERR_UNSUPPORTED, "%s: %s %s (layout %d, %d bits)", fn, layout_role, c->name.c_str(), c->col_kind, c->bits);
   return c;
+}
+
+Column* side_value_column(Segment& seg, const char* name, const char* fn, bool null_handling) {
+  Column* c = side_argument_column(seg, name, fn, "column", "argument column", "", null_handling);
+  // the registration pass (pg_segment.cpp) knows every FLOAT / DOUBLE column's non-finite values
+  if ((c->val_type == PG_V_F32 || c->val_type == PG_V_F64) && c->has_nonfinite)
+    fail(PG_ERR_UNSUPPORTED, "%s over %s, which holds a NaN or an infinity: the Java plan answers such a query", fn, c->name.c_str());
+  return c;
+}
+
+void side_columns_read(const pg_agg_spec& s, std::set<std::string>& read) {
+  if (!s.column) return;
+  const bool with_time = is_with_time_agg(s);
+  if (!with_time && !is_covariance_agg(s)) {
+    if (strcmp(s.column, "*") != 0) read.insert(s.column);
+    return;
+  }
+  std::vector<ExprArgument> args;   // x, t, 'TYPE' or x, y: the first two are columns
+  std::string error;
+  if (expr_split_arguments(s.column, args, error) != PG_OK || args.size() != (with_time ? 3u : 2u)) return;
+  for (int k = 0; k < 2; k++) if (!args[(size_t)k].quoted) read.insert(args[(size_t)k].text);
+}
+
+SideTable side_table_plan(Segment& seg, const pg_query& q, const char* subject, const char* who, std::set<std::string>& read, int32_t slots, uint64_t lds_max_slots,
+                          int bytes_per_slot, int64_t hbm_max_bytes, const char* noun, const char* knob) {
+  SideTable T;
+  T.groups = side_groups(seg, q, subject, who, read);
+  T.n_columns_read = (int)read.size();
+  T.slots = slots;
+  T.n_slots = T.groups.G * (uint64_t)slots;   // G <= 2^32 and a path's row has fewer than 2^7 slots
+  const uint64_t bytes = T.n_slots * (uint64_t)bytes_per_slot;
+  T.tier = side_tier(q.n_group_by, T.n_slots, lds_max_slots, bytes, hbm_max_bytes);
+  if (T.tier == TIER_REFUSED)
+    fail(PG_ERR_UNSUPPORTED, "%s: %llu groups x %d slots need a table of %llu bytes, more than %s (%lld)", noun, (unsigned long long)T.groups.G, slots,
+         (unsigned long long)bytes, knob, (long long)hbm_max_bytes);
+  return T;
 }
 
 const char* agg_function_text(int32_t fn) {
@@ -342,6 +389,60 @@ std::unique_ptr<Result> side_pass_finish(Segment& seg, const pg_query& q, const 
   st.host_ms_plan += (float)(P.t_plan - P.t0);
   st.host_ms_total = (float)(now_ms() - P.t0);
   return res;
+}
+
+// ---- the pass of the sum-table paths ---------------------------------------------------------------------------------------------------------
+SumTablePass::SumTablePass(Segment& seg, const pg_query& q, const char* who, const CancelToken* cancel) : seg_(seg), q_(q), who_(who), cancel_(cancel), t0_(now_ms()) {
+  use_device(seg.device);
+}
+
+void SumTablePass::begin_table(const SideTable& T) {
+  t_plan_ = now_ms();
+  T_ = &T;
+  side_base_query(q_, B_);
+  S_ = side_pass_begin(seg_, q_, B_, T.groups, who_, cancel_);
+  table_.alloc((size_t)T.n_slots * 8);
+}
+
+void SumTablePass::accumulate(const Launch& launch, int64_t lds_wgs_per_cu, int32_t count_slot, const Init& init) {
+  const SideTable& T = *T_;
+  hipStream_t stream = S_.stream;
+  // PG_QUERY_FLAG_PROFILE: the pass (initialisation, accumulation, gather and its copy) between two events of its own
+  ProfileTimer timer(q_.flags);
+  timer.start(stream);
+  if (init) {
+    init(side_flat_grid(S_.cus, (int64_t)T.n_slots), stream);
+    PG_HIP(hipGetLastError());
+  } else {
+    PG_HIP(hipMemsetAsync(table_.ptr, 0, (size_t)T.n_slots * 8, stream));
+  }
+  if (S_.M > 0 && S_.n_words > 0) {
+    launch(T.tier, side_pass_grid(T.tier, S_.cus, S_.n_words, lds_wgs_per_cu), stream);
+    PG_HIP(hipGetLastError());
+  }
+  got_.assign((size_t)S_.n_rows * (size_t)T.slots, 0);
+  side_gather_rows(S_, got_, cancel_, [&](const uint32_t* rows, int64_t* out) {
+    pg_expr_launch_gather(table_.as<int64_t>(), rows, S_.n_rows, T.slots, T.groups.G, out, side_flat_grid(S_.cus, (int64_t)got_.size()), stream);
+  });
+  pass_ms_ = timer.stop_ms();
+  if (count_slot < 0) return;
+  if (q_.n_group_by == 0 && row(0)[count_slot] != S_.M)
+    fail(PG_ERR_INTERNAL, "%s: %lld docs counted for %lld matching docs", who_, (long long)row(0)[count_slot], (long long)S_.M);
+  for (int32_t i = 0; i < S_.n_rows; i++) {
+    const int64_t n = row(i)[count_slot];
+    if (n < 0 || n > S_.M) fail(PG_ERR_INTERNAL, "%s: %lld docs counted in a group of %lld matching docs", who_, (long long)n, (long long)S_.M);
+  }
+}
+
+std::unique_ptr<Result> SumTablePass::finish(std::vector<AggResult>& out, const char* kernel, int64_t doc_bits, uint32_t merged) {
+  std::unique_ptr<Result> res = side_pass_finish(seg_, q_, B_, S_, out, {kernel, side_pass_bytes(seg_, S_, 1, doc_bits), T_->n_columns_read, pass_ms_, t0_, t_plan_});
+  res->merged_elsewhere |= merged;
+  return res;
+}
+
+void side_share_result(std::vector<AggResult>& out, const std::vector<int>& aggs, AggResult&& r) {
+  for (size_t k = 0; k + 1 < aggs.size(); k++) out[(size_t)aggs[k]] = r;
+  out[(size_t)aggs.back()] = std::move(r);
 }
 
 }  // namespace pg

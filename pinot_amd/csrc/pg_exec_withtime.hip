@@ -83,14 +83,11 @@ struct WtAgg {
   bool first = false;
 };
 struct WtPlan {
-  SideGroups groups;
+  SideTable table;              // one slot per distinct (time column, direction)
   std::vector<WtSlot> slots;
   std::vector<WtAgg> aggs;
   int doc_bits = 1;
   bool any_wide = false;
-  uint64_t n_slots = 0;
-  int tier = TIER_REG;
-  int n_columns_read = 0;       // distinct columns the query projects (ProjectOperator#getNumColumnsProjected)
 };
 
 int64_t dict_entry(const Column& c, int32_t id) {   // an INT / LONG dictionary's value (big-endian on the host)
@@ -125,8 +122,7 @@ WtPlan wt_plan(Segment& seg, const pg_query& q) {
   for (int a = 0; a < q.n_aggregations; a++) {
     const pg_agg_spec& s = q.aggregations[a];
     if (!is_with_time_agg(s)) {
-      if (is_covariance_function(s.function)) covariance_columns_read(s, read);   // its column is an argument list
-      else if (s.column && strcmp(s.column, "*") != 0) read.insert(s.column);
+      side_columns_read(s, read);
       continue;
     }
     const char* fn = agg_function_text(s.function);
@@ -161,15 +157,8 @@ WtPlan wt_plan(Segment& seg, const pg_query& q) {
     g.slot = (int)k;
     P.aggs.push_back(g);
   }
-  P.groups = side_groups(seg, q, kSubject, kWho, read);
-  P.n_columns_read = (int)read.size();
-  P.n_slots = P.groups.G * (uint64_t)P.slots.size();   // < 2^35
-  const uint64_t bytes = P.n_slots * 8 * (P.any_wide ? 2 : 1);
-  const Knobs& K = knobs();
-  P.tier = side_tier(q.n_group_by, P.n_slots, PG_WT_LDS_SLOTS, bytes, K.wt_hbm_max_bytes);
-  if (P.tier == TIER_REFUSED)
-    fail(PG_ERR_UNSUPPORTED, "FIRSTWITHTIME / LASTWITHTIME: %llu groups x %d slots need a table of %llu bytes, more than PG_WT_HBM_MAX_BYTES (%lld)",
-         (unsigned long long)P.groups.G, (int)P.slots.size(), (unsigned long long)bytes, (long long)K.wt_hbm_max_bytes);
+  // the wide mode keeps a doc plane next to the keys: twice the bytes
+  P.table = side_table_plan(seg, q, kSubject, kWho, read, (int32_t)P.slots.size(), PG_WT_LDS_SLOTS, P.any_wide ? 16 : 8, knobs().wt_hbm_max_bytes, kSubject, "PG_WT_HBM_MAX_BYTES");
   return P;
 }
 
@@ -216,16 +205,7 @@ int64_t convert_value(int64_t bits, int32_t stored, int32_t declared) {
 
 }  // namespace
 
-bool is_with_time_function(int32_t fn) { return fn == PG_AGG_FIRSTWITHTIME || fn == PG_AGG_LASTWITHTIME; }
-
-void with_time_columns_read(const pg_agg_spec& s, std::set<std::string>& read) {
-  std::vector<ExprArgument> args;
-  std::string error;
-  if (!s.column || expr_split_arguments(s.column, args, error) != PG_OK || args.size() != 3) return;
-  for (int k = 0; k < 2; k++) if (!args[(size_t)k].quoted) read.insert(args[(size_t)k].text);
-}
-
-bool is_with_time_agg(const pg_agg_spec& s) { return is_with_time_function(s.function); }
+bool is_with_time_agg(const pg_agg_spec& s) { return s.function == PG_AGG_FIRSTWITHTIME || s.function == PG_AGG_LASTWITHTIME; }
 void with_time_plan_check(Segment& seg, const pg_query& q) { (void)wt_plan(seg, q); }
 
 std::unique_ptr<Result> execute_with_time(Segment& seg, const pg_query& q, const CancelToken* cancel) {
@@ -235,7 +215,7 @@ std::unique_ptr<Result> execute_with_time(Segment& seg, const pg_query& q, const
   const double t_plan = now_ms();
   SideBaseQuery B;
   side_base_query(q, B);
-  SidePass S = side_pass_begin(seg, q, B, P.groups, kWho, cancel);
+  SidePass S = side_pass_begin(seg, q, B, P.table.groups, kWho, cancel);
   const int32_t n_rows = S.n_rows;
   const int64_t M = S.M, n_words = S.n_words;
   const int cus = S.cus;
@@ -244,11 +224,11 @@ std::unique_ptr<Result> execute_with_time(Segment& seg, const pg_query& q, const
   // ---- the arg-max passes ------------------------------------------------------------------------------------------------------------------------
   PgWtArgs A;
   memset(&A, 0, sizeof(A));
-  int64_t doc_bits = side_scan_fill(A.scan, seg, S, P.groups);
+  int64_t doc_bits = side_scan_fill(A.scan, seg, S, P.table.groups);
   A.slots = n_slots;
   A.doc_bits = P.doc_bits;
-  A.n_groups = P.groups.G;
-  A.n_slots = P.n_slots;
+  A.n_groups = P.table.groups.G;
+  A.n_slots = P.table.n_slots;
   for (int s = 0; s < n_slots; s++) {
     const WtSlot& W = P.slots[(size_t)s];
     expr_fill_src(A.slot[s].time, *W.time);
@@ -259,7 +239,7 @@ std::unique_ptr<Result> execute_with_time(Segment& seg, const pg_query& q, const
     for (int k = 0; k < s; k++) counted = counted || P.slots[(size_t)k].time == W.time;
     if (!counted) doc_bits += value_src_bits(*W.time);
   }
-  const size_t plane_bytes = (size_t)P.n_slots * 8;
+  const size_t plane_bytes = (size_t)P.table.n_slots * 8;
   DeviceBuffer keys(plane_bytes), docs(P.any_wide ? plane_bytes : 8);
   A.keys = keys.as<unsigned long long>();
   A.docs = P.any_wide ? docs.as<unsigned long long>() : nullptr;
@@ -272,11 +252,11 @@ std::unique_ptr<Result> execute_with_time(Segment& seg, const pg_query& q, const
   if (M > 0 && n_words > 0) {
     // the LDS tier's workgroups are persistent: one per CU for a full table, up to four (32 waves) where the tables are small enough to
     // share the CU's LDS — the loop keeps one load per wave in flight, so the waves per CU decide how much of the bandwidth it reaches
-    const int64_t lds_wgs = std::max<int64_t>(1, std::min<int64_t>(4, (int64_t)PG_WT_LDS_SLOTS / (int64_t)std::max<uint64_t>(1, P.n_slots)));
-    const int grid = side_pass_grid(P.tier, cus, n_words, lds_wgs);
+    const int64_t lds_wgs = std::max<int64_t>(1, std::min<int64_t>(4, (int64_t)PG_WT_LDS_SLOTS / (int64_t)std::max<uint64_t>(1, P.table.n_slots)));
+    const int grid = side_pass_grid(P.table.tier, cus, n_words, lds_wgs);
     for (int pass = 0; pass < passes; pass++) {   // the second pass reads the first one's maxima: stream order
       A.pass = pass;
-      pg_wt_launch_pass(&A, P.tier, grid, stream);
+      pg_wt_launch_pass(&A, P.table.tier, grid, stream);
       PG_HIP(hipGetLastError());
     }
   }
@@ -346,8 +326,8 @@ std::unique_ptr<Result> execute_with_time(Segment& seg, const pg_query& q, const
   }
   // the match words and the time and group columns once per pass, the gathered docs, times and values
   const int64_t pass_bytes = side_pass_bytes(seg, S, passes, doc_bits, (int64_t)got.size() * 8);
-  std::unique_ptr<Result> res = side_pass_finish(seg, q, B, S, out, {kTierKernel[P.tier], pass_bytes, P.n_columns_read, pass_ms, t0, t_plan});
-  res->with_time = true;
+  std::unique_ptr<Result> res = side_pass_finish(seg, q, B, S, out, {kTierKernel[P.table.tier], pass_bytes, P.table.n_columns_read, pass_ms, t0, t_plan});
+  res->merged_elsewhere |= MERGED_WITH_TIME;
   return res;
 }
 

@@ -511,6 +511,11 @@ struct ResultColumn {
   const uint8_t* dict = nullptr;    // big-endian dictionary values, dict_width bytes each
   int32_t dict_width = 0;
 };
+// Result::merged_elsewhere, one bit per side path
+enum MergedElsewhere : uint32_t {
+  MERGED_PERCENTILE = 1u << 0, MERGED_EXPRESSION = 1u << 1, MERGED_VARIANCE = 1u << 2, MERGED_FOURTH_MOMENT = 1u << 3, MERGED_COVARIANCE = 1u << 4,
+  MERGED_WITH_TIME = 1u << 5,
+};
 struct Result {
   std::vector<ResultColumn> schema_keys, schema_aggs;
   std::weak_ptr<int> schema_segment;   // the segment whose dictionaries the schema points into (pg_result_data_table_v4 refuses once it is destroyed)
@@ -530,12 +535,11 @@ struct Result {
   bool null_handling = false;   // the query ran with PG_QUERY_FLAG_NULL_HANDLING (its data table carries the columns' null bitmaps)
   bool distinct = false;        // PG_QUERY_FLAG_DISTINCT: the groups are the distinct tuples, no aggregation (never merged in the library)
   bool selection = false;       // PG_QUERY_FLAG_SELECTION: the groups are the selected rows (never merged in the library)
-  bool percentile = false;      // the query carried a PERCENTILE: its lists merge by value on the Java side (never merged in the library)
-  bool expression = false;      // the query carried an aggregation over an expression: the scale of its sums differs per segment (never merged in the library)
-  bool variance = false;        // the query carried a variance aggregation: its tuples merge on the Java side, VarianceTuple#apply (never merged in the library)
-  bool fourth_moment = false;   // the query carried a SKEWNESS / KURTOSIS: its tuples merge on the Java side, PinotFourthMoment#combine (never merged in the library)
-  bool covariance = false;      // the query carried a COVAR_POP / COVAR_SAMP: its tuples merge on the Java side, CovarianceTuple#apply (never merged in the library)
-  bool with_time = false;       // the query carried a FIRSTWITHTIME / LASTWITHTIME: its pairs merge on the Java side with the functions' own merge (never merged in the library)
+  // MERGED_* bits: the side aggregations the query carried.  Their results merge on the Java side, never in the library (pg_api.cpp words
+  // the refusals): a PERCENTILE's lists by value; an aggregation over an expression because the scale of its sums differs per segment; the
+  // variance, SKEWNESS / KURTOSIS and covariance tuples by VarianceTuple#apply, PinotFourthMoment#combine and CovarianceTuple#apply; the
+  // FIRSTWITHTIME / LASTWITHTIME pairs with the functions' own merge
+  uint32_t merged_elsewhere = 0;
   pg_exec_stats stats{};
 };
 struct DocIdSet {
@@ -627,7 +631,72 @@ int64_t side_pass_bytes(const Segment& seg, const SidePass& S, int passes, int64
 // `layout_role` — readable by the kernels: fixed-bit dictIds with a dictionary on the device, or raw values.  `fn` names the function, `role` and
 // `layout_role` the column ("column", "time column", "argument column") and `mv_note` ends the multi-value refusal, as the paths' messages differ.
 Column* side_argument_column(Segment& seg, const char* name, const char* fn, const char* role, const char* layout_role, const char* mv_note, bool null_handling);
+// ... of a column whose values are summed digit by digit (the variance family, covariance, SKEWNESS / KURTOSIS): an argument column the
+// kernels read, without a NaN or an infinity — the sums have no digits for them
+Column* side_value_column(Segment& seg, const char* name, const char* fn, bool null_handling);
+// The columns an aggregation of ANOTHER path reads, added to `read` (a pass counts every column the query projects): a plain column name,
+// or the column arguments of a FIRSTWITHTIME / LASTWITHTIME / COVAR argument list.  COUNT(*) and a malformed list add nothing — the list's
+// own path refuses it.
+void side_columns_read(const pg_agg_spec& s, std::set<std::string>& read);
 const char* agg_function_text(int32_t fn);   // "VAR_POP", "FIRSTWITHTIME", ...: the functions the side paths name in messages
+// The table of a slot-table path as its plan decides it (seg.mu held): the group-by columns (side_groups, which adds them to `read`; `read`
+// then holds every column the query projects), the table's slots and where it lives (side_tier).  A table of more than `hbm_max_bytes`
+// bytes is refused: "<noun>: .. groups x .. slots need a table of .. bytes, more than <knob> (..)".
+struct SideTable {
+  SideGroups groups;
+  int32_t slots = 0;            // of one group's row
+  uint64_t n_slots = 0;         // groups.G * slots
+  int tier = TIER_REG;
+  int n_columns_read = 0;       // distinct columns the query projects (ProjectOperator#getNumColumnsProjected)
+};
+SideTable side_table_plan(Segment& seg, const pg_query& q, const char* subject, const char* who, std::set<std::string>& read, int32_t slots, uint64_t lds_max_slots,
+                          int bytes_per_slot, int64_t hbm_max_bytes, const char* noun, const char* knob);
+// The pass of a path that keeps a table [G][slots] of int64 sums (expressions, the variance family, covariance, SKEWNESS / KURTOSIS), from
+// the query's first clock reading to its result.  A path's execute_* constructs one, plans, and then
+//   begin       runs the ordinary part and the filter (side_pass_begin), allocates the table and fills the head of the kernel arguments;
+//   accumulate  initialises the table, launches the path's kernels over the match words and gathers the admitted groups' rows, all between
+//               a ProfileTimer's events, and checks the doc counts of a path with a count slot;
+//   finish      joins the path's tuples to the ordinary part and writes the statistics (side_pass_finish).
+class SumTablePass {
+ public:
+  SumTablePass(Segment& seg, const pg_query& q, const char* who, const CancelToken* cancel);   // the query's start: before the path plans
+  // `A` zeroed; its scan, slots, n_groups, n_slots and table filled.  Returns the group columns' bits per doc; `T` outlives the pass.
+  template <typename Args>
+  int64_t begin(const SideTable& T, Args& A) {
+    begin_table(T);
+    memset(&A, 0, sizeof(A));
+    A.slots = T.slots;
+    A.n_groups = T.groups.G;
+    A.n_slots = T.n_slots;
+    A.table = table_.as<int64_t>();
+    return side_scan_fill(A.scan, seg_, S_, T.groups);
+  }
+  // launch(tier, grid, stream): the accumulation kernel of the table's tier (not called when no doc matches); `lds_wgs_per_cu`: the LDS
+  // tier's persistent workgroups per CU; `count_slot`: the slot of the group's doc count, -1 without one; init(grid, stream): sets the
+  // table's initial values with one thread per slot — none: the table is zeroed by a memset.
+  using Launch = std::function<void(int, int, hipStream_t)>;
+  using Init = std::function<void(int, hipStream_t)>;
+  void accumulate(const Launch& launch, int64_t lds_wgs_per_cu, int32_t count_slot, const Init& init = nullptr);
+  int32_t n_rows() const { return S_.n_rows; }
+  const int64_t* row(int32_t i) const { return &got_[(size_t)i * (size_t)T_->slots]; }   // the gathered row of admitted group i
+  // `kernel`: the name the statistics report; `doc_bits`: the bits the pass read per doc; `merged`: the path's MERGED_* bit
+  std::unique_ptr<Result> finish(std::vector<AggResult>& out, const char* kernel, int64_t doc_bits, uint32_t merged);
+ private:
+  void begin_table(const SideTable& T);
+  Segment& seg_;
+  const pg_query& q_;
+  const char* who_;
+  const CancelToken* cancel_;
+  double t0_, t_plan_ = 0;
+  const SideTable* T_ = nullptr;
+  SideBaseQuery B_;
+  SidePass S_;
+  DeviceBuffer table_;
+  std::vector<int64_t> got_;
+  float pass_ms_ = 0;
+};
+// one tuple column for all the aggregations that share it (`aggs`: their indexes in `out`, at least one)
+void side_share_result(std::vector<AggResult>& out, const std::vector<int>& aggs, AggResult&& r);
 // ---- the side paths: one entry per family in kSidePaths (pg_exec_sidepass.hip), in nesting order — the only statement of that order.  A new
 // family declares its three functions below and adds its entry; pg_query_supported (side_check) and pg_query_exec (execute_query) follow the table.
 struct SidePath {
@@ -663,23 +732,16 @@ bool is_variance_agg(const pg_agg_spec& s);
 void variance_plan_check(Segment& seg, const pg_query& q);
 std::unique_ptr<Result> execute_variance(Segment& seg, const pg_query& q, const CancelToken* cancel);
 // FIRSTWITHTIME / LASTWITHTIME (pg_exec_withtime.hip): one arg-max pass (two in wide mode, pg_with_time.h) for all of them and a gather of the
-// winners' values.  with_time_columns_read: the argument columns of such an aggregation, whose pg_agg_spec.column is an argument list, added
-// to `read` (an outer side pass counts them; a malformed list adds nothing — the path's own checks refuse it).
-bool is_with_time_function(int32_t fn);
+// winners' values
 bool is_with_time_agg(const pg_agg_spec& s);
 void with_time_plan_check(Segment& seg, const pg_query& q);
 std::unique_ptr<Result> execute_with_time(Segment& seg, const pg_query& q, const CancelToken* cancel);
-void with_time_columns_read(const pg_agg_spec& s, std::set<std::string>& read);
 // COVAR_POP / COVAR_SAMP (pg_exec_covar.hip): one fused accumulation pass of the exact sums of x, y and the rounded products (pg_covar.h)
-// for all of them.  covariance_columns_read: the two argument columns of such an aggregation, whose pg_agg_spec.column is an argument list,
-// added to `read` (an outer side pass counts them; a malformed list adds nothing — the path's own checks refuse it).
-bool is_covariance_function(int32_t fn);
+// for all of them
 bool is_covariance_agg(const pg_agg_spec& s);
 void covariance_plan_check(Segment& seg, const pg_query& q);
 std::unique_ptr<Result> execute_covariance(Segment& seg, const pg_query& q, const CancelToken* cancel);
-void covariance_columns_read(const pg_agg_spec& s, std::set<std::string>& read);
 // SKEWNESS / KURTOSIS (pg_exec_moment.hip): one accumulation pass of the exact power sums up to x^4 (pg_moment4.h) for all of them
-bool is_moment_function(int32_t fn);
 bool is_moment_agg(const pg_agg_spec& s);
 void moment_plan_check(Segment& seg, const pg_query& q);
 std::unique_ptr<Result> execute_moment(Segment& seg, const pg_query& q, const CancelToken* cancel);

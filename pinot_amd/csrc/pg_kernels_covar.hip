@@ -43,11 +43,6 @@ DEVFN pg_d8 covar_load_all(const PgCovarArgs& a, uint32_t doc) {
   return v;
 }
 
-template <typename Ptr>
-DEVFN void covar_add(Ptr slot, int64_t d) {
-  if (d) atomicAdd(reinterpret_cast<unsigned long long*>(slot), (unsigned long long)d);
-}
-
 // the tiers with a table: `row0` is the table's first slot — the workgroup's copy in LDS, or the table in HBM
 template <typename Ptr>
 DEVFN void covar_update(const PgCovarArgs& a, Ptr row0, uint32_t doc) {
@@ -65,10 +60,10 @@ DEVFN void covar_update(const PgCovarArgs& a, Ptr row0, uint32_t doc) {
     v[c & 7] = x;
     Ptr s = row + C.first_slot;
     if (C.is_int) {
-      covar_add(&s[0], (int64_t)x);   // exact: an INT value
+      side_sum_add(&s[0], (int64_t)x);   // exact: an INT value
     } else {
 #pragma unroll
-      for (int l = 0; l < PG_COVAR_DBL_SLOTS; l++) covar_add(&s[l], pg_fx_digit(x, C.q1, l));
+      for (int l = 0; l < PG_COVAR_DBL_SLOTS; l++) side_sum_add(&s[l], pg_fx_digit(x, C.q1, l));
     }
   }
 #pragma unroll 1
@@ -77,21 +72,16 @@ DEVFN void covar_update(const PgCovarArgs& a, Ptr row0, uint32_t doc) {
     const double prod = __dmul_rn(v[P.x & 7], v[P.y & 7]);
     Ptr s = row + P.first_slot;
 #pragma unroll
-    for (int l = 0; l < PG_COVAR_PROD_LIMBS; l++) covar_add(&s[l], pg_covar_prod_digit(prod, P.qp, l));
+    for (int l = 0; l < PG_COVAR_PROD_LIMBS; l++) side_sum_add(&s[l], pg_covar_prod_digit(prod, P.qp, l));
   }
 }
 
-template <bool LDS>
-DEVFN void covar_table_body(const PgCovarArgs& a) {
-  side_table_pass<LDS>(
-      a.scan, a.n_slots, a.table, [](uint32_t) PG_SIDE_INLINE { return (int64_t)0; }, [&](int64_t* tab, uint32_t doc) PG_SIDE_INLINE { covar_update(a, tab, doc); },
-      [&](uint32_t i, int64_t v) PG_SIDE_INLINE {   // only the touched slots
-        if (v) atomicAdd(reinterpret_cast<unsigned long long*>(a.table + i), (unsigned long long)v);
-      });
+extern "C" __global__ void __launch_bounds__(512) pg_covar_lds(const PgCovarArgs a) {
+  side_sum_table_pass<true>(a.scan, a.n_slots, a.table, [&](int64_t* row0, uint32_t doc) PG_SIDE_INLINE { covar_update(a, row0, doc); });
 }
-
-extern "C" __global__ void __launch_bounds__(512) pg_covar_lds(const PgCovarArgs a) { covar_table_body<true>(a); }
-extern "C" __global__ void __launch_bounds__(256) pg_covar_hbm(const PgCovarArgs a) { covar_table_body<false>(a); }
+extern "C" __global__ void __launch_bounds__(256) pg_covar_hbm(const PgCovarArgs a) {
+  side_sum_table_pass<false>(a.scan, a.n_slots, a.table, [&](int64_t* row0, uint32_t doc) PG_SIDE_INLINE { covar_update(a, row0, doc); });
+}
 
 // No GROUP BY: one row.  Every lane keeps the row in registers over all its docs; one reduction across the wavefront and one global atomic
 // per slot at the end.  NC / NP: the columns and pairs the instantiation holds — the accumulators are registers whether a query uses them

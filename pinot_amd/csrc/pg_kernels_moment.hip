@@ -28,17 +28,6 @@
 
 namespace {
 
-// an INT column's value: raw big-endian, or through its INT dictionary
-DEVFN int64_t moment_load_int(const PgValueSrc& S, uint32_t doc) {
-  if (S.col_kind == PG_COL_FIXED_BIT) return (int64_t)reinterpret_cast<const int32_t*>(S.dict)[pg_fixed_bit_id(S.data, S.bits, doc)];   // wave-uniform
-  return (int64_t)(int32_t)__builtin_bswap32(reinterpret_cast<const uint32_t*>(S.data)[doc]);
-}
-
-template <typename Ptr>
-DEVFN void moment_add(Ptr slot, int64_t d) {
-  if (d) atomicAdd(reinterpret_cast<unsigned long long*>(slot), (unsigned long long)d);
-}
-
 constexpr int kSq = PG_VAR_SUM_LIMBS, kCube = kSq + PG_VAR_SQ_LIMBS, kQuad = kCube + PG_M4_CUBE_LIMBS;   // where the double path's sums start
 
 // the tiers with a table: `row0` is the table's first slot — the workgroup's copy in LDS, or the table in HBM
@@ -54,37 +43,32 @@ DEVFN void moment_update(const PgMomentArgs& a, Ptr row0, uint32_t doc) {
     Ptr s = row + C.first_slot;
     if (C.is_int) {
       int64_t d[PG_M4_INT_SLOTS];
-      pg_m4_int_digits(moment_load_int(C.src, doc), d);
+      pg_m4_int_digits(side_load_int(C.src, doc), d);
 #pragma unroll
-      for (int l = 0; l < PG_M4_INT_SLOTS; l++) moment_add(&s[l], d[l]);
+      for (int l = 0; l < PG_M4_INT_SLOTS; l++) side_sum_add(&s[l], d[l]);
     } else {
       const double v = expr_load(C.src, doc);
       const pg_m4_powers P = pg_m4_powers_of(v);
 #pragma unroll
-      for (int l = 0; l < PG_VAR_SUM_LIMBS; l++) moment_add(&s[l], pg_fx_digit(v, C.q1, l));
+      for (int l = 0; l < PG_VAR_SUM_LIMBS; l++) side_sum_add(&s[l], pg_fx_digit(v, C.q1, l));
 #pragma unroll
-      for (int l = 0; l < PG_VAR_SQ_LIMBS; l++) moment_add(&s[kSq + l], (int64_t)pg_sq_digit(v, C.q2, l));
+      for (int l = 0; l < PG_VAR_SQ_LIMBS; l++) side_sum_add(&s[kSq + l], (int64_t)pg_sq_digit(v, C.q2, l));
 #pragma unroll
-      for (int l = 0; l < PG_M4_CUBE_LIMBS; l++) moment_add(&s[kCube + l], pg_m4_cube_digit(P, C.q3, l));
+      for (int l = 0; l < PG_M4_CUBE_LIMBS; l++) side_sum_add(&s[kCube + l], pg_m4_cube_digit(P, C.q3, l));
 #pragma unroll
-      for (int l = 0; l < PG_M4_QUAD_LIMBS; l++) moment_add(&s[kQuad + l], pg_m4_quad_digit(P, C.q4, l));
+      for (int l = 0; l < PG_M4_QUAD_LIMBS; l++) side_sum_add(&s[kQuad + l], pg_m4_quad_digit(P, C.q4, l));
     }
   }
 }
 
-template <bool LDS>
-DEVFN void moment_table_body(const PgMomentArgs& a) {
-  side_table_pass<LDS>(
-      a.scan, a.n_slots, a.table, [](uint32_t) PG_SIDE_INLINE { return (int64_t)0; }, [&](int64_t* tab, uint32_t doc) PG_SIDE_INLINE { moment_update(a, tab, doc); },
-      [&](uint32_t i, int64_t v) PG_SIDE_INLINE {   // only the touched slots
-        if (v) atomicAdd(reinterpret_cast<unsigned long long*>(a.table + i), (unsigned long long)v);
-      });
-}
-
 }  // namespace
 
-extern "C" __global__ void __launch_bounds__(512) pg_moment_lds(const PgMomentArgs a) { moment_table_body<true>(a); }
-extern "C" __global__ void __launch_bounds__(256) pg_moment_hbm(const PgMomentArgs a) { moment_table_body<false>(a); }
+extern "C" __global__ void __launch_bounds__(512) pg_moment_lds(const PgMomentArgs a) {
+  side_sum_table_pass<true>(a.scan, a.n_slots, a.table, [&](int64_t* row0, uint32_t doc) PG_SIDE_INLINE { moment_update(a, row0, doc); });
+}
+extern "C" __global__ void __launch_bounds__(256) pg_moment_hbm(const PgMomentArgs a) {
+  side_sum_table_pass<false>(a.scan, a.n_slots, a.table, [&](int64_t* row0, uint32_t doc) PG_SIDE_INLINE { moment_update(a, row0, doc); });
+}
 
 // No GROUP BY: one row.  Every lane keeps the row in registers over all its docs; one reduction across the wavefront and one global atomic
 // per slot at the end.
@@ -107,7 +91,7 @@ extern "C" __global__ void __launch_bounds__(256) pg_moment_reg(const PgMomentAr
         static_assert(PG_M4_INT_SLOTS == PG_VAR_SUM_LIMBS + PG_VAR_SQ_LIMBS, "the integer path's slots are the double path's digits of x and x^2");
         int64_t d[PG_M4_INT_SLOTS];
         if (C.is_int) {
-          pg_m4_int_digits(moment_load_int(C.src, doc), d);
+          pg_m4_int_digits(side_load_int(C.src, doc), d);
         } else {
           const double v = expr_load(C.src, doc);
           const pg_m4_powers P = pg_m4_powers_of(v);

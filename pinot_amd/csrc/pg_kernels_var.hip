@@ -26,17 +26,6 @@
 
 namespace {
 
-// an INT column's value: raw big-endian, or through its INT dictionary
-DEVFN int64_t var_load_int(const PgValueSrc& S, uint32_t doc) {
-  if (S.col_kind == PG_COL_FIXED_BIT) return (int64_t)reinterpret_cast<const int32_t*>(S.dict)[pg_fixed_bit_id(S.data, S.bits, doc)];   // wave-uniform
-  return (int64_t)(int32_t)__builtin_bswap32(reinterpret_cast<const uint32_t*>(S.data)[doc]);
-}
-
-template <typename Ptr>
-DEVFN void var_add(Ptr slot, int64_t d) {
-  if (d) atomicAdd(reinterpret_cast<unsigned long long*>(slot), (unsigned long long)d);
-}
-
 // the tiers with a table: `row0` is the table's first slot — the workgroup's copy in LDS, or the table in HBM
 template <typename Ptr>
 DEVFN void var_update(const PgVarArgs& a, Ptr row0, uint32_t doc) {
@@ -49,34 +38,29 @@ DEVFN void var_update(const PgVarArgs& a, Ptr row0, uint32_t doc) {
     const PgVarCol& C = a.cols[c];
     Ptr s = row + C.first_slot;
     if (C.is_int) {
-      const int64_t x = var_load_int(C.src, doc);
+      const int64_t x = side_load_int(C.src, doc);
       const int64_t sq = x * x;   // <= 2^62
-      var_add(&s[0], x);
-      var_add(&s[1], pg_long_digit(sq, 0));
-      var_add(&s[2], pg_long_digit(sq, 1));
+      side_sum_add(&s[0], x);
+      side_sum_add(&s[1], pg_long_digit(sq, 0));
+      side_sum_add(&s[2], pg_long_digit(sq, 1));
     } else {
       const double v = expr_load(C.src, doc);
 #pragma unroll
-      for (int l = 0; l < PG_VAR_SUM_LIMBS; l++) var_add(&s[l], pg_fx_digit(v, C.q1, l));
+      for (int l = 0; l < PG_VAR_SUM_LIMBS; l++) side_sum_add(&s[l], pg_fx_digit(v, C.q1, l));
 #pragma unroll
-      for (int l = 0; l < PG_VAR_SQ_LIMBS; l++) var_add(&s[PG_VAR_SUM_LIMBS + l], (int64_t)pg_sq_digit(v, C.q2, l));
+      for (int l = 0; l < PG_VAR_SQ_LIMBS; l++) side_sum_add(&s[PG_VAR_SUM_LIMBS + l], (int64_t)pg_sq_digit(v, C.q2, l));
     }
   }
 }
 
-template <bool LDS>
-DEVFN void var_table_body(const PgVarArgs& a) {
-  side_table_pass<LDS>(
-      a.scan, a.n_slots, a.table, [](uint32_t) PG_SIDE_INLINE { return (int64_t)0; }, [&](int64_t* tab, uint32_t doc) PG_SIDE_INLINE { var_update(a, tab, doc); },
-      [&](uint32_t i, int64_t v) PG_SIDE_INLINE {   // only the touched slots
-        if (v) atomicAdd(reinterpret_cast<unsigned long long*>(a.table + i), (unsigned long long)v);
-      });
-}
-
 }  // namespace
 
-extern "C" __global__ void __launch_bounds__(512) pg_var_lds(const PgVarArgs a) { var_table_body<true>(a); }
-extern "C" __global__ void __launch_bounds__(256) pg_var_hbm(const PgVarArgs a) { var_table_body<false>(a); }
+extern "C" __global__ void __launch_bounds__(512) pg_var_lds(const PgVarArgs a) {
+  side_sum_table_pass<true>(a.scan, a.n_slots, a.table, [&](int64_t* row0, uint32_t doc) PG_SIDE_INLINE { var_update(a, row0, doc); });
+}
+extern "C" __global__ void __launch_bounds__(256) pg_var_hbm(const PgVarArgs a) {
+  side_sum_table_pass<false>(a.scan, a.n_slots, a.table, [&](int64_t* row0, uint32_t doc) PG_SIDE_INLINE { var_update(a, row0, doc); });
+}
 
 // No GROUP BY: one row.  Every lane keeps the row in registers over all its docs; one reduction across the wavefront and one global atomic
 // per slot at the end.
@@ -100,7 +84,7 @@ extern "C" __global__ void __launch_bounds__(256) pg_var_reg(const PgVarArgs a) 
         static_assert(PG_VAR_INT_SLOTS <= PG_VAR_SUM_LIMBS, "the double path's first digits are digits of the sum");
         int64_t d[PG_VAR_INT_SLOTS];
         if (C.is_int) {
-          const int64_t x = var_load_int(C.src, doc);
+          const int64_t x = side_load_int(C.src, doc);
           const int64_t sq = x * x;
           d[0] = x;
           d[1] = pg_long_digit(sq, 0);

@@ -26,9 +26,9 @@ struct SideBaseQuery {
 // PG_OK, or PG_ERR_INVALID_ARGUMENT (an ORDER BY aggregation index out of range) with the reason in `error`.
 int32_t side_base_query(const pg_query& q, bool (*is_side)(const pg_agg_spec&), int32_t clear_flags, SideBaseQuery& out, std::string& error);
 
-// Where a slot-table path (expressions, the variance family, FIRSTWITHTIME / LASTWITHTIME) keeps its table [G][slots] of 64-bit slots: in
-// registers without GROUP BY (one row), per workgroup in LDS up to `lds_max_slots` slots, in HBM up to `hbm_max_bytes` bytes of table;
-// beyond that the query is refused (the caller words the refusal).  The tiers' values index the paths' kernel names.
+// Where a slot-table path (expressions, the variance family, covariance, SKEWNESS / KURTOSIS, FIRSTWITHTIME / LASTWITHTIME) keeps its
+// table [G][slots] of 64-bit slots: in registers without GROUP BY (one row), per workgroup in LDS up to `lds_max_slots` slots, in HBM up to
+// `hbm_max_bytes` bytes of table; beyond that the query is refused (side_table_plan, pg_exec_sidepass.hip, words the refusal).  The tiers' values index the paths' kernel names.
 enum Tier { TIER_REFUSED = -1, TIER_REG = 0, TIER_LDS = 1, TIER_HBM = 2 };
 Tier side_tier(int32_t n_group_by, uint64_t n_slots, uint64_t lds_max_slots, uint64_t table_bytes, int64_t hbm_max_bytes);
 }  // namespace pg

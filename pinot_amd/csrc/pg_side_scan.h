@@ -1,8 +1,10 @@
-// The device half of the slot-table side passes (pg_kernels_expr.hip, pg_kernels_var.hip, pg_kernels_withtime.hip; the host half is the
-// frame of pg_exec_sidepass.hip): the walk over the filter's match words, the reductions across a wavefront, the skeleton of the two tiers
-// with a table and the launcher of the three tiers.  A family's kernels supply what is theirs as callables — what a matching doc adds to
-// its group's row, a slot's initial value, how a touched slot is flushed; everything here is inlined into them, and what they compute per
-// doc stays in their own translation unit (pg_kernels_expr.hip keeps contraction off for what it instantiates from here).
+// The device half of the slot-table side passes (pg_kernels_expr.hip, pg_kernels_var.hip, pg_kernels_covar.hip, pg_kernels_moment.hip,
+// pg_kernels_withtime.hip; the host half is the frame of pg_exec_sidepass.hip): the walk over the filter's match words, the reductions
+// across a wavefront, the skeleton of the two tiers with a table and the launcher of the three tiers.  A family's kernels supply what is
+// theirs as callables — what a matching doc adds to its group's row, a slot's initial value, how a touched slot is flushed; the families
+// whose slots are int64 sums (the variance family, covariance, SKEWNESS / KURTOSIS) share those two in side_sum_table_pass, the addition
+// of a digit and the load of an INT column.  Everything here is inlined into the kernels, and what they compute per doc stays in their
+// own translation unit (pg_kernels_expr.hip and pg_kernels_covar.hip keep contraction off for what they instantiate from here).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -74,6 +76,28 @@ PG_SIDE_DEVFN void side_table_pass(const PgGroupScan& scan, uint64_t n_slots, T*
   } else {
     side_scan_walk(scan, at, [&](uint32_t doc) PG_SIDE_INLINE { update(table, doc); });
   }
+}
+
+// ---- tables of int64 sums ----------------------------------------------------------------------------------------------------------------
+// a digit added to its slot, in LDS or in HBM; zero digits are skipped
+template <typename Ptr>
+PG_SIDE_DEVFN void side_sum_add(Ptr slot, int64_t d) {
+  if (d) atomicAdd(reinterpret_cast<unsigned long long*>(slot), (unsigned long long)d);
+}
+
+// an INT column's value: raw big-endian, or through its INT dictionary
+static PG_SIDE_DEVFN int64_t side_load_int(const PgValueSrc& S, uint32_t doc) {
+  if (S.col_kind == PG_COL_FIXED_BIT) return (int64_t)reinterpret_cast<const int32_t*>(S.dict)[pg_fixed_bit_id(S.data, S.bits, doc)];   // wave-uniform
+  return (int64_t)(int32_t)__builtin_bswap32(reinterpret_cast<const uint32_t*>(S.data)[doc]);
+}
+
+// side_table_pass over sums: the workgroup's copy starts at zero and only its touched slots are added to `table`.  update(row0, doc):
+// `row0` is the table's first slot — the workgroup's copy in LDS, or the table in HBM.
+template <bool LDS, typename Update>
+PG_SIDE_DEVFN void side_sum_table_pass(const PgGroupScan& scan, uint64_t n_slots, int64_t* table, Update&& update) {
+  side_table_pass<LDS>(
+      scan, n_slots, table, [](uint32_t) PG_SIDE_INLINE { return (int64_t)0; }, update,
+      [&](uint32_t i, int64_t v) PG_SIDE_INLINE { side_sum_add(table + i, v); });
 }
 
 // the pass of one tier: the LDS tier's workgroup has 512 threads and a table of `lds_bytes` (at most `lds_max_bytes`), the others 256 threads

@@ -1,25 +1,42 @@
-"""What the two side passes — exact PERCENTILE (pg_exec_percentile.hip) and aggregations over an expression (pg_exec_expr.hip) — share: the
-split of the query, the filter's match words, the join by group key and the statistics written at the end (pg_exec_sidepass.hip).  Both paths
-run the same shapes over the segments of tests/test_gpu_percentile.py at 1, 64 and 1 003 docs (the last match word of 1 003 docs is partial:
-with a filter the word comes from the filter, without one it is made up in the kernel), and are held to the models of the two modules.
-The last test nests all four side paths of the frame's table in one query."""
+"""What the side passes — exact PERCENTILE (pg_exec_percentile.hip), aggregations over an expression (pg_exec_expr.hip), the variance family
+(pg_exec_var.hip), COVAR_POP / COVAR_SAMP (pg_exec_covar.hip) and SKEWNESS / KURTOSIS (pg_exec_moment.hip) — share: the split of the query, the
+filter's match words, the join by group key and the statistics written at the end (pg_exec_sidepass.hip).  All paths run the same shapes over
+the segments of tests/test_gpu_percentile.py at 1, 64 and 1 003 docs (the last match word of 1 003 docs is partial: with a filter the word
+comes from the filter, without one it is made up in the kernel), and are held to the models of their modules.  Between them the sum-table
+paths cover the integer path (v7) and the double path (ld, a dictionary LONG).  The last test nests all six side paths of the frame's table
+in one query."""
 import numpy as np
 import pytest
 
 from pinot_amd import capi
 from pinot_amd.executor import CancelToken, NativeSegment
 from pinot_amd.query import CQuery, parse_sql, with_time_arguments
+from tests import covariance_model as cm
 from tests import expression_model as em
+from tests import fourth_moment_model as fm
 from tests import percentile_model as pm
 from tests import variance_model as vm
 from tests import with_time_model as wm
+from tests import test_gpu_covariance as tc
 from tests import test_gpu_expressions as te
+from tests import test_gpu_moments as tm
 from tests import test_gpu_percentile as tp
+from tests import test_gpu_variance as tv
 
 pytestmark = pytest.mark.gpu
 SIZES = [1, 64, 1003]
-SIDE = {"percentile": "PERCENTILE(v7, 50)", "expression": "SUM(add(v7, v3))"}
-SIDE_COLUMNS = {"percentile": ["v7"], "expression": ["v7", "v3"]}
+SIDE = {"percentile": "PERCENTILE(v7, 50)", "expression": "SUM(add(v7, v3))", "variance": "VAR_POP(v7)", "covariance": "COVAR_SAMP(v7, ld)",
+        "moment": "KURTOSIS(ld)"}
+SIDE_COLUMNS = {"percentile": ["v7"], "expression": ["v7", "v3"], "variance": ["v7"], "covariance": ["v7", "ld"], "moment": ["ld"]}
+CHECK = {"percentile": tp._check, "expression": te._check, "variance": tv._check, "covariance": tc._check, "moment": tm._check}
+# the sum-table paths: the kernels' prefix, the slots of a group's row (v7 is an INT column: the integer path; ld a LONG: the double path)
+# and the LDS tier's slots (side_tier)
+TABLE = {
+    "expression": ("pg_expr", 4, 16384),                                                          # the four limbs of one SUM
+    "variance": ("pg_var", 1 + tv.K["PG_VAR_INT_SLOTS"], tv.LDS_SLOTS),                          # the doc count, Sx, two digits of Sq
+    "covariance": ("pg_covar", cm.slots_per_group(["INT", "LONG"], 1, tc.K), tc.LDS_SLOTS),      # the count, two sums, one pair's products
+    "moment": ("pg_moment", 1 + tm.DBL_SLOTS, tm.LDS_SLOTS),                                     # the count, the digits of x .. x^4
+}
 GROUP_BY = [[], ["rg"], ["g7", "rg"]]   # rg is a raw column: its groups come back as values and are mapped through its virtual dictionary
 WHERE = " WHERE s < 700"
 
@@ -51,13 +68,15 @@ def _id_bits(data, column):
 
 
 def _kernel(path, data, group_by):
-    """the tier the default knobs choose: PG_PCTL_LDS_KEYS = 32 768 counters, PG_EXPR_LDS_SLOTS = 16 384 slots (four limbs per SUM)"""
+    """the tier the default knobs choose: PG_PCTL_LDS_KEYS = 32 768 counters; a sum table in registers without GROUP BY, in LDS up to the
+    path's LDS slots (16 384 each), else in HBM"""
     groups = 1
     for g in group_by:
         groups *= len(np.unique(np.asarray(data[g])))
     if path == "percentile":
         return "pg_pctl_lds" if groups * len(np.unique(data["v7"])) <= 32768 else "pg_pctl_hbm"
-    return "pg_expr_reg" if not group_by else ("pg_expr_lds" if groups * 4 <= 16384 else "pg_expr_hbm")
+    prefix, slots, lds_slots = TABLE[path]
+    return prefix + ("_reg" if not group_by else ("_lds" if groups * slots <= lds_slots else "_hbm"))
 
 
 @pytest.mark.parametrize("n", SIZES)
@@ -69,7 +88,7 @@ def test_statistics_of_both_paths(segments, path, filtered, group_by, n):
     host, data, schema, gpu, oracle = seg
     sql = _sql(SIDE[path], group_by, filtered)
     # groups, values, numDocsScanned, numEntriesScannedPostFilter, numEntriesScannedInFilter, stats_exact, numTotalDocs and the kernel's name
-    b = (tp if path == "percentile" else te)._check(seg, sql, kernel=_kernel(path, data, group_by))
+    b = CHECK[path](seg, sql, kernel=_kernel(path, data, group_by))
     assert b.stats.star_tree_index == -1
     # the pass's bytes on top of the ordinary part's: one read of the ids of every doc, and of the match words when there is a filter
     ordinary = gpu.execute(_sql("COUNT(*)", group_by, filtered))
@@ -161,11 +180,13 @@ def test_all_three_kinds_with_order_by_and_limit(segments):
 
 
 def test_all_four_kinds_nested_in_one_query(gpu_api, segments):
-    """the table of side paths end to end: the expression pass outside, the FIRSTWITHTIME pass inside it, the variance's inside that, the
-    PERCENTILE's innermost, a plain SUM in the ordinary part at the bottom — and pg_query_supported walking the same nesting"""
+    """the table of side paths end to end, all six entries: the expression pass outside, the FIRSTWITHTIME pass inside it, then the
+    covariance's, the SKEWNESS / KURTOSIS pass, the variance's, the PERCENTILE's innermost, a plain SUM in the ordinary part at the bottom —
+    and pg_query_supported walking the same nesting"""
     seg = segments(1003)
     host, data, schema, gpu, oracle = seg
-    sql = "SELECT g7, SUM(add(v7,v3)), FIRSTWITHTIME(v3, ld, 'INT'), VAR_POP(v7), PERCENTILE(v3, 95), SUM(s) FROM t" + WHERE + " GROUP BY g7"
+    sql = ("SELECT g7, SUM(add(v7,v3)), FIRSTWITHTIME(v3, ld, 'INT'), VAR_POP(v7), PERCENTILE(v3, 95), SUM(s), COVAR_SAMP(v7, ld), KURTOSIS(ld) FROM t"
+           + WHERE + " GROUP BY g7")
     qc = parse_sql(sql)
     gpu_api.call("query_supported", gpu.handle, CQuery(qc).ptr())   # PG_OK: anything else raises
     b = gpu.execute(qc)
@@ -180,8 +201,11 @@ def test_all_four_kinds_nested_in_one_query(gpu_api, segments):
     x, t, declared = with_time_arguments(qc.aggregations[1].column)
     assert (x, t, declared) == ("v3", "ld", "INT")
     for key, gdocs in groups.items():
-        total, first, var, runs, plain = rows[key]
+        total, first, var, runs, plain, covar, moment = rows[key]
         gdocs = np.sort(np.asarray(gdocs, dtype=np.int64))
+        v7, ld = tc._doubles(data, schema, "v7", gdocs), tc._doubles(data, schema, "ld", gdocs)
+        assert tc._same_tuple(covar, cm.exact_tuple(v7, ld)), key
+        assert fm.same_tuple(moment, fm.exact_tuple(ld)), key
         assert pm.same_double(total, em.agg_sum(v[gdocs])), key
         assert wm.pair_bits(declared, *first) == wm.aggregate("FIRSTWITHTIME", schema[x], data[x], data[t], gdocs, declared), key
         want = vm.exact_tuple(vm.as_doubles(np.asarray(data["v7"])[gdocs], "INT"))
