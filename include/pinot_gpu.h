@@ -293,7 +293,29 @@ typedef enum pg_agg_function {   /* AggregationFunctionType (subset named by nor
    * never taken for such a query; pg_result_merge / pg_result_all_reduce refuse its results (the Java side merges with
    * PinotFourthMoment#combine). */
   PG_AGG_SKEWNESS = 25,
-  PG_AGG_KURTOSIS = 26
+  PG_AGG_KURTOSIS = 26,
+  /* HISTOGRAM (HistogramAggregationFunction.java; intermediate and final value a DoubleArrayList of numBins counts) over one single-value
+   * INT / LONG / FLOAT / DOUBLE column, dictionary-encoded or raw, read as getDoubleValuesSV reads it (an INT exact, a LONG (double) rounded
+   * first, a FLOAT widened exactly).  pg_agg_spec.column is the argument list (the multi-argument form of FIRSTWITHTIME; commas split at
+   * depth 0, blanks are ignored): "x,'lower','upper','numBins'" — numBins equal-width bins, binLength = (upper - lower) / numBins in double
+   * — or "x,arrayvalueconstructor(e0,e1,...)" — at least 2 strictly increasing edges, each quoted, or bare for Infinity / -Infinity; lower =
+   * e0, upper = e_last.  Bins are [e_i, e_i+1), the last one closed on the right.  A doc's bin is getBinId's, IEEE double operation by
+   * operation: none for val > upper || val < lower, numBins - 1 for val == upper, else (int) floor((val - lower) / binLength) — two rounded
+   * operations, never contracted, never a reciprocal multiply — or the largest i with e_i <= val.  Infinite values are ordinary (-Inf falls
+   * into bin 0 of a list that starts at -Infinity, +Inf == upper into the last bin).  The result is PG_RESULT_DOUBLE_ARRAY: numBins counts
+   * per group, exact and order-free.  A group that matched docs gets its array even if every value fell outside [lower, upper] (all zeros);
+   * a query without GROUP BY whose filter matches no doc returns numBins zeros.  The result column's name is histogram(x).
+   * PG_ERR_INVALID_ARGUMENT with the reference's message: an argument count other than 2 or 4, a second argument that is no array, fewer
+   * than 2 edges, edges not strictly increasing, upper <= lower, numBins <= 0, a bound that is no number.  PG_ERR_NOT_FOUND: an unknown
+   * column.  Refused (PG_ERR_UNSUPPORTED, the Java plan answers): a STRING / BYTES or multi-value x, an expression x, a multi-value group-by
+   * column next to it, under PG_QUERY_FLAG_NULL_HANDLING an x or group-by column that holds nulls, a group key space over 2^32, non-finite
+   * lower / upper in the equal-width form, more than 65 536 bins in one histogram, more than 4 distinct (column, bin specification) pairs
+   * in one query (equal pairs share their slots), a count table beyond PG_HIST_HBM_MAX_BYTES (default 256 MiB); and from pg_query_exec
+   * alone the two inputs on which the reference throws — a matching doc whose value is NaN (the edge form's search walks to index numBins),
+   * and one whose equal-width index rounds up to numBins (HISTOGRAM(x, 0, 1, 3) over 0.9999999999999999): nothing is clamped.  The
+   * star-tree route is never taken for such a query; pg_result_merge / pg_result_all_reduce refuse its results (the Java side merges with
+   * DoubleVectorOpUtils#vectorAdd). */
+  PG_AGG_HISTOGRAM = 27
 } pg_agg_function;
 
 typedef struct pg_agg_spec {
@@ -487,6 +509,8 @@ typedef enum pg_result_kind {
                               pg_result_doubles(r, agg, 2) sumXY (component 2 exists for this kind only), pg_result_longs(r, agg, 0) the count */
   PG_RESULT_FOURTH_MOMENT = 11, /* SKEWNESS / KURTOSIS: PinotFourthMoment — pg_result_longs(r, agg, 0) n, pg_result_doubles(r, agg, 0 .. 3) m1 .. m4
                               (components 2 and 3 exist for this kind; 2 also for PG_RESULT_COVARIANCE_TUPLE) */
+  PG_RESULT_DOUBLE_ARRAY = 12, /* HISTOGRAM: the group's DoubleArrayList of counts — pg_result_set_sizes gives numBins for every group,
+                              pg_result_set_values_double the counts, group-major */
   PG_RESULT_VALUE_COUNTS = 7 /* PERCENTILE: the group's DoubleArrayList as runs — pg_result_set_sizes gives the runs per group, pg_result_set_values_double
                               the runs' values (ascending under Double.compare within a group), pg_result_set_counts how often each occurs */
 } pg_result_kind;

@@ -318,6 +318,8 @@ public class GpuGroupByOperator extends BaseOperator<BaseResultsBlock> {
         return GpuResultObjects.varianceTuples(result, a, n);                    // (count, sum, m2) -> VarianceTuple, the holder's value and the intermediate alike (VarianceAggregationFunction.java:66-74)
       case PinotGpu.RESULT_COVARIANCE_TUPLE:
         return GpuResultObjects.covarianceTuples(result, a, n);                  // (sumX, sumY, sumXY, count) -> CovarianceTuple, the holder's value and the intermediate alike (CovarianceAggregationFunction.java:112-130)
+      case PinotGpu.RESULT_DOUBLE_ARRAY:
+        return GpuResultObjects.countArrays(result, a, n);                       // numBins counts -> DoubleArrayList, the holder's value and the intermediate alike (HistogramAggregationFunction)
       case PinotGpu.RESULT_FOURTH_MOMENT:
         return GpuResultObjects.fourthMoments(result, a, n);                     // (n, m1, m2, m3, m4) -> PinotFourthMoment, the holder's value and the intermediate alike (FourthMomentAggregationFunction)
       case PinotGpu.RESULT_VALUE_TIME_PAIR:

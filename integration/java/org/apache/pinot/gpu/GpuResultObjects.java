@@ -242,6 +242,30 @@ public final class GpuResultObjects {
     return out;
   }
 
+  /** HISTOGRAM (pg_result_kind PG_RESULT_DOUBLE_ARRAY): per group the function's DoubleArrayList of numBins counts, as the library counted
+   *  them.  Arrays of several segments merge with DoubleVectorOpUtils#vectorAdd (HistogramAggregationFunction#merge), as the reference's
+   *  own do. */
+  public static Object[] countArrays(long result, int aggregation, int numGroups) {
+    int[] sizes = new int[numGroups];
+    PinotGpu.resultSetSizes(result, aggregation, sizes);
+    long total = 0;
+    for (int s : sizes) {
+      total += s;
+    }
+    if (total > Integer.MAX_VALUE - 8) {
+      throw new UnsupportedOperationException("HISTOGRAM state of " + total + " bins exceeds one Java array");
+    }
+    double[] counts = new double[(int) total];
+    PinotGpu.resultSetValuesDouble(result, aggregation, counts);
+    Object[] out = new Object[numGroups];
+    int at = 0;
+    for (int g = 0; g < numGroups; g++) {
+      out[g] = it.unimi.dsi.fastutil.doubles.DoubleArrayList.wrap(java.util.Arrays.copyOfRange(counts, at, at + sizes[g]));
+      at += sizes[g];
+    }
+    return out;
+  }
+
   /** SKEWNESS / KURTOSIS (pg_result_kind PG_RESULT_FOURTH_MOMENT): per group the function's PinotFourthMoment from the library's five
    *  components — n and the exact m1 .. m4, each rounded once.  The object's fields are inherited and protected: it is built from its own
    *  serialized form (PinotFourthMoment#serialize: long n, doubles m1 .. m4, big-endian).  Moments of several segments merge with

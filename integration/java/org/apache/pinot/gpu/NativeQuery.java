@@ -112,6 +112,15 @@ public final class NativeQuery implements AutoCloseable {
         putString(b, args.get(0).getIdentifier() + "," + args.get(1).getIdentifier());
         continue;
       }
+      if (fn == 27) {   // PG_AGG_HISTOGRAM: the argument list "x,'lower','upper','numBins'" / "x,arrayvalueconstructor(e0,e1,...)" in pg_agg_spec.column
+        String list = histogramArguments(q, f);
+        if (list == null) {
+          return null;
+        }
+        b.putInt(fn).putInt(0);
+        putString(b, list);
+        continue;
+      }
       if (fn < 0 || args.size() > 1) {
         return null;
       }
@@ -300,6 +309,35 @@ public final class NativeQuery implements AutoCloseable {
     return args.get(0).getIdentifier() + "," + args.get(1).getIdentifier() + ",'" + type + "'";
   }
 
+  /** HISTOGRAM: the argument list as the query spells it.  The function keeps its bins to itself (no accessor), so they are read where it
+   *  read them: the FunctionContext of the query's aggregation with f's result column name — the column, then the three literals or the
+   *  arrayvalueconstructor call, each printed by ExpressionContext#toString (a literal quoted, Infinity / -Infinity bare identifiers).  Null
+   *  for an argument that is no column, for a filtered aggregation and for a literal array (the Java plan answers). */
+  private static String histogramArguments(QueryContext q, AggregationFunction f) {
+    for (java.util.Map.Entry<org.apache.commons.lang3.tuple.Pair<org.apache.pinot.common.request.context.FunctionContext,
+        org.apache.pinot.common.request.context.FilterContext>, Integer> e : q.getFilteredAggregationsIndexMap().entrySet()) {
+      org.apache.pinot.common.request.context.FunctionContext fc = e.getKey().getLeft();
+      if (q.getAggregationFunctions()[e.getValue()] != f) {
+        continue;
+      }
+      List<ExpressionContext> args = fc.getArguments();
+      if (e.getKey().getRight() != null || (args.size() != 2 && args.size() != 4) || args.get(0).getType() != ExpressionContext.Type.IDENTIFIER) {
+        return null;
+      }
+      StringBuilder list = new StringBuilder(args.get(0).getIdentifier());
+      for (int i = 1; i < args.size(); i++) {
+        ExpressionContext a = args.get(i);
+        boolean array = a.getType() == ExpressionContext.Type.FUNCTION && a.getFunction().getFunctionName().equals("arrayvalueconstructor");
+        if (args.size() == 2 ? !array : a.getType() != ExpressionContext.Type.LITERAL) {
+          return null;
+        }
+        list.append(',').append(a.toString());
+      }
+      return list.toString();
+    }
+    return null;
+  }
+
   private static String withTimeType(AggregationFunction f) {
     if (f instanceof org.apache.pinot.core.query.aggregation.function.FirstIntValueWithTimeAggregationFunction
         || f instanceof org.apache.pinot.core.query.aggregation.function.LastIntValueWithTimeAggregationFunction) {
@@ -355,6 +393,8 @@ public final class NativeQuery implements AutoCloseable {
       // type, FOURTHMOMENT, has no final result and stays with the Java plan
       case SKEWNESS: return f instanceof org.apache.pinot.core.query.aggregation.function.FourthMomentAggregationFunction ? 25 : -1;
       case KURTOSIS: return f instanceof org.apache.pinot.core.query.aggregation.function.FourthMomentAggregationFunction ? 26 : -1;
+      // the bin counts (pg_agg_function 27): intermediate and final value the same DoubleArrayList
+      case HISTOGRAM: return f instanceof org.apache.pinot.core.query.aggregation.function.HistogramAggregationFunction ? 27 : -1;
       case FIRSTWITHTIME:
         return f instanceof org.apache.pinot.core.query.aggregation.function.FirstWithTimeAggregationFunction && withTimeType(f) != null ? 21 : -1;
       case LASTWITHTIME:

@@ -24,6 +24,7 @@ public final class PinotGpu {
       RESULT_HLL = 5, RESULT_VALUE_SET = 6, RESULT_VALUE_COUNTS = 7,
       RESULT_VALUE_TIME_PAIR = 9,   // FIRSTWITHTIME / LASTWITHTIME: resultLongs(.., 0) the time, resultLongs(.., 1) an INT / LONG value, resultDoubles(.., 0) a FLOAT / DOUBLE value
       RESULT_VARIANCE_TUPLE = 8,   // VAR_POP / VAR_SAMP / STDDEV_POP / STDDEV_SAMP: resultLongs(.., 0) the count, resultDoubles(.., 0) the sum, resultDoubles(.., 1) m2
+      RESULT_DOUBLE_ARRAY = 12,   // HISTOGRAM: resultSetSizes(..) numBins for every group, resultSetValuesDouble(..) the counts, group-major
       RESULT_FOURTH_MOMENT = 11,   // SKEWNESS / KURTOSIS: resultLongs(.., 0) n, resultDoubles(.., 0 .. 3) m1 .. m4
       RESULT_COVARIANCE_TUPLE = 10;   // COVAR_POP / COVAR_SAMP: resultDoubles(.., 0) sumX, (.., 1) sumY, (.., 2) sumXY, resultLongs(.., 0) the count
   public static final int GROUP_KEY_DICT_IDS = 0, GROUP_KEY_LONG_VALUES = 1, GROUP_KEY_DOUBLE_VALUES = 2, GROUP_KEY_BYTES_VALUES = 3;

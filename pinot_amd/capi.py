@@ -40,9 +40,10 @@ AGG_FUNCTIONS = {"COUNT": 0, "SUM": 1, "MIN": 2, "MAX": 3, "AVG": 4, "DISTINCTCO
                  "DISTINCTCOUNTMV": 14, "DISTINCTCOUNTHLLMV": 15, "PERCENTILE": 16,
                  "VARPOP": 17, "VARSAMP": 18, "STDDEVPOP": 19, "STDDEVSAMP": 20,
                  "FIRSTWITHTIME": 21, "LASTWITHTIME": 22, "COVARPOP": 23, "COVARSAMP": 24,
-                 "SKEWNESS": 25, "KURTOSIS": 26}
+                 "SKEWNESS": 25, "KURTOSIS": 26, "HISTOGRAM": 27}
 WITH_TIME_FUNCTIONS = ("FIRSTWITHTIME", "LASTWITHTIME")   # their AggregationSpec.column is the argument list "x,t,'TYPE'" (include/pinot_gpu.h)
 COVARIANCE_FUNCTIONS = ("COVARPOP", "COVARSAMP")   # CovarianceAggregationFunction: one intermediate, two final values; AggregationSpec.column is the argument list "x,y"
+HISTOGRAM_FUNCTIONS = ("HISTOGRAM",)   # HistogramAggregationFunction: AggregationSpec.column is the argument list "x,'lower','upper','numBins'" or "x,arrayvalueconstructor(e0,e1,...)"
 FOURTH_MOMENT_FUNCTIONS = ("SKEWNESS", "KURTOSIS")   # FourthMomentAggregationFunction: one intermediate (PinotFourthMoment), two final values
 WITH_TIME_TYPES = ("INT", "LONG", "FLOAT", "DOUBLE")      # the declared types the GPU path runs
 VARIANCE_FUNCTIONS = ("VARPOP", "VARSAMP", "STDDEVPOP", "STDDEVSAMP")   # VarianceAggregationFunction: one intermediate, four final values
@@ -51,6 +52,7 @@ MV_TO_SV_FUNCTION = {"COUNTMV": "COUNT", "SUMMV": "SUM", "MINMV": "MIN", "MAXMV"
 RESULT_LONG, RESULT_DOUBLE, RESULT_AVG_PAIR, RESULT_MINMAX_PAIR, RESULT_DICTID_SET, RESULT_HLL, RESULT_VALUE_SET, RESULT_VALUE_COUNTS = range(8)
 RESULT_VALUE_TIME_PAIR = 9   # ValueLongPair: result_longs(.., 0) the time, result_longs(.., 1) an INT / LONG value, result_doubles(.., 0) a FLOAT / DOUBLE value
 RESULT_COVARIANCE_TUPLE = 10   # CovarianceTuple: result_doubles(.., 0) sumX, (.., 1) sumY, (.., 2) sumXY, result_longs(.., 0) the count
+RESULT_DOUBLE_ARRAY = 12   # HISTOGRAM's DoubleArrayList: result_set_sizes numBins per group, result_set_values_double the counts, group-major
 RESULT_FOURTH_MOMENT = 11   # PinotFourthMoment: result_longs(.., 0) n, result_doubles(.., 0 .. 3) m1 .. m4
 RESULT_VARIANCE_TUPLE = 8   # VarianceTuple: result_longs(.., 0) the count, result_doubles(.., 0) the sum, result_doubles(.., 1) m2
 

@@ -47,6 +47,8 @@ static void knobs_read(Knobs& k) {
   k.expr_hbm_max_bytes = std::max<int64_t>(8, num("PG_EXPR_HBM_MAX_BYTES", (int64_t)256 << 20));
   k.var_hbm_max_bytes = std::max<int64_t>(8, num("PG_VAR_HBM_MAX_BYTES", (int64_t)256 << 20));
   k.moment_hbm_max_bytes = std::max<int64_t>(8, num("PG_MOMENT_HBM_MAX_BYTES", (int64_t)256 << 20));
+  k.hist_hbm_max_bytes = std::max<int64_t>(8, num("PG_HIST_HBM_MAX_BYTES", (int64_t)256 << 20));
+  k.hist_combine_rounds = std::min<int64_t>(64, num("PG_HIST_COMBINE_ROUNDS", -1));
   k.covar_hbm_max_bytes = std::max<int64_t>(8, num("PG_COVAR_HBM_MAX_BYTES", (int64_t)256 << 20));
   k.wt_hbm_max_bytes = std::max<int64_t>(8, num("PG_WT_HBM_MAX_BYTES", (int64_t)256 << 20));
   k.limit_prefix_min_docs = std::max<int64_t>(PG_WAVE_DOCS, num("PG_LIMIT_PREFIX_MIN_DOCS", (int64_t)1 << 20));
@@ -319,6 +321,7 @@ static void refuse_merged_elsewhere(uint32_t kinds) {
       {MERGED_FOURTH_MOMENT, "results of SKEWNESS / KURTOSIS aggregations are merged on the Java side (PinotFourthMoment#combine)"},
       {MERGED_COVARIANCE, "results of covariance aggregations are merged on the Java side (CovarianceTuple#apply)"},
       {MERGED_WITH_TIME, "results of FIRSTWITHTIME / LASTWITHTIME are merged on the Java side (the functions' own merge of ValueLongPair)"},
+      {MERGED_HISTOGRAM, "results of HISTOGRAM aggregations are merged on the Java side (DoubleVectorOpUtils#vectorAdd)"},
   };
   for (const auto& r : kRefusals) if (kinds & r.bit) fail(PG_ERR_UNSUPPORTED, "%s", r.text);
 }
@@ -466,7 +469,7 @@ int32_t pg_result_longs(pg_result_t result, int32_t agg, int32_t component, int6
 int32_t pg_result_set_sizes(pg_result_t result, int32_t agg, int32_t* out_sizes, int32_t capacity) {
   return guarded([&] {
     AggResult& a = agg_of(result, agg);
-    REQUIRE(a.kind == PG_RESULT_DICTID_SET || a.kind == PG_RESULT_VALUE_SET || a.kind == PG_RESULT_VALUE_COUNTS, "aggregation is not a DISTINCTCOUNT or PERCENTILE");
+    REQUIRE(a.kind == PG_RESULT_DICTID_SET || a.kind == PG_RESULT_VALUE_SET || a.kind == PG_RESULT_VALUE_COUNTS || a.kind == PG_RESULT_DOUBLE_ARRAY, "aggregation is not a DISTINCTCOUNT, PERCENTILE or HISTOGRAM");
     REQUIRE(capacity >= result->r->num_groups, "capacity too small");
     if (!a.set_sizes.empty()) memcpy(out_sizes, a.set_sizes.data(), a.set_sizes.size() * 4);
   });
@@ -490,7 +493,7 @@ int32_t pg_result_set_values_long(pg_result_t result, int32_t agg, int64_t* out_
 int32_t pg_result_set_values_double(pg_result_t result, int32_t agg, double* out_values, int64_t capacity) {
   return guarded([&] {
     AggResult& a = agg_of(result, agg);
-    REQUIRE((a.kind == PG_RESULT_VALUE_SET && a.set_value_kind >= 2) || a.kind == PG_RESULT_VALUE_COUNTS, "aggregation is not a DISTINCTCOUNT over a raw FLOAT / DOUBLE column or a PERCENTILE");
+    REQUIRE((a.kind == PG_RESULT_VALUE_SET && a.set_value_kind >= 2) || a.kind == PG_RESULT_VALUE_COUNTS || a.kind == PG_RESULT_DOUBLE_ARRAY, "aggregation is not a DISTINCTCOUNT over a raw FLOAT / DOUBLE column, a PERCENTILE or a HISTOGRAM");
     REQUIRE(capacity >= (int64_t)a.d[0].size(), "capacity too small");
     if (!a.d[0].empty()) memcpy(out_values, a.d[0].data(), a.d[0].size() * 8);
   });

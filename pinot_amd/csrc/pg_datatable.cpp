@@ -86,6 +86,7 @@ const char* function_name(int32_t fn) {   // AggregationFunctionType#getName().t
     case PG_AGG_STDDEVSAMP: return "stddevsamp";
     case PG_AGG_SKEWNESS: return "skewness";
     case PG_AGG_KURTOSIS: return "kurtosis";
+    case PG_AGG_HISTOGRAM: return "histogram";   // getResultColumnName: "histogram(" + the first argument + ")"; the bins are not part of the name
     case PG_AGG_COVARPOP: return "covarpop";   // getResultColumnName: the lower-case name + "(" + the arguments joined by "," + ")"
     case PG_AGG_COVARSAMP: return "covarsamp";
     case PG_AGG_FIRSTWITHTIME: return "firstwithtime";   // getResultColumnName: the lower-case name + "(" + the argument list as given + ")"
@@ -156,6 +157,10 @@ std::vector<uint8_t> result_data_table_v4(const Result& r) {
     std::string arguments = c.name;
     if (c.function == PG_AGG_COVARPOP || c.function == PG_AGG_COVARSAMP)   // the argument list without its blanks: "covarpop(x,y)"
       arguments.erase(std::remove_if(arguments.begin(), arguments.end(), [](char ch) { return ch == ' ' || ch == '\t' || ch == '\n' || ch == '\r'; }), arguments.end());
+    if (c.function == PG_AGG_HISTOGRAM) {   // the first argument alone: up to the first comma (x is a column), without blanks
+      arguments = arguments.substr(0, arguments.find(','));
+      arguments.erase(std::remove_if(arguments.begin(), arguments.end(), [](char ch) { return ch == ' ' || ch == '\t' || ch == '\n' || ch == '\r'; }), arguments.end());
+    }
     names.push_back(count_star ? std::string("count(*)") : std::string(function_name(c.function)) + "(" + arguments + ")");
     switch (r.aggs[(size_t)a].kind) {
       case PG_RESULT_LONG:
@@ -322,6 +327,14 @@ std::vector<uint8_t> result_data_table_v4(const Result& r) {
           Out p;
           p.i32((int32_t)total);
           for (int32_t e = 0; e < n; e++) for (int64_t k = 0; k < ar.l[0][at + (size_t)e]; k++) p.f64(ar.d[0][at + (size_t)e]);
+          object(3, p);
+          break;
+        }
+        case PG_RESULT_DOUBLE_ARRAY: {   // HISTOGRAM: the DoubleArrayList of numBins counts (ObjectSerDeUtils type 3, as PERCENTILE's list)
+          const int32_t n = ar.set_sizes[(size_t)i];
+          Out p;
+          p.i32(n);
+          for (int32_t e = 0; e < n; e++) p.f64(ar.d[0][(size_t)i * (size_t)n + (size_t)e]);
           object(3, p);
           break;
         }

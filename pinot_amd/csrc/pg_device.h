@@ -736,6 +736,47 @@ struct PgMomentArgs {
   int64_t* table;              // [G][slots] in HBM, zeroed by the caller
   PgMomentCol cols[PG_MOMENT_MAX_COLS];
 };
+// ---- HISTOGRAM (pg_kernels_hist.hip) -----------------------------------------------------------------------------------------------------
+// One counting pass for all HISTOGRAM aggregations of a query: per matching doc the group key, then per distinct (column, bin specification)
+// the doc's bin (pg_hist_bin, pg_histogram.h) and one add to the group's row — a table [G][slots] of int64 counts, a row the concatenated
+// bins of the query's distinct specifications.  The groups come from the ordinary part: there is no count slot.
+#include "pg_histogram.h"
+#define PG_HIST_LDS_SLOTS 16384       // 128 KiB of the CU's 160 KiB as int64 (pg_hist_lds: persistent workgroups, up to 4 per CU where their tables fit); pg_hist_one keeps
+                                      // such a row as 32-bit counts, in as many copies as fit PG_HIST_ONE_LDS_BYTES
+#define PG_HIST_LDS_MAX_BYTES 147456  // the LDS tier's table with the edges staged behind it (144 KiB); edges that do not fit are read from HBM
+#define PG_HIST_ONE_LDS_BYTES 65536   // pg_hist_one: the copies of the row (two workgroups per CU); the edges are staged behind them while
+#define PG_HIST_ONE_EDGE_BYTES 12288  //   they fit these bytes
+#define PG_HIST_ONE_WAVES 16          // wavefronts of a pg_hist_one workgroup (two of them fill a CU's 32): at most so many copies of the row
+// What pg_hist_one combines inside the wavefront before its LDS atomics.  0: nothing, one plain atomic per doc.  1: a 64-doc word whose docs
+// all fall into one bin adds their number once (one readfirstlane, two ballots, a popcount), every other word takes plain atomics.  r >= 2:
+// besides, the first r distinct bins of a mixed word are combined, one readfirstlane + ballot + popcount round and one add each, and the
+// lanes left after that take plain atomics.  The cut is 1, from profiles/histogram_prof.txt (2 x 10^8 docs, pass time in ms, uniform data /
+// all docs in one bin): 0: 0.68 / 0.77, 1: 0.72 / 0.80, 2: 1.05 / 0.86, 4: 1.37 / 0.86, 64: 2.37 / 0.88 at 10 bins and 10.7 at 1 000.  The
+// kernel is bound by its per-doc instructions (the double division of getBinId), not by LDS: with a copy of the row per wavefront even 64
+// lanes on one address cost 0.08 ms per 2 x 10^8 docs, so every round of the loop costs more than the conflicts it removes, from the
+// second distinct bin on.  The one-bin test is kept at its 5 % so that no word issues 64 same-address atomics.
+#define PG_HIST_COMBINE_ROUNDS 1
+struct PgHistCol {
+  PgValueSrc src;
+  pg_hist_spec spec;             // `edges` points into PgHistArgs::edges
+  int32_t first_slot;            // the specification's first bin within the group's row
+  int32_t edge_off;              // its first edge in PgHistArgs::edges (the edge form)
+};
+struct PgHistArgs {
+  PgGroupScan scan;            // match words and group columns
+  int32_t n_cols;
+  int32_t slots;               // slots per group
+  uint64_t n_groups;           // G (<= 2^32)
+  uint64_t n_slots;            // G x slots
+  int64_t* table;              // [G][slots] in HBM, zeroed by the caller
+  const double* edges;         // the edge lists of every specification, back to back (HBM)
+  int32_t n_edges;
+  int32_t stage_edges;         // the kernel copies `edges` into LDS behind its table
+  int32_t copies;              // pg_hist_one: copies of the row in LDS (a wavefront adds to copy wave % copies)
+  int32_t combine_rounds;      // pg_hist_one: PG_HIST_COMBINE_ROUNDS, or what PG_HIST_COMBINE_ROUNDS in the environment asks for (a measurement)
+  uint32_t* throws;            // set to -PG_HIST_THROWS_* by any lane whose doc is one the reference throws on; zeroed by the caller
+  PgHistCol cols[PG_HIST_MAX_SPECS];
+};
 // a time-bucket transform as a key (pg_kernels_timekey.hip): the value column and the normal form, wave-uniform kernel arguments
 struct PgTimeKeyArgs {
   PgValueSrc src;

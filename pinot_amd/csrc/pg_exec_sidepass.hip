@@ -1,5 +1,5 @@
 // The frame of the side passes: aggregations answered by a pass of their own and joined to the ordinary plan by group key (exact PERCENTILE:
-// pg_exec_percentile.hip; aggregations over an expression: pg_exec_expr.hip; the variance family: pg_exec_var.hip; COVAR_POP / COVAR_SAMP: pg_exec_covar.hip; SKEWNESS / KURTOSIS: pg_exec_moment.hip; FIRSTWITHTIME / LASTWITHTIME: pg_exec_withtime.hip).
+// pg_exec_percentile.hip; aggregations over an expression: pg_exec_expr.hip; the variance family: pg_exec_var.hip; COVAR_POP / COVAR_SAMP: pg_exec_covar.hip; SKEWNESS / KURTOSIS: pg_exec_moment.hip; HISTOGRAM: pg_exec_hist.hip; FIRSTWITHTIME / LASTWITHTIME: pg_exec_withtime.hip).
 // The paths are the entries of kSidePaths below, in nesting order; side_path_of, side_check and execute_query (pg_nullaware.cpp) follow that list.  A path plans its aggregations and its group-by
 // columns (side_groups, side_argument_column; side_columns_read for what the other paths' aggregations read), splits the query
 // (side_base_query), and then
@@ -11,7 +11,7 @@
 // The paths with a table [G][slots] of 64-bit slots share more: the end of their plans (side_table_plan: the groups, where the table lives
 // — side_tier — and the refusal of a table over the path's knob), the pass's grid (side_pass_grid), the gather of the admitted rows
 // (side_gather_rows) and the pass's bytes (side_pass_bytes, value_src_bits).
-// The four of them whose slots are int64 sums (expressions, the variance family, covariance, SKEWNESS / KURTOSIS) share the whole sequence:
+// The five of them whose slots are int64 sums (expressions, the variance family, covariance, SKEWNESS / KURTOSIS, HISTOGRAM) share the whole sequence:
 // SumTablePass, at the end of this file, runs steps 1 to 3 with the table's allocation and initialisation, the launch, the gather through
 // pg_expr_gather and the doc-count checks.  Such a path supplies its plan, its kernel arguments, a launch callable, the LDS tier's
 // workgroups per CU, the kernel name to report, an initialiser where zero is not the identity, and the reading of the gathered rows into its
@@ -24,6 +24,7 @@
 
 #include "pg_internal.hpp"
 #include "pg_expr.h"
+#include "pg_histogram.h"
 
 void pg_expr_launch_gather(const int64_t* table, const uint32_t* rows, int32_t n_rows, int32_t slots, uint64_t n_groups, int64_t* out, int grid, hipStream_t stream);
 
@@ -141,6 +142,8 @@ const SidePath kSidePaths[] = {
     {is_covariance_agg, covariance_plan_check, execute_covariance, kSideBaseClears},
     // inside the covariance pass, outside the variance's: SKEWNESS / KURTOSIS next to VAR_POP and PERCENTILE leave those to the passes below
     {is_moment_agg, moment_plan_check, execute_moment, kSideBaseClears},
+    // inside the SKEWNESS / KURTOSIS pass, outside the variance's: its ordinary part (COUNT(*) when nothing else remains) names the groups
+    {is_histogram_agg, histogram_plan_check, execute_histogram, kSideBaseClears},
     // inside the expression pass, outside the PERCENTILE's: its ordinary part comes back through execute_query
     {is_variance_agg, variance_plan_check, execute_variance, kSideBaseClears},
     // its ordinary part comes back through execute_query; nulls in its columns are refused (percentile_plan_check)
@@ -226,6 +229,12 @@ Column* side_value_column(Segment& seg, const char* name, const char* fn, bool n
 
 void side_columns_read(const pg_agg_spec& s, std::set<std::string>& read) {
   if (!s.column) return;
+  if (is_histogram_agg(s)) {   // x, then the bins
+    HistSpec spec;
+    std::string error;
+    if (hist_parse_arguments(s.column, spec, error) == PG_OK && !expr_is_expression(spec.column.c_str())) read.insert(spec.column);
+    return;
+  }
   const bool with_time = is_with_time_agg(s);
   if (!with_time && !is_covariance_agg(s)) {
     if (strcmp(s.column, "*") != 0) read.insert(s.column);
@@ -274,6 +283,7 @@ const char* agg_function_text(int32_t fn) {
     case PG_AGG_COVARSAMP: return "COVAR_SAMP";
     case PG_AGG_SKEWNESS: return "SKEWNESS";
     case PG_AGG_KURTOSIS: return "KURTOSIS";
+    case PG_AGG_HISTOGRAM: return "HISTOGRAM";
     case PG_AGG_FIRSTWITHTIME: return "FIRSTWITHTIME";
     case PG_AGG_LASTWITHTIME: return "LASTWITHTIME";
     default: return "this aggregation function";

@@ -465,6 +465,7 @@ struct AggResult {
   // PG_RESULT_VARIANCE_TUPLE (VAR_POP / VAR_SAMP / STDDEV_POP / STDDEV_SAMP): l[0] = count, d[0] = sum, d[1] = m2
   // PG_RESULT_COVARIANCE_TUPLE (COVAR_POP / COVAR_SAMP): d[0] = sumX, d[1] = sumY, d[2] = sumXY, l[0] = count
   // PG_RESULT_FOURTH_MOMENT (SKEWNESS / KURTOSIS): l[0] = n, d[0] .. d[3] = m1 .. m4
+  // PG_RESULT_DOUBLE_ARRAY (HISTOGRAM): set_sizes = numBins for every group, d[0] = the groups' counts back to back (group-major)
   // PG_RESULT_VALUE_TIME_PAIR (FIRSTWITHTIME / LASTWITHTIME): l[0] = time; l[1] = the value in its declared type — an INT / LONG value, or the
   // raw IEEE bits of a FLOAT (32, zero-extended) / DOUBLE —, d[0] = a FLOAT / DOUBLE value (the FLOAT widened exactly); `value_type` the
   // declared type (pg_data_type: the data table's object type and the width of its value)
@@ -514,7 +515,7 @@ struct ResultColumn {
 // Result::merged_elsewhere, one bit per side path
 enum MergedElsewhere : uint32_t {
   MERGED_PERCENTILE = 1u << 0, MERGED_EXPRESSION = 1u << 1, MERGED_VARIANCE = 1u << 2, MERGED_FOURTH_MOMENT = 1u << 3, MERGED_COVARIANCE = 1u << 4,
-  MERGED_WITH_TIME = 1u << 5,
+  MERGED_WITH_TIME = 1u << 5, MERGED_HISTOGRAM = 1u << 6,
 };
 struct Result {
   std::vector<ResultColumn> schema_keys, schema_aggs;
@@ -538,7 +539,7 @@ struct Result {
   // MERGED_* bits: the side aggregations the query carried.  Their results merge on the Java side, never in the library (pg_api.cpp words
   // the refusals): a PERCENTILE's lists by value; an aggregation over an expression because the scale of its sums differs per segment; the
   // variance, SKEWNESS / KURTOSIS and covariance tuples by VarianceTuple#apply, PinotFourthMoment#combine and CovarianceTuple#apply; the
-  // FIRSTWITHTIME / LASTWITHTIME pairs with the functions' own merge
+  // FIRSTWITHTIME / LASTWITHTIME pairs with the functions' own merge; the HISTOGRAM arrays by DoubleVectorOpUtils#vectorAdd
   uint32_t merged_elsewhere = 0;
   pg_exec_stats stats{};
 };
@@ -567,7 +568,7 @@ constexpr int32_t kQueryFlagNullPartition = 0x40000000;
 std::unique_ptr<Result> execute_distinct(Segment& seg, const pg_query& q, const CancelToken* cancel);   // PG_QUERY_FLAG_DISTINCT (pg_exec.hip)
 std::unique_ptr<Result> execute_selection(Segment& seg, const pg_query& q, const CancelToken* cancel);  // PG_QUERY_FLAG_SELECTION (pg_exec.hip)
 // ---- side passes: aggregations answered by a pass of their own and joined to the ordinary plan by group key -------------------------------
-// The frame they share (pg_exec_sidepass.hip; `who` names the path in messages — "PERCENTILE" / "expression" / "variance" / "covariance" / "fourth-moment" / "FIRSTWITHTIME / LASTWITHTIME" —,
+// The frame they share (pg_exec_sidepass.hip; `who` names the path in messages — "PERCENTILE" / "expression" / "variance" / "covariance" / "fourth-moment" / "HISTOGRAM" / "FIRSTWITHTIME / LASTWITHTIME" —,
 // `subject` is how a refusal names its aggregation: "PERCENTILE" / "an aggregation over an expression" / "a variance aggregation" /
 // "FIRSTWITHTIME / LASTWITHTIME").
 bool column_has_nulls(Segment& seg, const std::string& name);   // seg.mu held
@@ -618,7 +619,7 @@ struct SidePassStats {
 // the ordinary part's columns and null vectors moved to their places in `out` (through B.base_index), `out` made the result's aggregations,
 // every statistic of the query written, the schema filled
 std::unique_ptr<Result> side_pass_finish(Segment& seg, const pg_query& q, const SideBaseQuery& B, SidePass& S, std::vector<AggResult>& out, const SidePassStats& P);
-// ---- the slot-table paths (expressions, the variance family, COVAR_POP / COVAR_SAMP, SKEWNESS / KURTOSIS, FIRSTWITHTIME / LASTWITHTIME): a table [G][slots] of 64-bit slots, filled over
+// ---- the slot-table paths (expressions, the variance family, COVAR_POP / COVAR_SAMP, SKEWNESS / KURTOSIS, HISTOGRAM, FIRSTWITHTIME / LASTWITHTIME): a table [G][slots] of 64-bit slots, filled over
 // the match words by one of three tiers (side_tier, pg_side_query.h; the kernels' half is pg_side_scan.h) and gathered for the admitted rows
 int side_pass_grid(int tier, int cus, int64_t n_words, int64_t lds_wgs_per_cu = 1);   // workgroups of a tier's pass: persistent ones in the LDS tier
 int side_flat_grid(int cus, int64_t items);                                           // ... of a kernel with one thread per item (256 per workgroup)
@@ -635,7 +636,7 @@ Column* side_argument_column(Segment& seg, const char* name, const char* fn, con
 // kernels read, without a NaN or an infinity — the sums have no digits for them
 Column* side_value_column(Segment& seg, const char* name, const char* fn, bool null_handling);
 // The columns an aggregation of ANOTHER path reads, added to `read` (a pass counts every column the query projects): a plain column name,
-// or the column arguments of a FIRSTWITHTIME / LASTWITHTIME / COVAR argument list.  COUNT(*) and a malformed list add nothing — the list's
+// the column arguments of a FIRSTWITHTIME / LASTWITHTIME / COVAR argument list, or the first argument of a HISTOGRAM's.  COUNT(*) and a malformed list add nothing — the list's
 // own path refuses it.
 void side_columns_read(const pg_agg_spec& s, std::set<std::string>& read);
 const char* agg_function_text(int32_t fn);   // "VAR_POP", "FIRSTWITHTIME", ...: the functions the side paths name in messages
@@ -651,7 +652,7 @@ struct SideTable {
 };
 SideTable side_table_plan(Segment& seg, const pg_query& q, const char* subject, const char* who, std::set<std::string>& read, int32_t slots, uint64_t lds_max_slots,
                           int bytes_per_slot, int64_t hbm_max_bytes, const char* noun, const char* knob);
-// The pass of a path that keeps a table [G][slots] of int64 sums (expressions, the variance family, covariance, SKEWNESS / KURTOSIS), from
+// The pass of a path that keeps a table [G][slots] of int64 sums (expressions, the variance family, covariance, SKEWNESS / KURTOSIS, HISTOGRAM), from
 // the query's first clock reading to its result.  A path's execute_* constructs one, plans, and then
 //   begin       runs the ordinary part and the filter (side_pass_begin), allocates the table and fills the head of the kernel arguments;
 //   accumulate  initialises the table, launches the path's kernels over the match words and gathers the admitted groups' rows, all between
@@ -745,6 +746,10 @@ std::unique_ptr<Result> execute_covariance(Segment& seg, const pg_query& q, cons
 bool is_moment_agg(const pg_agg_spec& s);
 void moment_plan_check(Segment& seg, const pg_query& q);
 std::unique_ptr<Result> execute_moment(Segment& seg, const pg_query& q, const CancelToken* cancel);
+// HISTOGRAM (pg_exec_hist.hip): one counting pass of the bins (pg_histogram.h) for all of them
+bool is_histogram_agg(const pg_agg_spec& s);
+void histogram_plan_check(Segment& seg, const pg_query& q);
+std::unique_ptr<Result> execute_histogram(Segment& seg, const pg_query& q, const CancelToken* cancel);
 std::unique_ptr<Result> execute_query_plain(Segment& seg, const pg_query& q, const CancelToken* cancel);   // ... the executor proper (pg_exec.hip)
 void fill_result_schema(Segment& seg, const pg_query& q, Result& r);
 int64_t hll_cardinality(const uint8_t* regs, int log2m);   // HyperLogLog#cardinality of one register row (pg_exec.hip)
@@ -819,6 +824,8 @@ struct Knobs {
   int64_t expr_hbm_max_bytes = (int64_t)256 << 20;   // PG_EXPR_HBM_MAX_BYTES
   int64_t var_hbm_max_bytes = (int64_t)256 << 20;    // PG_VAR_HBM_MAX_BYTES: the slot table of the variance aggregations (pg_exec_var.hip) beyond its LDS tier; larger ones are refused
   int64_t moment_hbm_max_bytes = (int64_t)256 << 20; // PG_MOMENT_HBM_MAX_BYTES: the slot table of the SKEWNESS / KURTOSIS aggregations (pg_exec_moment.hip) beyond its LDS tier; larger ones are refused
+  int64_t hist_hbm_max_bytes = (int64_t)256 << 20;   // PG_HIST_HBM_MAX_BYTES: the count table of the HISTOGRAM aggregations (pg_exec_hist.hip) beyond its LDS tier; larger ones are refused
+  int64_t hist_combine_rounds = -1;                  // PG_HIST_COMBINE_ROUNDS: distinct bins per 64-doc word pg_hist_one combines inside the wavefront (unset: the constant of pg_device.h; a measurement, tools/prof_histogram.py)
   int64_t covar_hbm_max_bytes = (int64_t)256 << 20;  // PG_COVAR_HBM_MAX_BYTES: the slot table of the covariance aggregations (pg_exec_covar.hip) beyond its LDS tier; larger ones are refused
   int64_t wt_hbm_max_bytes = (int64_t)256 << 20;     // PG_WT_HBM_MAX_BYTES: the planes of FIRSTWITHTIME / LASTWITHTIME (pg_exec_withtime.hip) beyond their LDS tier; larger ones are refused
   int64_t limit_prefix_min_docs = (int64_t)1 << 20;   // PG_LIMIT_PREFIX_MIN_DOCS: smallest doc prefix of the numGroupsLimit admission pass (tests lower it)

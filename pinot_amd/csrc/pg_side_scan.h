@@ -1,8 +1,8 @@
 // The device half of the slot-table side passes (pg_kernels_expr.hip, pg_kernels_var.hip, pg_kernels_covar.hip, pg_kernels_moment.hip,
-// pg_kernels_withtime.hip; the host half is the frame of pg_exec_sidepass.hip): the walk over the filter's match words, the reductions
+// pg_kernels_hist.hip, pg_kernels_withtime.hip; the host half is the frame of pg_exec_sidepass.hip): the walk over the filter's match words, the reductions
 // across a wavefront, the skeleton of the two tiers with a table and the launcher of the three tiers.  A family's kernels supply what is
 // theirs as callables — what a matching doc adds to its group's row, a slot's initial value, how a touched slot is flushed; the families
-// whose slots are int64 sums (the variance family, covariance, SKEWNESS / KURTOSIS) share those two in side_sum_table_pass, the addition
+// whose slots are int64 sums (the variance family, covariance, SKEWNESS / KURTOSIS, HISTOGRAM) share those two in side_sum_table_pass, the addition
 // of a digit and the load of an INT column.  Everything here is inlined into the kernels, and what they compute per doc stays in their
 // own translation unit (pg_kernels_expr.hip and pg_kernels_covar.hip keep contraction off for what they instantiate from here).
 #pragma once

@@ -437,6 +437,13 @@ class ResultsBlock:
                 api.call("result_set_values_double", h, a, values.ctypes.data, total)
                 api.call("result_set_counts", h, a, counts.ctypes.data, total)
                 rb.arrays.append((k, sizes, values[:total], counts[:total]))
+            elif k == capi.RESULT_DOUBLE_ARRAY:   # HISTOGRAM: per group the numBins counts of its DoubleArrayList
+                sizes = np.zeros(ng, dtype=np.int32)
+                api.call("result_set_sizes", h, a, sizes.ctypes.data, ng)
+                total = int(sizes.sum())
+                values = np.zeros(max(total, 1), dtype=np.float64)
+                api.call("result_set_values_double", h, a, values.ctypes.data, total)
+                rb.arrays.append((k, sizes, values[:total]))
             elif k == capi.RESULT_VARIANCE_TUPLE:   # VAR_POP / VAR_SAMP / STDDEV_POP / STDDEV_SAMP: VarianceTuple(count, sum, m2)
                 n = np.zeros(ng, dtype=np.int64)
                 s = np.zeros(ng, dtype=np.float64)
@@ -568,6 +575,12 @@ class ResultsBlock:
                     cols.append([(int(n), float(m1), float(m2), float(m3), float(m4)) for n, m1, m2, m3, m4 in zip(*arr[1:6])])
                 elif k == capi.RESULT_VALUE_TIME_PAIR:   # (value, time) per group; a FLOAT / DOUBLE value keeps its bits (NaN payloads, -0.0)
                     cols.append([(v.item(), int(t)) for v, t in zip(arr[1], arr[2])])
+                elif k == capi.RESULT_DOUBLE_ARRAY:   # a tuple of floats per group
+                    col, pos = [], 0
+                    for sz in arr[1]:
+                        col.append(tuple(float(v) for v in arr[2][pos:pos + sz]))
+                        pos += sz
+                    cols.append(col)
                 elif k == capi.RESULT_VALUE_COUNTS:   # (values, counts) per group
                     col, pos = [], 0
                     for sz in arr[1]:
@@ -732,6 +745,14 @@ def fourth_moment_merge(a, b):
     return (n, float(m1), float(m2), float(m3), float(m4))
 
 
+def histogram_merge(a, b):
+    """HistogramAggregationFunction#merge (DoubleVectorOpUtils#vectorAdd): the element-wise sum of two count arrays, what the Java side does
+    with the arrays of two segments; arrays of unequal lengths are refused, as vectorAdd's checkState refuses them."""
+    if len(a) != len(b):
+        raise ValueError(f"The two operand arrays are not of the same size! provided {len(a)}, {len(b)}")
+    return tuple(float(x) + float(y) for x, y in zip(a, b))
+
+
 def with_time_merge(function: str, a, b):
     """FirstWithTimeAggregationFunction#merge / LastWithTimeAggregationFunction#merge over two (value, time) pairs, what the Java side does
     with the pairs of two segments: LAST keeps `a` where a.time >= b.time, FIRST where a.time <= b.time — the first argument wins a tie."""
@@ -773,6 +794,8 @@ def merge_intermediate(function: str, a, b):
         return fourth_moment_merge(a, b)
     if function in capi.WITH_TIME_FUNCTIONS:
         return with_time_merge(function, a, b)
+    if function in capi.HISTOGRAM_FUNCTIONS:
+        return histogram_merge(a, b)
     raise ValueError(function)
 
 
@@ -795,6 +818,8 @@ def extract_final(function: str, v):
         return skewness_final(v) if function == "SKEWNESS" else kurtosis_final(v)
     if function in capi.WITH_TIME_FUNCTIONS:   # the pair's value
         return v[0]
+    if function in capi.HISTOGRAM_FUNCTIONS:   # the array itself (DOUBLE_ARRAY)
+        return tuple(float(x) for x in v)
     return v
 
 

@@ -137,6 +137,7 @@ class QueryContext:
             return variance_function_name(head) + paren + rest if paren and variance_function_name(head) else t
         aggs = [norm(f"{a.function}({a.column or '*'}{',' + str(a.log2m) if a.log2m else ''})") for a in self.aggregations]
         pctl = [(a.column, a.percentile) if a.function == "PERCENTILE" else None for a in self.aggregations]
+        hists = [a.column if a.function in capi.HISTOGRAM_FUNCTIONS else None for a in self.aggregations]
         expr_aggs = {}   # (function, canonical text) of the aggregations over expressions -> the first one's index
         for i, a in enumerate(self.aggregations):
             if "(" in (a.column or ""):
@@ -152,6 +153,8 @@ class QueryContext:
                 out.append((capi.ORDER_BY_AGGREGATION, aggs.index(norm(text)), asc))
             elif _percentile_of_text(text) is not None and _percentile_of_text(text) in pctl:   # any of PERCENTILE's spellings names the same aggregation
                 out.append((capi.ORDER_BY_AGGREGATION, pctl.index(_percentile_of_text(text)), asc))
+            elif _histogram_of_text(text) is not None and _histogram_of_text(text) in hists:   # a HISTOGRAM by its canonical argument list
+                out.append((capi.ORDER_BY_AGGREGATION, hists.index(_histogram_of_text(text)), asc))
             elif expr_aggs and _expression_aggregation_of_text(text) in expr_aggs:
                 # an aggregation over an expression, whatever its spelling (infix or function form): by its canonical text
                 out.append((capi.ORDER_BY_AGGREGATION, expr_aggs[_expression_aggregation_of_text(text)], asc))
@@ -171,6 +174,14 @@ def covariance_function_name(fn: str):
     """COVARPOP / COVARSAMP for any spelling of them (COVAR_POP, covarSamp), else None."""
     name = fn.replace("_", "").upper()
     return name if name in capi.COVARIANCE_FUNCTIONS else None
+
+
+def _is_number(text: str) -> bool:
+    try:
+        float(text)
+        return True
+    except ValueError:
+        return False
 
 
 def with_time_function_name(fn: str):
@@ -212,6 +223,20 @@ def _percentile_of_text(text: str):
 
 
 @functools.lru_cache(maxsize=256)
+def _histogram_of_text(text: str):
+    """The canonical argument list of an ORDER BY expression text that spells a HISTOGRAM, else None."""
+    try:
+        p = _Parser(text)
+        if not (p.kw("HISTOGRAM") and p.peek(1) == ("op", "(")):
+            return None
+        p.i += 2
+        args = p.histogram_arguments()
+    except (SqlError, IndexError):
+        return None
+    return args if p.peek()[0] == "eof" else None
+
+
+@functools.lru_cache(maxsize=256)
 def _expression_aggregation_of_text(text: str):
     """(function, canonical expression text) of an ORDER BY expression that spells an aggregation over an arithmetic expression, else None
     (parsed once per text)."""
@@ -244,7 +269,7 @@ def canonical_expression(text: str):
 # SQL subset parser
 # ----------------------------------------------------------------------------------------------------------------------
 _TOKEN = re.compile(r"\s*(?:(?P<num>-?\d+(?:\.\d+)?(?:[eE][-+]?\d+)?)|(?P<str>'(?:[^']|'')*')|(?P<id>[A-Za-z_][A-Za-z_0-9.$]*)"
-                    r"|(?P<op><=|>=|<>|!=|=|<|>|\(|\)|,|\*|\+|-|/))")
+                    r"|(?P<qid>\"[^\"]*\")|(?P<op><=|>=|<>|!=|=|<|>|\(|\)|\[|\]|,|\*|\+|-|/))")
 
 
 class SqlError(ValueError):
@@ -266,6 +291,8 @@ def _tokenize(sql: str) -> List[Tuple[str, str]]:
             out.append(("str", m.group("str")[1:-1].replace("''", "'")))
         elif m.group("id") is not None:
             out.append(("id", m.group("id")))
+        elif m.group("qid") is not None:   # a double-quoted identifier: "Infinity" / "-Infinity" among a HISTOGRAM's edges
+            out.append(("id", m.group("qid")[1:-1]))
         else:
             out.append(("op", m.group("op")))
     return out
@@ -520,6 +547,68 @@ class _Parser:
             raise SqlError(f"bad aggregation argument {e}: a literal")
         return e
 
+    def histogram_arguments(self) -> str:
+        """The canonical argument list of a HISTOGRAM, the opening parenthesis taken: "x,'lower','upper','numBins'" or
+        "x,arrayvalueconstructor('e0','e1',...)" with Infinity / -Infinity bare (identifiers, as the reference's parser hands them over).  The
+        malformed forms raise with HistogramAggregationFunction's own texts."""
+        args = [self.aggregation_argument()]
+        while self.peek() == ("op", ","):
+            self.i += 1
+            if self.kw("ARRAY") and self.peek(1) == ("op", "["):
+                self.i += 2
+                edges = []
+                while self.peek() != ("op", "]"):
+                    t = self.take()
+                    if t == ("op", "-") and self.peek() == ("id", "Infinity"):   # (an ORDER BY text spells the quoted identifier bare)
+                        t = ("id", "-" + self.take()[1])
+                    if t[0] == "id" and t[1] in ("Infinity", "-Infinity"):
+                        edges.append((t[1], float(t[1].replace("Infinity", "inf"))))
+                    elif t[0] in ("num", "str"):
+                        try:
+                            edges.append((f"'{t[1]}'", float(t[1])))
+                        except ValueError:
+                            raise SqlError(f'For input string: "{t[1]}"')
+                    else:
+                        raise SqlError(f"HISTOGRAM: bad bin edge {t}")
+                    if self.peek() == ("op", ","):
+                        self.i += 1
+                self.i += 1
+                args.append(edges)
+            else:
+                t = self.take()
+                if t[0] not in ("num", "str"):
+                    raise SqlError(f"HISTOGRAM: expected a literal, got {t}")
+                args.append(t[1])
+        self.expect_op(")")
+        if len(args) not in (2, 4):
+            raise SqlError(f"Histogram expects 2 or 4 arguments, got: {len(args)}; usage example: `Histogram(columnName, ARRAY[0,1,10,100])` to "
+                           "specify bins [0,1), [1,10), [10,1000] or `Histogram(columnName, 0, 1000, 10)` to specify 10 equal-length bins "
+                           "[0,100), [100,200), ..., [900,1000]")
+        if len(args) == 2:
+            edges = args[1]
+            if not isinstance(edges, list):
+                raise SqlError("Please use the format of `Histogram(columnName, ARRAY[1,10,100])` to specify the bin edges")
+            if len(edges) < 2:
+                raise SqlError("The number of bin edges must be greater than 1")
+            if any(not (b[1] > a[1]) for a, b in zip(edges, edges[1:])):
+                raise SqlError("The bin edges must be strictly increasing")
+            return f"{args[0]},arrayvalueconstructor({','.join(e[0] for e in edges)})"
+        if any(isinstance(a, list) for a in args[1:]):
+            raise SqlError("HISTOGRAM: the equal-width form takes three literals, not an array")
+        try:
+            lower, upper = float(args[1]), float(args[2])
+        except ValueError:
+            bad = args[1] if not _is_number(args[1]) else args[2]
+            raise SqlError(f'For input string: "{bad}"')
+        if not _is_number(args[3]) or float(args[3]) != int(float(args[3])):
+            raise SqlError(f'For input string: "{args[3]}"')
+        bins = int(float(args[3]))
+        if not upper > lower:
+            raise SqlError(f"The right most edge must be greater than left most edge, given {lower!r} and {upper!r}")
+        if bins <= 0:
+            raise SqlError(f"The number of bins must be greater than zero, given {bins}")
+        return f"{args[0]},'{args[1]}','{args[2]}','{args[3]}'"
+
     # --- select -------------------------------------------------------------------------------------------------
     def select_item(self, q: QueryContext):
         if self.peek() != ("op", "*") and self.starts_expression():   # an arithmetic expression: a DISTINCT / GROUP BY key of the select list
@@ -542,6 +631,11 @@ class _Parser:
                 args.append(self.aggregation_argument())
                 self.expect_op(")")
                 q.aggregations.append(AggregationSpec(fn, f"{args[0]},{args[1]}"))
+                if self.kw("AS"):
+                    self.i += 2
+                return
+            if fn in capi.HISTOGRAM_FUNCTIONS:   # HISTOGRAM(x, lower, upper, numBins) / HISTOGRAM(x, ARRAY[e0, e1, ...])
+                q.aggregations.append(AggregationSpec(fn, self.histogram_arguments()))
                 if self.kw("AS"):
                     self.i += 2
                 return
