@@ -315,7 +315,28 @@ typedef enum pg_agg_function {   /* AggregationFunctionType (subset named by nor
    * and one whose equal-width index rounds up to numBins (HISTOGRAM(x, 0, 1, 3) over 0.9999999999999999): nothing is clamped.  The
    * star-tree route is never taken for such a query; pg_result_merge / pg_result_all_reduce refuse its results (the Java side merges with
    * DoubleVectorOpUtils#vectorAdd). */
-  PG_AGG_HISTOGRAM = 27
+  PG_AGG_HISTOGRAM = 27,
+  /* MODE (ModeAggregationFunction.java; intermediate a map value -> count typed by the column's stored type, final value a DOUBLE) over one
+   * single-value INT / LONG / FLOAT / DOUBLE column, dictionary-encoded or raw.  pg_agg_spec.column is the argument list (the multi-argument
+   * form of FIRSTWITHTIME and HISTOGRAM; commas split at depth 0, blanks are ignored): "x" or "x,'MAX'" — the quoted MultiModeReducerType,
+   * exactly MIN, MAX or AVG (valueOf), MIN when absent.  pg_query.agg_params is not read for it.  MODE joins PERCENTILE's counting path:
+   * MODE(x) next to PERCENTILE(x, p) shares the column's counting pass, the tiers and the PG_PCTL_* knobs are PERCENTILE's.  The result is
+   * PG_RESULT_VALUE_COUNT_MAP: per group the map's entries ascending by key — counts are integers, so the map is the reference's bit for
+   * bit; a group without a value has no entry — or, with PG_QUERY_FLAG_FINAL_MODE, PG_RESULT_DOUBLE: the key of greatest count, ties
+   * resolved to the smallest key (MIN), the largest (MAX) or sum / count of the tied keys (AVG); -Infinity for an empty map.  Two points are
+   * defined rather than copied.  Key order is Double.compare's (-0.0 < 0.0, NaN greatest, one NaN): where the reference, comparing with
+   * < / >, depends on its hash map's iteration order — a tie at the greatest count that involves NaN or both zeros — MIN takes the lowest
+   * and MAX the highest key in that order.  AVG's sum is the exact sum of the tied keys as doubles, rounded once, then one IEEE division:
+   * equal to the reference whenever its running sum is exact (always for INT columns).  The result column's name is mode(x).
+   * PG_ERR_INVALID_ARGUMENT with the reference's message where it has one: more than 2 arguments ("Mode expects at most 2 arguments, got:
+   * 3"), an unknown or unquoted reducer ("No enum constant ...MultiModeReducerType.avg"), a malformed list.  PG_ERR_NOT_FOUND: an unknown
+   * column.  Refused (PG_ERR_UNSUPPORTED, the Java plan answers), as for PERCENTILE and each naming MODE: a STRING / BYTES or multi-value
+   * x, an expression x, a multi-value group-by column next to it, under PG_QUERY_FLAG_NULL_HANDLING an x or group-by column that holds
+   * nulls (the reference's null final for an empty map included), a group key space over 2^32, and from pg_query_exec alone a sort work
+   * area over PG_PCTL_SORT_MAX_BYTES.  The star-tree route is never taken for such a query and an ORDER BY naming a MODE leaves the segment
+   * untrimmed; pg_result_merge / pg_result_all_reduce refuse its results (the Java side merges the maps by value: the per-key sum of
+   * ModeAggregationFunction#merge); pg_result_data_table refuses a result executed with PG_QUERY_FLAG_FINAL_MODE. */
+  PG_AGG_MODE = 28
 } pg_agg_function;
 
 typedef struct pg_agg_spec {
@@ -463,6 +484,9 @@ typedef struct pg_query {
 /* PERCENTILE aggregations come back as their FINAL value (PG_RESULT_DOUBLE: extractFinalResult), not as (value, count) runs: only one double
    per group and aggregation crosses PCIe.  For a caller that merges nothing afterwards. */
 #define PG_QUERY_FLAG_FINAL_PERCENTILE 0x200
+/* MODE aggregations come back as their final double (PG_RESULT_DOUBLE, one per group) instead of the map; governs MODE only, as
+ * PG_QUERY_FLAG_FINAL_PERCENTILE governs PERCENTILE only */
+#define PG_QUERY_FLAG_FINAL_MODE 0x400
 #define PG_QUERY_FLAG_KEEP_DEVICE_TABLE 0x4 /* keep the dense accumulator table in HBM with the result (pg_result_merge / _all_reduce) */
 
 /* ExecutionStatistics (pinot-core/.../operator/ExecutionStatistics.java) + device timings. */
@@ -511,6 +535,10 @@ typedef enum pg_result_kind {
                               (components 2 and 3 exist for this kind; 2 also for PG_RESULT_COVARIANCE_TUPLE) */
   PG_RESULT_DOUBLE_ARRAY = 12, /* HISTOGRAM: the group's DoubleArrayList of counts — pg_result_set_sizes gives numBins for every group,
                               pg_result_set_values_double the counts, group-major */
+  PG_RESULT_VALUE_COUNT_MAP = 13, /* MODE: the group's map value -> count — pg_result_set_sizes gives the entries per group, pg_result_set_values_long
+                              the keys of an INT / LONG column, exactly, pg_result_set_values_double the keys of a FLOAT / DOUBLE column (a FLOAT
+                              widened exactly; the other getter returns PG_ERR_INVALID_ARGUMENT, as for PG_RESULT_VALUE_SET), pg_result_set_counts the
+                              counts; entries ascending by key (Double.compare order) within a group */
   PG_RESULT_VALUE_COUNTS = 7 /* PERCENTILE: the group's DoubleArrayList as runs — pg_result_set_sizes gives the runs per group, pg_result_set_values_double
                               the runs' values (ascending under Double.compare within a group), pg_result_set_counts how often each occurs */
 } pg_result_kind;

@@ -318,6 +318,8 @@ public class GpuGroupByOperator extends BaseOperator<BaseResultsBlock> {
         return GpuResultObjects.varianceTuples(result, a, n);                    // (count, sum, m2) -> VarianceTuple, the holder's value and the intermediate alike (VarianceAggregationFunction.java:66-74)
       case PinotGpu.RESULT_COVARIANCE_TUPLE:
         return GpuResultObjects.covarianceTuples(result, a, n);                  // (sumX, sumY, sumXY, count) -> CovarianceTuple, the holder's value and the intermediate alike (CovarianceAggregationFunction.java:112-130)
+      case PinotGpu.RESULT_VALUE_COUNT_MAP:
+        return GpuResultObjects.modeMaps(result, a, n, _segment, function);      // (key, count) entries -> Int2Long / Long2Long / Float2Long / Double2LongOpenHashMap (ModeAggregationFunction)
       case PinotGpu.RESULT_DOUBLE_ARRAY:
         return GpuResultObjects.countArrays(result, a, n);                       // numBins counts -> DoubleArrayList, the holder's value and the intermediate alike (HistogramAggregationFunction)
       case PinotGpu.RESULT_FOURTH_MOMENT:

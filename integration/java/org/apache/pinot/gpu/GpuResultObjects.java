@@ -242,6 +242,80 @@ public final class GpuResultObjects {
     return out;
   }
 
+  /** MODE (pg_result_kind PG_RESULT_VALUE_COUNT_MAP): per group the function's map value -> count, typed by the column's stored type as
+   *  ModeAggregationFunction types it — Int2LongOpenHashMap / Long2LongOpenHashMap / Float2LongOpenHashMap / Double2LongOpenHashMap; a group
+   *  without a value gets the empty Int2LongOpenHashMap, whatever the column.  INT / LONG keys arrive exactly (resultSetValuesLong), FLOAT /
+   *  DOUBLE keys as doubles (resultSetValuesDouble, a FLOAT widened exactly).  Maps of several segments merge by the per-key sum
+   *  (ModeAggregationFunction#merge), as the reference's own do. */
+  public static Object[] modeMaps(long result, int aggregation, int numGroups, IndexSegment segment, AggregationFunction function) {
+    String column = ((ExpressionContext) function.getInputExpressions().get(0)).getIdentifier();
+    DataType stored = segment.getDataSource(column).getDataSourceMetadata().getDataType().getStoredType();
+    int[] sizes = new int[numGroups];
+    PinotGpu.resultSetSizes(result, aggregation, sizes);
+    long total = 0;
+    for (int s : sizes) {
+      total += s;
+    }
+    if (total > Integer.MAX_VALUE - 8) {
+      throw new UnsupportedOperationException("MODE state of " + total + " entries exceeds one Java array");
+    }
+    boolean floating = stored == DataType.FLOAT || stored == DataType.DOUBLE;
+    long[] longs = new long[floating ? 0 : (int) total];
+    double[] doubles = new double[floating ? (int) total : 0];
+    if (floating) {
+      PinotGpu.resultSetValuesDouble(result, aggregation, doubles);
+    } else {
+      PinotGpu.resultSetValuesLong(result, aggregation, longs);
+    }
+    long[] counts = new long[(int) total];
+    PinotGpu.resultSetCounts(result, aggregation, counts);
+    Object[] out = new Object[numGroups];
+    int at = 0;
+    for (int g = 0; g < numGroups; g++) {
+      int n = sizes[g];
+      if (n == 0) {
+        out[g] = new it.unimi.dsi.fastutil.ints.Int2LongOpenHashMap();
+        continue;
+      }
+      switch (stored) {
+        case INT: {
+          it.unimi.dsi.fastutil.ints.Int2LongOpenHashMap m = new it.unimi.dsi.fastutil.ints.Int2LongOpenHashMap(n);
+          for (int e = at; e < at + n; e++) {
+            m.put((int) longs[e], counts[e]);
+          }
+          out[g] = m;
+          break;
+        }
+        case LONG: {
+          it.unimi.dsi.fastutil.longs.Long2LongOpenHashMap m = new it.unimi.dsi.fastutil.longs.Long2LongOpenHashMap(n);
+          for (int e = at; e < at + n; e++) {
+            m.put(longs[e], counts[e]);
+          }
+          out[g] = m;
+          break;
+        }
+        case FLOAT: {
+          it.unimi.dsi.fastutil.floats.Float2LongOpenHashMap m = new it.unimi.dsi.fastutil.floats.Float2LongOpenHashMap(n);
+          for (int e = at; e < at + n; e++) {
+            m.put((float) doubles[e], counts[e]);
+          }
+          out[g] = m;
+          break;
+        }
+        default: {
+          it.unimi.dsi.fastutil.doubles.Double2LongOpenHashMap m = new it.unimi.dsi.fastutil.doubles.Double2LongOpenHashMap(n);
+          for (int e = at; e < at + n; e++) {
+            m.put(doubles[e], counts[e]);
+          }
+          out[g] = m;
+          break;
+        }
+      }
+      at += n;
+    }
+    return out;
+  }
+
   /** HISTOGRAM (pg_result_kind PG_RESULT_DOUBLE_ARRAY): per group the function's DoubleArrayList of numBins counts, as the library counted
    *  them.  Arrays of several segments merge with DoubleVectorOpUtils#vectorAdd (HistogramAggregationFunction#merge), as the reference's
    *  own do. */

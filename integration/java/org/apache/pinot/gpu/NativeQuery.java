@@ -121,6 +121,15 @@ public final class NativeQuery implements AutoCloseable {
         putString(b, list);
         continue;
       }
+      if (fn == 28) {   // PG_AGG_MODE: the argument list "x" / "x,'MAX'" in pg_agg_spec.column
+        String list = modeArguments(q, f);
+        if (list == null) {
+          return null;
+        }
+        b.putInt(fn).putInt(0);
+        putString(b, list);
+        continue;
+      }
       if (fn < 0 || args.size() > 1) {
         return null;
       }
@@ -338,6 +347,31 @@ public final class NativeQuery implements AutoCloseable {
     return null;
   }
 
+  /** MODE: the argument list as the query spells it.  The function keeps its reducer to itself (no accessor), so it is read where the
+   *  function read it: the FunctionContext of the query's aggregation — the column, then the MultiModeReducerType literal as
+   *  ExpressionContext#toString prints it ('MAX').  Null for an argument that is no column, a filtered aggregation, a second argument that
+   *  is no literal, or more than two arguments (the Java plan answers, with the reference's own errors). */
+  private static String modeArguments(QueryContext q, AggregationFunction f) {
+    for (java.util.Map.Entry<org.apache.commons.lang3.tuple.Pair<org.apache.pinot.common.request.context.FunctionContext,
+        org.apache.pinot.common.request.context.FilterContext>, Integer> e : q.getFilteredAggregationsIndexMap().entrySet()) {
+      if (q.getAggregationFunctions()[e.getValue()] != f) {
+        continue;
+      }
+      List<ExpressionContext> args = e.getKey().getLeft().getArguments();
+      if (e.getKey().getRight() != null || args.isEmpty() || args.size() > 2 || args.get(0).getType() != ExpressionContext.Type.IDENTIFIER) {
+        return null;
+      }
+      if (args.size() == 1) {
+        return args.get(0).getIdentifier();
+      }
+      if (args.get(1).getType() != ExpressionContext.Type.LITERAL) {
+        return null;
+      }
+      return args.get(0).getIdentifier() + "," + args.get(1).toString();
+    }
+    return null;
+  }
+
   private static String withTimeType(AggregationFunction f) {
     if (f instanceof org.apache.pinot.core.query.aggregation.function.FirstIntValueWithTimeAggregationFunction
         || f instanceof org.apache.pinot.core.query.aggregation.function.LastIntValueWithTimeAggregationFunction) {
@@ -394,6 +428,8 @@ public final class NativeQuery implements AutoCloseable {
       case SKEWNESS: return f instanceof org.apache.pinot.core.query.aggregation.function.FourthMomentAggregationFunction ? 25 : -1;
       case KURTOSIS: return f instanceof org.apache.pinot.core.query.aggregation.function.FourthMomentAggregationFunction ? 26 : -1;
       // the bin counts (pg_agg_function 27): intermediate and final value the same DoubleArrayList
+      // the map value -> count (pg_agg_function 28); the reducer travels in the argument list
+      case MODE: return f instanceof org.apache.pinot.core.query.aggregation.function.ModeAggregationFunction ? 28 : -1;
       case HISTOGRAM: return f instanceof org.apache.pinot.core.query.aggregation.function.HistogramAggregationFunction ? 27 : -1;
       case FIRSTWITHTIME:
         return f instanceof org.apache.pinot.core.query.aggregation.function.FirstWithTimeAggregationFunction && withTimeType(f) != null ? 21 : -1;

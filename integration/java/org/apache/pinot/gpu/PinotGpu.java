@@ -24,6 +24,7 @@ public final class PinotGpu {
       RESULT_HLL = 5, RESULT_VALUE_SET = 6, RESULT_VALUE_COUNTS = 7,
       RESULT_VALUE_TIME_PAIR = 9,   // FIRSTWITHTIME / LASTWITHTIME: resultLongs(.., 0) the time, resultLongs(.., 1) an INT / LONG value, resultDoubles(.., 0) a FLOAT / DOUBLE value
       RESULT_VARIANCE_TUPLE = 8,   // VAR_POP / VAR_SAMP / STDDEV_POP / STDDEV_SAMP: resultLongs(.., 0) the count, resultDoubles(.., 0) the sum, resultDoubles(.., 1) m2
+      RESULT_VALUE_COUNT_MAP = 13,   // MODE: resultSetSizes(..) entries per group, resultSetValuesLong(..) INT / LONG keys or resultSetValuesDouble(..) FLOAT / DOUBLE keys, resultSetCounts(..) the counts
       RESULT_DOUBLE_ARRAY = 12,   // HISTOGRAM: resultSetSizes(..) numBins for every group, resultSetValuesDouble(..) the counts, group-major
       RESULT_FOURTH_MOMENT = 11,   // SKEWNESS / KURTOSIS: resultLongs(.., 0) n, resultDoubles(.., 0 .. 3) m1 .. m4
       RESULT_COVARIANCE_TUPLE = 10;   // COVAR_POP / COVAR_SAMP: resultDoubles(.., 0) sumX, (.., 1) sumY, (.., 2) sumXY, resultLongs(.., 0) the count
@@ -88,6 +89,7 @@ public final class PinotGpu {
   public static final int QUERY_FLAG_SKIP_STAR_TREE = 0x2, QUERY_FLAG_KEEP_DEVICE_TABLE = 0x4, QUERY_FLAG_APPROX_FILTER_STATS = 0x8,
       QUERY_FLAG_EXACT_FILTER_STATS = 0x10, QUERY_FLAG_FINAL_DISTINCT = 0x20, QUERY_FLAG_NULL_HANDLING = 0x40,
       QUERY_FLAG_DISTINCT = 0x80, QUERY_FLAG_SELECTION = 0x100,
+      QUERY_FLAG_FINAL_MODE = 0x400,   // MODE aggregations come back as their final double (RESULT_DOUBLE)
       QUERY_FLAG_FINAL_PERCENTILE = 0x200;   // PERCENTILE aggregations come back as their final double (RESULT_DOUBLE)
   public static final int COMM_UNIQUE_ID_BYTES = 128;
   public static native void resultMerge(long dst, long src);                 // same device

@@ -41,8 +41,15 @@ AGG_FUNCTIONS = {"COUNT": 0, "SUM": 1, "MIN": 2, "MAX": 3, "AVG": 4, "DISTINCTCO
                  "VARPOP": 17, "VARSAMP": 18, "STDDEVPOP": 19, "STDDEVSAMP": 20,
                  "FIRSTWITHTIME": 21, "LASTWITHTIME": 22, "COVARPOP": 23, "COVARSAMP": 24,
                  "SKEWNESS": 25, "KURTOSIS": 26, "HISTOGRAM": 27}
+# AGG_FUNCTIONS holds the functions with a side path or an ordinary plan of their own (ids 0 .. 27; tests/test_histogram_query.py pins its
+# size).  MODE has none: it rides PERCENTILE's counting path.  AGG_FUNCTION_IDS is every function the ABI carries — what the parser and
+# CQuery look a name up in.
+PG_AGG_MODE = 28
+AGG_FUNCTION_IDS = dict(AGG_FUNCTIONS, MODE=PG_AGG_MODE)
 WITH_TIME_FUNCTIONS = ("FIRSTWITHTIME", "LASTWITHTIME")   # their AggregationSpec.column is the argument list "x,t,'TYPE'" (include/pinot_gpu.h)
 COVARIANCE_FUNCTIONS = ("COVARPOP", "COVARSAMP")   # CovarianceAggregationFunction: one intermediate, two final values; AggregationSpec.column is the argument list "x,y"
+MODE_FUNCTIONS = ("MODE",)   # ModeAggregationFunction: AggregationSpec.column is the argument list "x" or "x,'MAX'" (the MultiModeReducerType: MIN, MAX or AVG)
+MODE_REDUCERS = ("MIN", "MAX", "AVG")
 HISTOGRAM_FUNCTIONS = ("HISTOGRAM",)   # HistogramAggregationFunction: AggregationSpec.column is the argument list "x,'lower','upper','numBins'" or "x,arrayvalueconstructor(e0,e1,...)"
 FOURTH_MOMENT_FUNCTIONS = ("SKEWNESS", "KURTOSIS")   # FourthMomentAggregationFunction: one intermediate (PinotFourthMoment), two final values
 WITH_TIME_TYPES = ("INT", "LONG", "FLOAT", "DOUBLE")      # the declared types the GPU path runs
@@ -52,6 +59,7 @@ MV_TO_SV_FUNCTION = {"COUNTMV": "COUNT", "SUMMV": "SUM", "MINMV": "MIN", "MAXMV"
 RESULT_LONG, RESULT_DOUBLE, RESULT_AVG_PAIR, RESULT_MINMAX_PAIR, RESULT_DICTID_SET, RESULT_HLL, RESULT_VALUE_SET, RESULT_VALUE_COUNTS = range(8)
 RESULT_VALUE_TIME_PAIR = 9   # ValueLongPair: result_longs(.., 0) the time, result_longs(.., 1) an INT / LONG value, result_doubles(.., 0) a FLOAT / DOUBLE value
 RESULT_COVARIANCE_TUPLE = 10   # CovarianceTuple: result_doubles(.., 0) sumX, (.., 1) sumY, (.., 2) sumXY, result_longs(.., 0) the count
+RESULT_VALUE_COUNT_MAP = 13   # MODE's map value -> count: result_set_sizes entries per group, result_set_values_long (INT / LONG keys) or result_set_values_double (FLOAT / DOUBLE), result_set_counts
 RESULT_DOUBLE_ARRAY = 12   # HISTOGRAM's DoubleArrayList: result_set_sizes numBins per group, result_set_values_double the counts, group-major
 RESULT_FOURTH_MOMENT = 11   # PinotFourthMoment: result_longs(.., 0) n, result_doubles(.., 0 .. 3) m1 .. m4
 RESULT_VARIANCE_TUPLE = 8   # VarianceTuple: result_longs(.., 0) the count, result_doubles(.., 0) the sum, result_doubles(.., 1) m2
@@ -65,6 +73,7 @@ QUERY_FLAG_FINAL_DISTINCT = 0x20
 QUERY_FLAG_NULL_HANDLING = 0x40
 QUERY_FLAG_DISTINCT = 0x80   # SELECT DISTINCT: group_by_columns are the DISTINCT columns, no aggregation
 QUERY_FLAG_SELECTION = 0x100   # SELECT cols | * ... [ORDER BY] LIMIT n: group_by_columns are the output columns (extractExpressions order)
+QUERY_FLAG_FINAL_MODE = 0x400   # MODE aggregations come back as their final double, not as their map
 QUERY_FLAG_FINAL_PERCENTILE = 0x200   # PERCENTILE aggregations come back as their final double, not as (value, count) runs
 LIMIT_UNBOUNDED = 2**31 - 1   # DISTINCT ... LIMIT Integer.MAX_VALUE: every tuple
 COMM_UNIQUE_ID_BYTES = 128

@@ -43,6 +43,7 @@ static void knobs_read(Knobs& k) {
   k.pctl_lds_max_keys = std::max<int64_t>(1, std::min<int64_t>(32768, num("PG_PCTL_LDS_MAX_KEYS", 32768)));
   k.pctl_hbm_max_bytes = std::max<int64_t>(4, num("PG_PCTL_HBM_MAX_BYTES", (int64_t)256 << 20));
   k.pctl_sort_max_bytes = num("PG_PCTL_SORT_MAX_BYTES", (int64_t)8 << 30);
+  k.mode_split_ids = std::max<int64_t>(64, num("PG_MODE_SPLIT_IDS", 1024));
   k.expr_lds_max_slots = std::max<int64_t>(1, std::min<int64_t>(PG_EXPR_LDS_SLOTS, num("PG_EXPR_LDS_MAX_SLOTS", PG_EXPR_LDS_SLOTS)));
   k.expr_hbm_max_bytes = std::max<int64_t>(8, num("PG_EXPR_HBM_MAX_BYTES", (int64_t)256 << 20));
   k.var_hbm_max_bytes = std::max<int64_t>(8, num("PG_VAR_HBM_MAX_BYTES", (int64_t)256 << 20));
@@ -324,6 +325,9 @@ static void refuse_merged_elsewhere(uint32_t kinds) {
       {MERGED_HISTOGRAM, "results of HISTOGRAM aggregations are merged on the Java side (DoubleVectorOpUtils#vectorAdd)"},
   };
   for (const auto& r : kRefusals) if (kinds & r.bit) fail(PG_ERR_UNSUPPORTED, "%s", r.text);
+  // (one entry per side path above; the counting path carries a second family, whose maps merge as its lists do: by value)
+  if (kinds & MERGED_MODE)
+    fail(PG_ERR_UNSUPPORTED, "results of MODE aggregations are merged by value on the Java side (the per-key sum of ModeAggregationFunction#merge)");
 }
 
 int32_t pg_result_merge(pg_result_t dst, pg_result_t src) {
@@ -469,7 +473,8 @@ int32_t pg_result_longs(pg_result_t result, int32_t agg, int32_t component, int6
 int32_t pg_result_set_sizes(pg_result_t result, int32_t agg, int32_t* out_sizes, int32_t capacity) {
   return guarded([&] {
     AggResult& a = agg_of(result, agg);
-    REQUIRE(a.kind == PG_RESULT_DICTID_SET || a.kind == PG_RESULT_VALUE_SET || a.kind == PG_RESULT_VALUE_COUNTS || a.kind == PG_RESULT_DOUBLE_ARRAY, "aggregation is not a DISTINCTCOUNT, PERCENTILE or HISTOGRAM");
+    REQUIRE(a.kind == PG_RESULT_DICTID_SET || a.kind == PG_RESULT_VALUE_SET || a.kind == PG_RESULT_VALUE_COUNTS || a.kind == PG_RESULT_DOUBLE_ARRAY || a.kind == PG_RESULT_VALUE_COUNT_MAP,
+            "aggregation is not a DISTINCTCOUNT, PERCENTILE, HISTOGRAM or MODE");
     REQUIRE(capacity >= result->r->num_groups, "capacity too small");
     if (!a.set_sizes.empty()) memcpy(out_sizes, a.set_sizes.data(), a.set_sizes.size() * 4);
   });
@@ -485,15 +490,17 @@ int32_t pg_result_set_dict_ids(pg_result_t result, int32_t agg, int32_t* out_dic
 int32_t pg_result_set_values_long(pg_result_t result, int32_t agg, int64_t* out_values, int64_t capacity) {
   return guarded([&] {
     AggResult& a = agg_of(result, agg);
-    REQUIRE(a.kind == PG_RESULT_VALUE_SET && a.set_value_kind <= 1, "aggregation is not a DISTINCTCOUNT over a raw INT / LONG column");
-    REQUIRE(capacity >= (int64_t)a.l[0].size(), "capacity too small");
-    if (!a.l[0].empty()) memcpy(out_values, a.l[0].data(), a.l[0].size() * 8);
+    REQUIRE((a.kind == PG_RESULT_VALUE_SET || a.kind == PG_RESULT_VALUE_COUNT_MAP) && a.set_value_kind <= 1, "aggregation is not a DISTINCTCOUNT over a raw INT / LONG column or a MODE over an INT / LONG column");
+    const std::vector<int64_t>& keys = a.l[a.kind == PG_RESULT_VALUE_COUNT_MAP ? 1 : 0];   // (a MODE's l[0] holds its counts)
+    REQUIRE(capacity >= (int64_t)keys.size(), "capacity too small");
+    if (!keys.empty()) memcpy(out_values, keys.data(), keys.size() * 8);
   });
 }
 int32_t pg_result_set_values_double(pg_result_t result, int32_t agg, double* out_values, int64_t capacity) {
   return guarded([&] {
     AggResult& a = agg_of(result, agg);
-    REQUIRE((a.kind == PG_RESULT_VALUE_SET && a.set_value_kind >= 2) || a.kind == PG_RESULT_VALUE_COUNTS || a.kind == PG_RESULT_DOUBLE_ARRAY, "aggregation is not a DISTINCTCOUNT over a raw FLOAT / DOUBLE column, a PERCENTILE or a HISTOGRAM");
+    REQUIRE(((a.kind == PG_RESULT_VALUE_SET || a.kind == PG_RESULT_VALUE_COUNT_MAP) && a.set_value_kind >= 2) || a.kind == PG_RESULT_VALUE_COUNTS || a.kind == PG_RESULT_DOUBLE_ARRAY,
+            "aggregation is not a DISTINCTCOUNT over a raw FLOAT / DOUBLE column, a PERCENTILE, a HISTOGRAM or a MODE over a FLOAT / DOUBLE column");
     REQUIRE(capacity >= (int64_t)a.d[0].size(), "capacity too small");
     if (!a.d[0].empty()) memcpy(out_values, a.d[0].data(), a.d[0].size() * 8);
   });
@@ -501,7 +508,7 @@ int32_t pg_result_set_values_double(pg_result_t result, int32_t agg, double* out
 int32_t pg_result_set_counts(pg_result_t result, int32_t agg, int64_t* out_counts, int64_t capacity) {
   return guarded([&] {
     AggResult& a = agg_of(result, agg);
-    REQUIRE(a.kind == PG_RESULT_VALUE_COUNTS, "aggregation is not a PERCENTILE");
+    REQUIRE(a.kind == PG_RESULT_VALUE_COUNTS || a.kind == PG_RESULT_VALUE_COUNT_MAP, "aggregation is not a PERCENTILE or a MODE");
     REQUIRE(capacity >= (int64_t)a.l[0].size(), "capacity too small");
     if (!a.l[0].empty()) memcpy(out_counts, a.l[0].data(), a.l[0].size() * 8);
   });

@@ -86,6 +86,7 @@ const char* function_name(int32_t fn) {   // AggregationFunctionType#getName().t
     case PG_AGG_STDDEVSAMP: return "stddevsamp";
     case PG_AGG_SKEWNESS: return "skewness";
     case PG_AGG_KURTOSIS: return "kurtosis";
+    case PG_AGG_MODE: return "mode";   // getResultColumnName: "mode(" + the first argument + ")"; the reducer is not part of the name
     case PG_AGG_HISTOGRAM: return "histogram";   // getResultColumnName: "histogram(" + the first argument + ")"; the bins are not part of the name
     case PG_AGG_COVARPOP: return "covarpop";   // getResultColumnName: the lower-case name + "(" + the arguments joined by "," + ")"
     case PG_AGG_COVARSAMP: return "covarsamp";
@@ -157,7 +158,9 @@ std::vector<uint8_t> result_data_table_v4(const Result& r) {
     std::string arguments = c.name;
     if (c.function == PG_AGG_COVARPOP || c.function == PG_AGG_COVARSAMP)   // the argument list without its blanks: "covarpop(x,y)"
       arguments.erase(std::remove_if(arguments.begin(), arguments.end(), [](char ch) { return ch == ' ' || ch == '\t' || ch == '\n' || ch == '\r'; }), arguments.end());
-    if (c.function == PG_AGG_HISTOGRAM) {   // the first argument alone: up to the first comma (x is a column), without blanks
+    if (c.function == PG_AGG_MODE && r.aggs[(size_t)a].kind != PG_RESULT_VALUE_COUNT_MAP)
+      fail(PG_ERR_INVALID_ARGUMENT, "final MODE values (PG_QUERY_FLAG_FINAL_MODE) are not intermediate results: no data table");
+    if (c.function == PG_AGG_HISTOGRAM || c.function == PG_AGG_MODE) {   // the first argument alone: up to the first comma (x is a column), without blanks
       arguments = arguments.substr(0, arguments.find(','));
       arguments.erase(std::remove_if(arguments.begin(), arguments.end(), [](char ch) { return ch == ' ' || ch == '\t' || ch == '\n' || ch == '\r'; }), arguments.end());
     }
@@ -328,6 +331,25 @@ std::vector<uint8_t> result_data_table_v4(const Result& r) {
           p.i32((int32_t)total);
           for (int32_t e = 0; e < n; e++) for (int64_t k = 0; k < ar.l[0][at + (size_t)e]; k++) p.f64(ar.d[0][at + (size_t)e]);
           object(3, p);
+          break;
+        }
+        case PG_RESULT_VALUE_COUNT_MAP: {   // MODE: Int2LongMap / Long2LongMap / Float2LongMap / Double2LongMap (ObjectSerDeUtils types 23 .. 26): int size,
+          // then (key in its own width, long count) entries, ascending by key; an empty map is the Int2LongOpenHashMap whatever the column
+          const int32_t n = ar.set_sizes[(size_t)i];
+          const size_t at = set_pos[(size_t)a];
+          set_pos[(size_t)a] += n;
+          Out p;
+          p.i32(n);
+          for (int32_t e = 0; e < n; e++) {
+            switch (ar.set_value_kind) {
+              case 0: p.i32((int32_t)ar.l[1][at + (size_t)e]); break;
+              case 1: p.i64(ar.l[1][at + (size_t)e]); break;
+              case 2: { const float f = (float)ar.d[0][at + (size_t)e]; int32_t b; memcpy(&b, &f, 4); p.i32(b); break; }
+              default: p.f64(ar.d[0][at + (size_t)e]); break;
+            }
+            p.i64(ar.l[0][at + (size_t)e]);
+          }
+          object(n == 0 ? 23 : 23 + std::min(std::max(ar.set_value_kind, 0), 3), p);
           break;
         }
         case PG_RESULT_DOUBLE_ARRAY: {   // HISTOGRAM: the DoubleArrayList of numBins counts (ObjectSerDeUtils type 3, as PERCENTILE's list)

@@ -557,6 +557,36 @@ struct PgPctlSelectArgs {
   int32_t* sel;                // [n_rows][n_p] the selected value id, -1 for an empty row
 };
 
+// ---- MODE (pg_kernels_mode.hip): the most frequent ids of the counting pass's rows ----------------------------------------------------------
+// What the selection delivers per row — and per share of a row that several wavefronts walk: the same record, combined by pg_mode_finish.
+#include "pg_mode.h"
+struct PgModeRow {
+  uint64_t n;                  // values in the row (the sum of its counters)
+  uint32_t nnz;                // non-zero counters
+  uint32_t pad;
+  pg_mode_partial p;           // (max_count, n_tied, lowest tied id, highest tied id), pg_mode.h
+};
+#define PG_MODE_MAX_SHARES 4096   // wavefronts over one row
+struct PgModeSelectArgs {
+  const uint32_t* table;
+  const uint32_t* rows;        // [n_rows] group keys (row r of the table starts at rows[r] x card)
+  int32_t n_rows;
+  uint32_t card;
+  uint32_t shares;             // wavefronts per row (1: one wavefront walks its row alone and `out` is final)
+  uint32_t share_ids;          // ids per share, a multiple of 64; shares x share_ids >= card
+  PgModeRow* out;              // [n_rows][shares]
+};
+struct PgModeSortSelectArgs {
+  const uint64_t* run_keys;    // [n_runs] distinct keys, ascending
+  const uint32_t* run_counts;  // [n_runs]
+  int64_t n_runs;
+  const uint32_t* rows;        // [n_rows] group keys
+  int32_t n_rows;
+  uint32_t card;
+  PgModeRow* out;              // [n_rows]
+  int64_t* first_run;          // [n_rows] index of the row's first run
+};
+
 // Selection queries (pg_kernels_select.hip): the ORDER BY columns of a doc folded into one 64-bit order-space key (the K smallest keys are
 // the top K rows), then the output columns gathered at the rows' docIds.
 #define PG_SELECT_LDS_MAX_K 1024   // the streaming top-K keeps up to this many rows per wavefront in LDS; beyond it the matches are sorted

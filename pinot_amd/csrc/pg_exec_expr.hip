@@ -188,8 +188,9 @@ double order_key_to_double(int64_t k) {
 
 }  // namespace
 
-// (a HISTOGRAM's argument list holds parentheses of its own — arrayvalueconstructor(...) —: its path looks at the first argument itself)
-bool is_expression_agg(const pg_agg_spec& s) { return s.function != PG_AGG_HISTOGRAM && expr_is_expression(s.column); }
+// (a HISTOGRAM's argument list holds parentheses of its own — arrayvalueconstructor(...) —: its path looks at the first argument itself; a
+// MODE over an expression is refused by the counting path, in its own words)
+bool is_expression_agg(const pg_agg_spec& s) { return s.function != PG_AGG_HISTOGRAM && s.function != PG_AGG_MODE && expr_is_expression(s.column); }
 void expression_plan_check(Segment& seg, const pg_query& q) { (void)expr_plan(seg, q, false); }
 
 std::unique_ptr<Result> execute_expression(Segment& seg, const pg_query& q, const CancelToken* cancel) {

@@ -1,5 +1,5 @@
 // The frame of the side passes: aggregations answered by a pass of their own and joined to the ordinary plan by group key (exact PERCENTILE:
-// pg_exec_percentile.hip; aggregations over an expression: pg_exec_expr.hip; the variance family: pg_exec_var.hip; COVAR_POP / COVAR_SAMP: pg_exec_covar.hip; SKEWNESS / KURTOSIS: pg_exec_moment.hip; HISTOGRAM: pg_exec_hist.hip; FIRSTWITHTIME / LASTWITHTIME: pg_exec_withtime.hip).
+// and MODE: pg_exec_percentile.hip; aggregations over an expression: pg_exec_expr.hip; the variance family: pg_exec_var.hip; COVAR_POP / COVAR_SAMP: pg_exec_covar.hip; SKEWNESS / KURTOSIS: pg_exec_moment.hip; HISTOGRAM: pg_exec_hist.hip; FIRSTWITHTIME / LASTWITHTIME: pg_exec_withtime.hip).
 // The paths are the entries of kSidePaths below, in nesting order; side_path_of, side_check and execute_query (pg_nullaware.cpp) follow that list.  A path plans its aggregations and its group-by
 // columns (side_groups, side_argument_column; side_columns_read for what the other paths' aggregations read), splits the query
 // (side_base_query), and then
@@ -130,8 +130,8 @@ SideGroups side_groups(Segment& seg, const pg_query& q, const char* subject, con
 // part comes back through execute_query and meets the next.
 // the ordinary part may hold a PERCENTILE, which reads PG_QUERY_FLAG_FINAL_PERCENTILE; it does not keep its table (the result is not merged in the library)
 constexpr int32_t kSideBaseClears = PG_QUERY_FLAG_KEEP_DEVICE_TABLE;
-// the PERCENTILE's ordinary part holds none: it neither keeps its table (the result is not merged in the library) nor reads the final-form flag
-constexpr int32_t kPercentileBaseClears = PG_QUERY_FLAG_FINAL_PERCENTILE | PG_QUERY_FLAG_KEEP_DEVICE_TABLE;
+// the counting path's ordinary part holds neither a PERCENTILE nor a MODE: it neither keeps its table (the result is not merged in the library) nor reads the final-form flags
+constexpr int32_t kPercentileBaseClears = PG_QUERY_FLAG_FINAL_PERCENTILE | PG_QUERY_FLAG_FINAL_MODE | PG_QUERY_FLAG_KEEP_DEVICE_TABLE;
 const SidePath kSidePaths[] = {
     // aggregations over expressions: before the PERCENTILE, so that the expression pass is the outer one of a query that carries both — its
     // statistics count the operand columns, and its ordinary part (PERCENTILEs included) comes back through execute_query
@@ -146,7 +146,9 @@ const SidePath kSidePaths[] = {
     {is_histogram_agg, histogram_plan_check, execute_histogram, kSideBaseClears},
     // inside the expression pass, outside the PERCENTILE's: its ordinary part comes back through execute_query
     {is_variance_agg, variance_plan_check, execute_variance, kSideBaseClears},
-    // its ordinary part comes back through execute_query; nulls in its columns are refused (percentile_plan_check)
+    // the counting path, PERCENTILE or MODE (is_percentile_agg), innermost: its ordinary part comes back through execute_query; nulls in its
+    // columns are refused (percentile_plan_check).  MODE has no entry of its own: its intermediate is the table the PERCENTILE's counting
+    // pass builds, so MODE(x) next to PERCENTILE(x, p) shares one pass, and next to a HISTOGRAM, a variance or an expression it nests as a PERCENTILE does
     {is_percentile_agg, percentile_plan_check, execute_percentile, kPercentileBaseClears},
 };
 
@@ -235,6 +237,12 @@ void side_columns_read(const pg_agg_spec& s, std::set<std::string>& read) {
     if (hist_parse_arguments(s.column, spec, error) == PG_OK && !expr_is_expression(spec.column.c_str())) read.insert(spec.column);
     return;
   }
+  if (s.function == PG_AGG_MODE) {   // x, then the reducer
+    ModeSpec spec;
+    std::string error;
+    if (mode_parse_arguments(s.column, spec, error) == PG_OK && !expr_is_expression(spec.column.c_str()) && spec.column != "*") read.insert(spec.column);
+    return;
+  }
   const bool with_time = is_with_time_agg(s);
   if (!with_time && !is_covariance_agg(s)) {
     if (strcmp(s.column, "*") != 0) read.insert(s.column);
@@ -284,6 +292,7 @@ const char* agg_function_text(int32_t fn) {
     case PG_AGG_SKEWNESS: return "SKEWNESS";
     case PG_AGG_KURTOSIS: return "KURTOSIS";
     case PG_AGG_HISTOGRAM: return "HISTOGRAM";
+    case PG_AGG_MODE: return "MODE";
     case PG_AGG_FIRSTWITHTIME: return "FIRSTWITHTIME";
     case PG_AGG_LASTWITHTIME: return "LASTWITHTIME";
     default: return "this aggregation function";

@@ -473,6 +473,8 @@ struct AggResult {
   // PG_RESULT_VALUE_COUNTS (PERCENTILE): set_sizes = runs per group, d[0] = the runs' values (ascending under Double.compare within a group),
   // l[0] = their counts; `param` is the aggregation's p (also kept on a final PG_RESULT_DOUBLE: the data table names the column by it)
   double param = 0;
+  // PG_RESULT_VALUE_COUNT_MAP (MODE): set_sizes = entries per group, ascending by key; l[0] = the counts; `set_value_kind` the column's stored
+  // type (0 INT, 1 LONG: the keys exactly in l[1]; 2 FLOAT, 3 DOUBLE: the keys in d[0], a FLOAT widened exactly)
 };
 // What pg_result_merge / pg_result_all_reduce need to merge two results of the same query and to re-assemble the groups:
 // the dense accumulator table [n_ops][G] + the statistics counters + the DISTINCTCOUNT / HLL regions, left in HBM.
@@ -515,7 +517,7 @@ struct ResultColumn {
 // Result::merged_elsewhere, one bit per side path
 enum MergedElsewhere : uint32_t {
   MERGED_PERCENTILE = 1u << 0, MERGED_EXPRESSION = 1u << 1, MERGED_VARIANCE = 1u << 2, MERGED_FOURTH_MOMENT = 1u << 3, MERGED_COVARIANCE = 1u << 4,
-  MERGED_WITH_TIME = 1u << 5, MERGED_HISTOGRAM = 1u << 6,
+  MERGED_WITH_TIME = 1u << 5, MERGED_HISTOGRAM = 1u << 6, MERGED_MODE = 1u << 7,
 };
 struct Result {
   std::vector<ResultColumn> schema_keys, schema_aggs;
@@ -539,7 +541,8 @@ struct Result {
   // MERGED_* bits: the side aggregations the query carried.  Their results merge on the Java side, never in the library (pg_api.cpp words
   // the refusals): a PERCENTILE's lists by value; an aggregation over an expression because the scale of its sums differs per segment; the
   // variance, SKEWNESS / KURTOSIS and covariance tuples by VarianceTuple#apply, PinotFourthMoment#combine and CovarianceTuple#apply; the
-  // FIRSTWITHTIME / LASTWITHTIME pairs with the functions' own merge; the HISTOGRAM arrays by DoubleVectorOpUtils#vectorAdd
+  // FIRSTWITHTIME / LASTWITHTIME pairs with the functions' own merge; the HISTOGRAM arrays by DoubleVectorOpUtils#vectorAdd; a MODE's maps by
+  // value (the per-key sum of ModeAggregationFunction#merge)
   uint32_t merged_elsewhere = 0;
   pg_exec_stats stats{};
 };
@@ -636,7 +639,7 @@ Column* side_argument_column(Segment& seg, const char* name, const char* fn, con
 // kernels read, without a NaN or an infinity — the sums have no digits for them
 Column* side_value_column(Segment& seg, const char* name, const char* fn, bool null_handling);
 // The columns an aggregation of ANOTHER path reads, added to `read` (a pass counts every column the query projects): a plain column name,
-// the column arguments of a FIRSTWITHTIME / LASTWITHTIME / COVAR argument list, or the first argument of a HISTOGRAM's.  COUNT(*) and a malformed list add nothing — the list's
+// the column arguments of a FIRSTWITHTIME / LASTWITHTIME / COVAR argument list, or the first argument of a HISTOGRAM's or a MODE's.  COUNT(*) and a malformed list add nothing — the list's
 // own path refuses it.
 void side_columns_read(const pg_agg_spec& s, std::set<std::string>& read);
 const char* agg_function_text(int32_t fn);   // "VAR_POP", "FIRSTWITHTIME", ...: the functions the side paths name in messages
@@ -709,7 +712,8 @@ struct SidePath {
 const SidePath* side_path_of(const pg_query& q);     // the outermost path with an aggregation in `q`; null: none, or a DISTINCT / selection query
 void side_check(Segment& seg, const pg_query& q);    // every nested path's plan_check, then the checks and the cached plan of the innermost ordinary part
 void side_base_query(const pg_query& q, SideBaseQuery& out);   // `q` without the aggregations of its outermost path (pg_side_query.h), failing through fail()
-// exact PERCENTILE (pg_exec_percentile.hip): the ordinary part and one counting pass per distinct percentile column
+// exact PERCENTILE and MODE (pg_exec_percentile.hip): the ordinary part and one counting pass per distinct column; is_percentile_agg is the
+// counting path's test, PERCENTILE or MODE
 bool is_percentile_agg(const pg_agg_spec& s);
 void percentile_plan_check(Segment& seg, const pg_query& q);
 std::unique_ptr<Result> execute_percentile(Segment& seg, const pg_query& q, const CancelToken* cancel);
@@ -817,6 +821,7 @@ struct Knobs {
   // counters); beyond that the sort tier runs.  Tests lower both to cross the boundaries on small segments.
   int64_t pctl_lds_max_keys = 32768;          // PG_PCTL_LDS_MAX_KEYS
   int64_t pctl_hbm_max_bytes = (int64_t)256 << 20;   // PG_PCTL_HBM_MAX_BYTES
+  int64_t mode_split_ids = 1024;              // PG_MODE_SPLIT_IDS: fewest ids of a row worth a wavefront of their own in pg_mode_select (few wide rows are cut into such shares; flat from 64 to 4 096 in tools/prof_mode.py's sweep)
   int64_t pctl_sort_max_bytes = (int64_t)8 << 30;    // PG_PCTL_SORT_MAX_BYTES: work area of the sort tier (larger ones are refused by pg_query_exec, which alone knows the matches)
   // expressions inside aggregations (pg_exec_expr.hip): tables of up to expr_lds_max_slots 64-bit slots (groups x slots per group) live in the
   // workgroups' LDS (default and ceiling PG_EXPR_LDS_SLOTS = 16 384: 128 KiB), up to expr_hbm_max_bytes in HBM; beyond that the query is refused.

@@ -144,10 +144,11 @@ extern "C" __global__ void __launch_bounds__(256) pg_pctl_select(const PgPctlSel
   }
 }
 
-// One wavefront per row: its non-zero (id, count) runs, ascending, at offsets[row]
+// One wavefront per row: its (id, count) runs whose count reaches the row's threshold, ascending, at offsets[row].  Without `min_counts` the
+// threshold is 1 — the row's non-zero runs, PERCENTILE's and MODE's intermediate —; MODE passes a row's greatest count and gets its tied ids.
 extern "C" __global__ void __launch_bounds__(256) pg_pctl_runs(const uint32_t* __restrict__ table, const uint32_t* __restrict__ rows, int32_t n_rows,
-                                                               uint32_t card, const int64_t* __restrict__ offsets, uint32_t* __restrict__ out_ids,
-                                                               uint32_t* __restrict__ out_counts) {
+                                                               uint32_t card, const int64_t* __restrict__ offsets, const uint32_t* __restrict__ min_counts,
+                                                               uint32_t* __restrict__ out_ids, uint32_t* __restrict__ out_counts) {
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int waves = blockDim.x >> 6;
@@ -155,11 +156,13 @@ extern "C" __global__ void __launch_bounds__(256) pg_pctl_runs(const uint32_t* _
     const uint32_t* r = table + (uint64_t)rows[row] * card;
     int64_t at = offsets[row];
     const int64_t end = offsets[row + 1];
+    const uint32_t least = min_counts ? min_counts[row] : 1u;   // (never 0: a row without a counted id has no run)
+    if (at == end) continue;
     for (uint32_t i0 = 0; i0 < card; i0 += 64) {
       const uint32_t c = i0 + lane < card ? r[i0 + lane] : 0u;
-      const uint64_t nzm = __ballot(c != 0);
+      const uint64_t nzm = __ballot(c >= least);
       const int64_t pos = at + __popcll(nzm & ((1ULL << lane) - 1ULL));
-      if (c != 0 && pos < end) { out_ids[pos] = i0 + lane; out_counts[pos] = c; }
+      if (c >= least && pos < end) { out_ids[pos] = i0 + lane; out_counts[pos] = c; }
       at += __popcll(nzm);
     }
   }
@@ -246,10 +249,12 @@ extern "C" __global__ void __launch_bounds__(256) pg_pctl_sort_select(const PgPc
   }
 }
 
-// One wavefront per admitted group: its runs' (value id, count) at offsets[row]
+// One wavefront per admitted group: its runs' (value id, count) at offsets[row] — all of them, or with `min_counts` (MODE's tied ids) those of
+// its `n_runs[row]` runs whose count reaches the row's threshold, compacted
 extern "C" __global__ void __launch_bounds__(256) pg_pctl_sort_runs(const uint64_t* __restrict__ run_keys, const uint32_t* __restrict__ run_counts,
                                                                     const uint32_t* __restrict__ rows, const int64_t* __restrict__ first_run, int32_t n_rows,
-                                                                    uint32_t card, const int64_t* __restrict__ offsets, uint32_t* __restrict__ out_ids,
+                                                                    uint32_t card, const int64_t* __restrict__ offsets, const uint32_t* __restrict__ min_counts,
+                                                                    const uint32_t* __restrict__ n_runs, uint32_t* __restrict__ out_ids,
                                                                     uint32_t* __restrict__ out_counts) {
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -257,9 +262,23 @@ extern "C" __global__ void __launch_bounds__(256) pg_pctl_sort_runs(const uint64
   for (int64_t row = (int64_t)blockIdx.x * waves + wave; row < n_rows; row += (int64_t)gridDim.x * waves) {
     const int64_t at = offsets[row], n = offsets[row + 1] - at, src = first_run[row];
     const uint64_t k0 = (uint64_t)rows[row] * card;
-    for (int64_t i = lane; i < n; i += 64) {
-      out_ids[at + i] = (uint32_t)(run_keys[src + i] - k0);
-      out_counts[at + i] = run_counts[src + i];
+    if (!min_counts) {
+      for (int64_t i = lane; i < n; i += 64) {
+        out_ids[at + i] = (uint32_t)(run_keys[src + i] - k0);
+        out_counts[at + i] = run_counts[src + i];
+      }
+      continue;
+    }
+    if (n == 0) continue;
+    const uint32_t least = min_counts[row];
+    const int64_t in_row = n_runs[row];
+    int64_t pos0 = at;
+    for (int64_t i0 = 0; i0 < in_row; i0 += 64) {
+      const uint32_t c = i0 + lane < in_row ? run_counts[src + i0 + lane] : 0u;
+      const uint64_t hit = __ballot(c >= least);
+      const int64_t pos = pos0 + __popcll(hit & ((1ULL << lane) - 1ULL));
+      if (c >= least && pos < at + n) { out_ids[pos] = (uint32_t)(run_keys[src + i0 + lane] - k0); out_counts[pos] = c; }
+      pos0 += __popcll(hit);
     }
   }
 }
@@ -334,8 +353,9 @@ void pg_pctl_launch_sort_select(const PgPctlSortSelectArgs* args, hipStream_t st
   hipLaunchKernelGGL(pg_pctl_sort_select, dim3((unsigned)((a.n_rows + 255) / 256)), dim3(256), 0, stream, a);
 }
 void pg_pctl_launch_sort_runs(const uint64_t* run_keys, const uint32_t* run_counts, const uint32_t* rows, const int64_t* first_run, int32_t n_rows,
-                              uint32_t card, const int64_t* offsets, uint32_t* out_ids, uint32_t* out_counts, int grid, hipStream_t stream) {
-  hipLaunchKernelGGL(pg_pctl_sort_runs, dim3(grid), dim3(256), 0, stream, run_keys, run_counts, rows, first_run, n_rows, card, offsets, out_ids, out_counts);
+                              uint32_t card, const int64_t* offsets, const uint32_t* min_counts, const uint32_t* n_runs, uint32_t* out_ids, uint32_t* out_counts,
+                              int grid, hipStream_t stream) {
+  hipLaunchKernelGGL(pg_pctl_sort_runs, dim3(grid), dim3(256), 0, stream, run_keys, run_counts, rows, first_run, n_rows, card, offsets, min_counts, n_runs, out_ids, out_counts);
 }
 
 // ---- launchers (pg_exec_percentile.hip) -----------------------------------------------------------------------------------------------------------
@@ -353,7 +373,7 @@ void pg_pctl_launch_select(const PgPctlSelectArgs* args, int grid, hipStream_t s
   const PgPctlSelectArgs a = *args;
   hipLaunchKernelGGL(pg_pctl_select, dim3(grid), dim3(256), 0, stream, a);
 }
-void pg_pctl_launch_runs(const uint32_t* table, const uint32_t* rows, int32_t n_rows, uint32_t card, const int64_t* offsets, uint32_t* out_ids,
-                         uint32_t* out_counts, int grid, hipStream_t stream) {
-  hipLaunchKernelGGL(pg_pctl_runs, dim3(grid), dim3(256), 0, stream, table, rows, n_rows, card, offsets, out_ids, out_counts);
+void pg_pctl_launch_runs(const uint32_t* table, const uint32_t* rows, int32_t n_rows, uint32_t card, const int64_t* offsets, const uint32_t* min_counts,
+                         uint32_t* out_ids, uint32_t* out_counts, int grid, hipStream_t stream) {
+  hipLaunchKernelGGL(pg_pctl_runs, dim3(grid), dim3(256), 0, stream, table, rows, n_rows, card, offsets, min_counts, out_ids, out_counts);
 }

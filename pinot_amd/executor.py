@@ -17,6 +17,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 from dataclasses import dataclass
+from fractions import Fraction
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -437,6 +438,17 @@ class ResultsBlock:
                 api.call("result_set_values_double", h, a, values.ctypes.data, total)
                 api.call("result_set_counts", h, a, counts.ctypes.data, total)
                 rb.arrays.append((k, sizes, values[:total], counts[:total]))
+            elif k == capi.RESULT_VALUE_COUNT_MAP:   # MODE: per group the map value -> count, keys typed by the column (exact int64, or float64)
+                sizes = np.zeros(ng, dtype=np.int32)
+                api.call("result_set_sizes", h, a, sizes.ctypes.data, ng)
+                total = int(sizes.sum())
+                data_type = host.columns[spec.column.split(",")[0].strip()].data_type
+                floating = data_type in ("FLOAT", "DOUBLE")
+                keys = np.zeros(max(total, 1), dtype=np.float64 if floating else np.int64)
+                counts = np.zeros(max(total, 1), dtype=np.int64)
+                api.call("result_set_values_double" if floating else "result_set_values_long", h, a, keys.ctypes.data, total)
+                api.call("result_set_counts", h, a, counts.ctypes.data, total)
+                rb.arrays.append((k, sizes, keys[:total], counts[:total], data_type))
             elif k == capi.RESULT_DOUBLE_ARRAY:   # HISTOGRAM: per group the numBins counts of its DoubleArrayList
                 sizes = np.zeros(ng, dtype=np.int32)
                 api.call("result_set_sizes", h, a, sizes.ctypes.data, ng)
@@ -575,6 +587,12 @@ class ResultsBlock:
                     cols.append([(int(n), float(m1), float(m2), float(m3), float(m4)) for n, m1, m2, m3, m4 in zip(*arr[1:6])])
                 elif k == capi.RESULT_VALUE_TIME_PAIR:   # (value, time) per group; a FLOAT / DOUBLE value keeps its bits (NaN payloads, -0.0)
                     cols.append([(v.item(), int(t)) for v, t in zip(arr[1], arr[2])])
+                elif k == capi.RESULT_VALUE_COUNT_MAP:   # a ModeMap per group: (type, ((key, count), ...)) ascending by key; empty: ("INT", ())
+                    col, pos = [], 0
+                    for sz in arr[1]:
+                        col.append(mode_map(arr[4], [v.item() for v in arr[2][pos:pos + sz]], [int(c) for c in arr[3][pos:pos + sz]]))
+                        pos += sz
+                    cols.append(col)
                 elif k == capi.RESULT_DOUBLE_ARRAY:   # a tuple of floats per group
                     col, pos = [], 0
                     for sz in arr[1]:
@@ -745,6 +763,70 @@ def fourth_moment_merge(a, b):
     return (n, float(m1), float(m2), float(m3), float(m4))
 
 
+def _double_compare_key(v):
+    """Double.compare order for float keys (-0.0 < 0.0, NaN greatest, one NaN); integers as they are"""
+    if isinstance(v, float):
+        if v != v:
+            return (1, 0.0, 0)
+        return (0, v, 0 if (v != 0.0 or math.copysign(1.0, v) < 0) else 1)
+    return (0, v, 0)
+
+
+def mode_map(data_type: str, keys, counts):
+    """MODE's intermediate as a hashable value: (type, ((key, count), ...)), the entries ascending by key — "INT" / "LONG" keys Python ints,
+    "FLOAT" / "DOUBLE" keys floats (a FLOAT widened exactly).  An empty map is ("INT", ()): the reference's Int2LongOpenHashMap, whatever
+    the column's type."""
+    entries = tuple(sorted(zip(keys, counts), key=lambda e: _double_compare_key(e[0])))
+    return (data_type, entries) if entries else ("INT", ())
+
+
+def mode_merge(a, b):
+    """ModeAggregationFunction#merge: an empty map yields the other; else the per-key sum; maps of two key types are refused with the
+    reference's text."""
+    if not a[1]:
+        return b
+    if not b[1]:
+        return a
+    if a[0] != b[0]:
+        names = {"INT": "Int2LongOpenHashMap", "LONG": "Long2LongOpenHashMap", "FLOAT": "Float2LongOpenHashMap", "DOUBLE": "Double2LongOpenHashMap"}
+        raise ValueError(f"Illegal data type for Intermediate Result of MODE aggregation function: {names[a[0]]}, {names[b[0]]}")
+    out = {}
+    for k, c in a[1] + b[1]:
+        kk = _double_compare_key(k)
+        out[kk] = (k, out[kk][1] + c) if kk in out else (k, c)
+    return (a[0], tuple(out[kk] for kk in sorted(out)))
+
+
+def mode_final(m, reducer: str = "MIN") -> float:
+    """ModeAggregationFunction#extractFinalResult: the key of greatest count; ties go to the lowest key (MIN), the highest (MAX) — in
+    Double.compare order — or to the exact sum of the tied keys as doubles, rounded once, over their number (AVG).  -Infinity for an empty map."""
+    if reducer not in capi.MODE_REDUCERS:
+        raise ValueError("No enum constant org.apache.pinot.core.query.aggregation.function.ModeAggregationFunction.MultiModeReducerType." + reducer)
+    if not m[1]:
+        return float("-inf")
+    top = max(c for _, c in m[1])
+    tied = [float(k) for k, c in m[1] if c == top]   # ascending by key
+    if reducer == "MIN":
+        return tied[0]
+    if reducer == "MAX":
+        return tied[-1]
+    if any(t != t for t in tied) or (float("inf") in tied and float("-inf") in tied):
+        return float("nan")
+    if float("inf") in tied or float("-inf") in tied:
+        return float("inf") if float("inf") in tied else float("-inf")
+    try:
+        total = math.fsum(tied)   # the exact sum, rounded once
+    except OverflowError:
+        total = float("inf") if sum(Fraction(t) for t in tied) > 0 else float("-inf")
+    return total / len(tied)
+
+
+def mode_reducer_of(column: str) -> str:
+    """the reducer of a MODE's canonical argument list: "x" -> MIN, "x,'AVG'" -> AVG"""
+    _, comma, rest = column.partition(",")
+    return rest.strip().strip("'") if comma else "MIN"
+
+
 def histogram_merge(a, b):
     """HistogramAggregationFunction#merge (DoubleVectorOpUtils#vectorAdd): the element-wise sum of two count arrays, what the Java side does
     with the arrays of two segments; arrays of unequal lengths are refused, as vectorAdd's checkState refuses them."""
@@ -796,11 +878,13 @@ def merge_intermediate(function: str, a, b):
         return with_time_merge(function, a, b)
     if function in capi.HISTOGRAM_FUNCTIONS:
         return histogram_merge(a, b)
+    if function in capi.MODE_FUNCTIONS:
+        return mode_merge(a, b)
     raise ValueError(function)
 
 
-def extract_final(function: str, v):
-    """AggregationFunction#extractFinalResult."""
+def extract_final(function: str, v, column: "Optional[str]" = None):
+    """AggregationFunction#extractFinalResult (`column`: the aggregation's argument list, which carries a MODE's reducer)."""
     function = capi.MV_TO_SV_FUNCTION.get(function, function)
     if function == "AVG":
         return v[0] / v[1] if v[1] else float("-inf")
@@ -818,6 +902,8 @@ def extract_final(function: str, v):
         return skewness_final(v) if function == "SKEWNESS" else kurtosis_final(v)
     if function in capi.WITH_TIME_FUNCTIONS:   # the pair's value
         return v[0]
+    if function in capi.MODE_FUNCTIONS:   # a map: its mode under the reducer; a final double (PG_QUERY_FLAG_FINAL_MODE) as it is
+        return mode_final(v, mode_reducer_of(column or "")) if isinstance(v, tuple) else v
     if function in capi.HISTOGRAM_FUNCTIONS:   # the array itself (DOUBLE_ARRAY)
         return tuple(float(x) for x in v)
     return v
@@ -843,8 +929,8 @@ class GroupByCombineOperator:
         return table
 
     def final(self) -> Dict[tuple, list]:
-        fns = [a.function for a in self.blocks[0].query.aggregations]
-        return {k: [extract_final(f, v) for f, v in zip(fns, vals)] for k, vals in self.merge().items()}
+        aggs = self.blocks[0].query.aggregations
+        return {k: [extract_final(a.function, v, a.column) for a, v in zip(aggs, vals)] for k, vals in self.merge().items()}
 
 
 class GpuInstancePlanMaker:

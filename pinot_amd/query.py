@@ -138,6 +138,7 @@ class QueryContext:
         aggs = [norm(f"{a.function}({a.column or '*'}{',' + str(a.log2m) if a.log2m else ''})") for a in self.aggregations]
         pctl = [(a.column, a.percentile) if a.function == "PERCENTILE" else None for a in self.aggregations]
         hists = [a.column if a.function in capi.HISTOGRAM_FUNCTIONS else None for a in self.aggregations]
+        modes = [a.column if a.function in capi.MODE_FUNCTIONS else None for a in self.aggregations]
         expr_aggs = {}   # (function, canonical text) of the aggregations over expressions -> the first one's index
         for i, a in enumerate(self.aggregations):
             if "(" in (a.column or ""):
@@ -155,6 +156,8 @@ class QueryContext:
                 out.append((capi.ORDER_BY_AGGREGATION, pctl.index(_percentile_of_text(text)), asc))
             elif _histogram_of_text(text) is not None and _histogram_of_text(text) in hists:   # a HISTOGRAM by its canonical argument list
                 out.append((capi.ORDER_BY_AGGREGATION, hists.index(_histogram_of_text(text)), asc))
+            elif _mode_of_text(text) is not None and _mode_of_text(text) in modes:   # a MODE by its canonical argument list: MODE(x) names MODE(x) alone, not MODE(x, 'MIN')
+                out.append((capi.ORDER_BY_AGGREGATION, modes.index(_mode_of_text(text)), asc))
             elif expr_aggs and _expression_aggregation_of_text(text) in expr_aggs:
                 # an aggregation over an expression, whatever its spelling (infix or function form): by its canonical text
                 out.append((capi.ORDER_BY_AGGREGATION, expr_aggs[_expression_aggregation_of_text(text)], asc))
@@ -231,6 +234,20 @@ def _histogram_of_text(text: str):
             return None
         p.i += 2
         args = p.histogram_arguments()
+    except (SqlError, IndexError):
+        return None
+    return args if p.peek()[0] == "eof" else None
+
+
+@functools.lru_cache(maxsize=256)
+def _mode_of_text(text: str):
+    """The canonical argument list of an ORDER BY expression text that spells a MODE, else None."""
+    try:
+        p = _Parser(text)
+        if not (p.kw("MODE") and p.peek(1) == ("op", "(")):
+            return None
+        p.i += 2
+        args = p.mode_arguments(bare=True)   # (an ORDER BY text spells the reducer literal without its quotes)
     except (SqlError, IndexError):
         return None
     return args if p.peek()[0] == "eof" else None
@@ -609,6 +626,28 @@ class _Parser:
             raise SqlError(f"The number of bins must be greater than zero, given {bins}")
         return f"{args[0]},'{args[1]}','{args[2]}','{args[3]}'"
 
+    def mode_arguments(self, bare: bool = False) -> str:
+        """The canonical argument list of a MODE, the opening parenthesis taken: "x" or "x,'MAX'".  The malformed forms raise with
+        ModeAggregationFunction's own texts: more than two arguments, a reducer MultiModeReducerType.valueOf does not know (it is exact:
+        upper case)."""
+        args = [self.aggregation_argument()]
+        while self.peek() == ("op", ","):
+            self.i += 1
+            t = self.take()
+            if t[0] not in ("str", "num", "id"):
+                raise SqlError(f"MODE: expected an argument, got {t}")
+            args.append(t)
+        self.expect_op(")")
+        if len(args) > 2:
+            raise SqlError(f"Mode expects at most 2 arguments, got: {len(args)}")
+        if len(args) == 1:
+            return args[0]
+        if args[1][0] != "str" and not (bare and args[1][0] == "id"):
+            raise SqlError(f"MODE: the second argument must be a quoted MultiModeReducerType ('MIN', 'MAX' or 'AVG'), got {args[1][1]}")
+        if args[1][1] not in capi.MODE_REDUCERS:
+            raise SqlError("No enum constant org.apache.pinot.core.query.aggregation.function.ModeAggregationFunction.MultiModeReducerType." + args[1][1])
+        return f"{args[0]},'{args[1][1]}'"
+
     # --- select -------------------------------------------------------------------------------------------------
     def select_item(self, q: QueryContext):
         if self.peek() != ("op", "*") and self.starts_expression():   # an arithmetic expression: a DISTINCT / GROUP BY key of the select list
@@ -636,6 +675,11 @@ class _Parser:
                 return
             if fn in capi.HISTOGRAM_FUNCTIONS:   # HISTOGRAM(x, lower, upper, numBins) / HISTOGRAM(x, ARRAY[e0, e1, ...])
                 q.aggregations.append(AggregationSpec(fn, self.histogram_arguments()))
+                if self.kw("AS"):
+                    self.i += 2
+                return
+            if fn in capi.MODE_FUNCTIONS:   # MODE(x) / MODE(x, 'MIN' | 'MAX' | 'AVG')
+                q.aggregations.append(AggregationSpec(fn, self.mode_arguments()))
                 if self.kw("AS"):
                     self.i += 2
                 return
@@ -678,7 +722,7 @@ class _Parser:
                 self.i += 1
                 log2m = int(self.literal())
             self.expect_op(")")
-            if fn not in capi.AGG_FUNCTIONS:
+            if fn not in capi.AGG_FUNCTION_IDS:
                 raise SqlError(f"unsupported aggregation function {fn}")
             q.aggregations.append(AggregationSpec(fn, col, log2m))
         else:
@@ -818,7 +862,7 @@ class CQuery:
         if na:
             aggs = (capi.PgAggSpec * na)()
             for i, a in enumerate(q.aggregations):
-                aggs[i].function = capi.AGG_FUNCTIONS[a.function]
+                aggs[i].function = capi.AGG_FUNCTION_IDS[a.function]
                 aggs[i].log2m = a.log2m
                 aggs[i].column = a.column.encode() if a.column else None
             self._keep.append(aggs)
