@@ -349,6 +349,11 @@ typedef struct pg_agg_spec {
                              an expression.  At most 15 operations and 8 distinct columns per expression, 4 distinct expressions per query
                              (PG_ERR_UNSUPPORTED beyond); malformed text is PG_ERR_INVALID_ARGUMENT.  Evaluated in IEEE double, one rounded
                              operation at a time in the reference's argument order; results that carry one are not merged in the library.
+                             Such an expression may hold CASEs, case(when1,then1,...,else) — a WHEN a call of equals / not_equals /
+                             greater_than / greater_than_or_equal / less_than / less_than_or_equal or of and / or / not over those, a
+                             THEN / ELSE a column, numeric literal, arithmetic call or CASE, 'null' the omitted ELSE; a dictionary-encoded
+                             STRING column may stand under equals / not_equals against a literal.  Comparisons, logical calls and
+                             selects count as operations.  Only here: as a filter's lhs or a group-by key it is PG_ERR_UNSUPPORTED.
                              FIRSTWITHTIME / LASTWITHTIME: the argument list, "x,t,'DOUBLE'" (see PG_AGG_FIRSTWITHTIME); COVAR_POP / COVAR_SAMP:
                              the argument list "x,y" (see PG_AGG_COVARPOP). */
 } pg_agg_spec;

@@ -25,6 +25,7 @@ import org.apache.pinot.common.request.context.predicate.RangePredicate;
 import org.apache.pinot.core.query.aggregation.function.AggregationFunction;
 import org.apache.pinot.core.query.aggregation.function.DistinctCountHLLAggregationFunction;
 import org.apache.pinot.core.query.request.context.QueryContext;
+import org.apache.pinot.spi.data.FieldSpec;
 
 public final class NativeQuery implements AutoCloseable {
   private static final int MAGIC = 0x32514750;   // "PGQ2": + ORDER BY block, LIMIT, minSegmentGroupTrimSize
@@ -133,10 +134,10 @@ public final class NativeQuery implements AutoCloseable {
       if (fn < 0 || args.size() > 1) {
         return null;
       }
-      // the argument: a column, or — for SUM / MIN / MAX / AVG / MINMAXRANGE — an arithmetic expression over columns and literals, handed
-      // over as the text ExpressionContext#toString prints (pg_agg_spec.column; the library parses it, pg_expr.h)
+      // the argument: a column, or — for SUM / MIN / MAX / AVG / MINMAXRANGE — an arithmetic expression over columns and literals, with or
+      // without a CASE in it, handed over as the text ExpressionContext#toString prints (pg_agg_spec.column; the library parses it, pg_expr.h)
       String argument = args.isEmpty() ? "*" : args.get(0).getType() == ExpressionContext.Type.IDENTIFIER ? args.get(0).getIdentifier()
-          : takesExpression(fn) && isArithmetic(args.get(0)) ? args.get(0).toString() : null;
+          : takesExpression(fn) && (isArithmetic(args.get(0)) || isCaseExpression(args.get(0))) ? args.get(0).toString() : null;
       if (argument == null) {
         return null;
       }
@@ -603,6 +604,123 @@ public final class NativeQuery implements AutoCloseable {
       }
     }
     return true;
+  }
+
+  /**
+   * An expression with a CASE in it (CaseTransformFunction; DESIGN 4.16): calls of the eight arithmetic names, of case, of the six comparisons
+   * and of and / or / not, with identifiers or literals as leaves — conditions where a WHEN stands, values everywhere else.  The library parses
+   * the text ExpressionContext#toString prints, which shows every literal quoted: it types a literal from its text, as
+   * RequestUtils.getLiteral does for a literal the query spells as a number.  Where the two disagree the Java plan answers (false here): a
+   * literal whose LiteralContext type is not what its text implies (a number spelled as a string, a CAST folded by the compiler), and a
+   * STRING-typed literal compared with a value that can only be numeric.  (A STRING-typed literal against an identifier is the library's to
+   * judge: it knows the column's type and refuses a numeric one.)
+   */
+  static boolean isCaseExpression(ExpressionContext e) {
+    return e.getType() == ExpressionContext.Type.FUNCTION && isCaseValue(e) && !isArithmetic(e);
+  }
+
+  private static boolean isCaseValue(ExpressionContext e) {
+    if (e.getType() == ExpressionContext.Type.IDENTIFIER) {
+      return true;
+    }
+    if (e.getType() == ExpressionContext.Type.LITERAL) {
+      return impliedType(e) != FieldSpec.DataType.STRING && e.getLiteral().getType() == impliedType(e);
+    }
+    if (e.getType() != ExpressionContext.Type.FUNCTION || e.getFunction().getType() != FunctionContext.Type.TRANSFORM) {
+      return false;
+    }
+    FunctionContext f = e.getFunction();
+    List<ExpressionContext> args = f.getArguments();
+    switch (f.getFunctionName()) {
+      case "add":
+      case "plus":
+      case "sub":
+      case "minus":
+      case "mult":
+      case "times":
+      case "div":
+      case "divide":
+        for (ExpressionContext a : args) {
+          if (!isCaseValue(a)) {
+            return false;
+          }
+        }
+        return true;
+      case "case":
+        if (args.size() < 3 || args.size() % 2 == 0) {
+          return false;
+        }
+        for (int i = 0; i + 1 < args.size(); i += 2) {
+          if (!isCaseCondition(args.get(i)) || !isCaseValue(args.get(i + 1))) {
+            return false;
+          }
+        }
+        ExpressionContext otherwise = args.get(args.size() - 1);   // an omitted ELSE and ELSE NULL: the literal 'null'
+        boolean none = otherwise.getType() == ExpressionContext.Type.LITERAL
+            && (otherwise.getLiteral().isNull() || "null".equals(otherwise.getLiteral().getStringValue()));
+        return none || isCaseValue(otherwise);
+      default:
+        return false;
+    }
+  }
+
+  private static boolean isCaseCondition(ExpressionContext e) {
+    if (e.getType() != ExpressionContext.Type.FUNCTION || e.getFunction().getType() != FunctionContext.Type.TRANSFORM) {
+      return false;
+    }
+    FunctionContext f = e.getFunction();
+    List<ExpressionContext> args = f.getArguments();
+    switch (f.getFunctionName()) {
+      case "and":
+      case "or":
+      case "not":
+        for (ExpressionContext a : args) {
+          if (!isCaseCondition(a)) {
+            return false;
+          }
+        }
+        return f.getFunctionName().equals("not") ? args.size() == 1 : args.size() >= 2;
+      case "equals":
+      case "notequals":
+        if (args.size() != 2) {
+          return false;
+        }
+        for (int i = 0; i < 2; i++) {   // a string literal: against an identifier only, and typed STRING
+          ExpressionContext a = args.get(i);
+          if (a.getType() == ExpressionContext.Type.LITERAL && impliedType(a) == FieldSpec.DataType.STRING) {
+            return a.getLiteral().getType() == FieldSpec.DataType.STRING && args.get(1 - i).getType() == ExpressionContext.Type.IDENTIFIER;
+          }
+        }
+        return isCaseValue(args.get(0)) && isCaseValue(args.get(1));
+      case "greaterthan":
+      case "greaterthanorequal":
+      case "lessthan":
+      case "lessthanorequal":
+        return args.size() == 2 && isCaseValue(args.get(0)) && isCaseValue(args.get(1));
+      default:
+        return false;
+    }
+  }
+
+  /** The type RequestUtils.getLiteral gives a literal spelled as this one's text: INT, LONG, DOUBLE — or STRING when it is no number. */
+  private static FieldSpec.DataType impliedType(ExpressionContext literal) {
+    String text = literal.getLiteral().getStringValue();
+    try {
+      Integer.parseInt(text);
+      return FieldSpec.DataType.INT;
+    } catch (NumberFormatException notAnInt) {
+      try {
+        Long.parseLong(text);
+        return FieldSpec.DataType.LONG;
+      } catch (NumberFormatException notALong) {
+        try {
+          Double.parseDouble(text);
+          return FieldSpec.DataType.DOUBLE;
+        } catch (NumberFormatException notANumber) {
+          return FieldSpec.DataType.STRING;
+        }
+      }
+    }
   }
 
   private static int estimate(QueryContext q) {

@@ -58,6 +58,7 @@ enum PgColKind : int32_t {
                         // its virtual dictionary, pg_vdict.hip)
 };
 enum PgValType : int32_t { PG_V_I32 = 0, PG_V_I64 = 1, PG_V_F32 = 2, PG_V_F64 = 3 };
+#define PG_V_DICTID 4   // PgValueSrc::val_type of an expression's operand only: the dictId itself is the value (STRING equality inside a CASE)
 
 enum PgPredKind : int32_t {
   PG_P_RANGE = 0,       // inclusive [lo, hi] on the value (typed by val_type) or on the dictId (dictionary columns)
@@ -653,6 +654,8 @@ struct PgExprArgs {
   int64_t ident[PG_EXPR_MAX_SLOTS];   // per slot of a row: 0 (SUM limbs, count), INT64_MAX (MIN), INT64_MIN (MAX)
   pg_expr_step steps[PG_EXPR_MAX_EXPRS * PG_EXPR_MAX_OPS];
 };
+// kernel arguments live in a 4 KiB segment: the block, and what the widest kernel takes beside it (pg_expr_pred's PgExprPred, 48 bytes)
+static_assert(sizeof(PgExprArgs) + 64 <= 4096, "PgExprArgs no longer fits the kernel-argument segment");
 // ---- VAR_POP / VAR_SAMP / STDDEV_POP / STDDEV_SAMP (pg_kernels_var.hip) -------------------------------------------------------------
 // One accumulation pass for all variance aggregations of a query: per matching doc the group key, then the group's 64-bit slots — a table
 // [G][slots] of int64, every slot a sum (identity 0).  Slot 0 is the doc count; every distinct argument column follows with the exact power

@@ -13,6 +13,8 @@
 //                identities (pg_expr_init)
 //   the results  SUM, MIN, MAX, AVG's pair and MINMAXRANGE's pair from the gathered rows; the reference's defaults over no doc fall out of
 //                the identities.
+// An expression may hold CASEs: more steps of the same program — comparisons, logical operations, selects —, resolved against
+// the operand columns' types by expr_resolve_operands (pg_plan.cpp) before the bounds pass; nothing else of the path knows of them.
 // The ordinary part is the query without its expression aggregations (a PERCENTILE among the others takes its own side pass from there);
 // an ORDER BY that names an expression aggregation leaves the segment untrimmed.
 #include <hip/hip_runtime.h>
@@ -131,11 +133,9 @@ ExprPlan expr_plan(Segment& seg, const pg_query& q, bool compute_bounds) {
       std::string error;
       const int32_t st = expr_parse(s.column, item.prog, error);
       if (st != PG_OK) fail(st, "%s (in %s)", error.c_str(), item.text.size() > 200 ? (item.text.substr(0, 197) + "...").c_str() : item.text.c_str());
-      std::vector<Column*> cols;
-      for (const std::string& name : item.prog.columns) {
-        Column* c = expr_operand_column(seg, name, null_handling);   // the rules expression predicates share (pg_plan.cpp)
+      const std::vector<Column*> cols = expr_resolve_operands(seg, item.prog, null_handling);   // the rules expression predicates share; a CASE typed (pg_plan.cpp)
+      for (Column* c : cols) {
         read.insert(c->name);
-        cols.push_back(c);
         size_t j = 0;
         while (j < P.srcs.size() && P.srcs[j] != c) j++;
         if (j == P.srcs.size()) {
@@ -220,6 +220,7 @@ std::unique_ptr<Result> execute_expression(Segment& seg, const pg_query& q, cons
       pg_expr_step st = item.prog.steps[k];   // the program's column indexes -> the query's sources
       if (st.a >= 0 && st.a < PG_EXPR_MAX_SRCS) st.a = item.src[(size_t)st.a];
       if (st.b >= 0 && st.b < PG_EXPR_MAX_SRCS) st.b = item.src[(size_t)st.b];
+      if (st.c >= 0 && st.c < PG_EXPR_MAX_SRCS) st.c = item.src[(size_t)st.c];
       A.steps[n_steps++] = st;
     }
     if (item.min_slot >= 0) A.ident[item.min_slot] = INT64_MAX;

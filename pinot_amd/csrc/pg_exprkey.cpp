@@ -68,6 +68,8 @@ KeySpec key_spec(Segment& seg, const char* text, bool null_handling) {
   ExprProgram prog;
   const int32_t st = expr_parse(text, prog, error);
   if (st != PG_OK) fail(st, "%s (in %s)", error.c_str(), short_text(K.text).c_str());
+  if (prog.conditional)   // (its type would be the branches' — INT, LONG ... —, not the DOUBLE of the derived key column)
+    fail(PG_ERR_UNSUPPORTED, "a CASE, a comparison or a logical call as a GROUP BY / DISTINCT key (%s): inside SUM, MIN, MAX, AVG and MINMAXRANGE they run on the GPU path", short_text(K.text).c_str());
   for (const std::string& name : prog.columns) {
     Column* c = expr_operand_column(seg, name, null_handling);   // the rules every expression shares (pg_plan.cpp)
     expr_fill_src(K.args.srcs[K.cols.size()], *c);               // (expr_parse admits at most PG_EXPR_MAX_SRCS columns)

@@ -391,6 +391,11 @@ struct ExprLeafSpec {
 bool filter_has_expression(const pg_filter_node* filter);
 Column* expr_operand_column(Segment& seg, const std::string& name, bool null_handling);   // an expression's operand, checked (seg.mu held)
 void expr_fill_src(PgValueSrc& S, const Column& c);
+// The operand columns of an aggregation's expression, checked, in the program's order.  A program that holds a CASE (pg_expr.h) is resolved
+// against their types: a literal compared with a STRING column becomes its dictId, a FLOAT-typed CASE narrows its INT / LONG literals, and
+// what the program cannot restate is refused.  seg.mu held.
+struct ExprProgram;
+std::vector<Column*> expr_resolve_operands(Segment& seg, ExprProgram& prog, bool null_handling);
 std::vector<ExprLeafSpec> expr_leaf_specs(Segment& seg, const pg_filter_node* filter, int32_t flags);   // seg.mu held
 void expr_leaf_run(Segment& seg, ExprLeafSpec& leaf);                                                    // seg.mu not needed
 // `expr_leaves`: the filter's expression leaves with their words (a filter that holds one and finds no words is PG_ERR_INTERNAL)

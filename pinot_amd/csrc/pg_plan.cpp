@@ -434,6 +434,99 @@ void expr_fill_src(PgValueSrc& S, const Column& c) {
   S.bits = c.bits;
   S.val_type = c.val_type;
   S.fx_q = 0;
+  if (c.data_type == PG_TYPE_STRING) {   // only a CASE's equality operand comes this far (expr_resolve_operands): the dictId is the value
+    S.dict = nullptr;
+    S.val_type = PG_V_DICTID;
+  }
+}
+// a STRING column inside a CASE: single-value, dictionary-encoded, and an operand of equals / not_equals against a literal wherever it is named
+static Column* case_string_column(Segment& seg, const ExprProgram& prog, int32_t index, Column* c, bool null_handling) {
+  for (int k = 0; k < prog.n_steps; k++) {
+    const pg_expr_step& st = prog.steps[k];
+    const bool is_a = st.a == index, is_b = st.b == index, is_c = st.op == PG_EXPR_SELECT && st.c == index;
+    if (!is_a && !is_b && !is_c) continue;
+    if (st.op >= PG_EXPR_GT && st.op <= PG_EXPR_LE)
+      fail(PG_ERR_UNSUPPORTED, "expression: an ordering comparison over the STRING column %s (equals and not_equals against a literal run on the GPU path)", c->name.c_str());
+    if (st.op != PG_EXPR_EQ && st.op != PG_EXPR_NE) fail(PG_ERR_UNSUPPORTED, "expression over the STRING column %s", c->name.c_str());
+    if (is_a && is_b) fail(PG_ERR_UNSUPPORTED, "expression: the STRING column %s compared with itself", c->name.c_str());
+    if ((is_a ? st.b : st.a) >= 0)
+      fail(PG_ERR_UNSUPPORTED, "expression: the STRING column %s compared with something other than a literal", c->name.c_str());
+  }
+  if (c->is_mv || c->raw_mv) fail(PG_ERR_UNSUPPORTED, "expression over the multi-value column %s", c->name.c_str());
+  if (!c->has_dictionary) fail(PG_ERR_UNSUPPORTED, "expression: a comparison over the raw STRING column %s (dictionary-encoded STRING columns run on the GPU path)", c->name.c_str());
+  if (c->col_kind != PG_COL_FIXED_BIT || c->bits < 1 || c->bits > 31 || c->cardinality < 1)
+    fail(PG_ERR_UNSUPPORTED, "expression: operand column %s (layout %d, %d bits)", c->name.c_str(), c->col_kind, c->bits);
+  if (null_handling && column_has_nulls(seg, c->name)) fail(PG_ERR_UNSUPPORTED, "enableNullHandling: expression over %s, which holds nulls", c->name.c_str());
+  return c;
+}
+std::vector<Column*> expr_resolve_operands(Segment& seg, ExprProgram& prog, bool null_handling) {
+  std::vector<Column*> cols;
+  for (size_t i = 0; i < prog.columns.size(); i++) {
+    Column* c = prog.conditional ? seg.find(prog.columns[i].c_str()) : nullptr;
+    if (c && c->data_type == PG_TYPE_STRING) cols.push_back(case_string_column(seg, prog, (int32_t)i, c, null_handling));
+    else cols.push_back(expr_operand_column(seg, prog.columns[i], null_handling));
+  }
+  if (!prog.conditional) return cols;
+  constexpr uint64_t kExact = 1ULL << 53;   // beyond it a LONG is no double: the reference compares such values through BigDecimal
+  for (const ExprComparison& cmp : prog.comparisons) {
+    const Column* str = nullptr;
+    for (int k = 0; k < 2; k++) {
+      if (cmp.column[k] < 0) continue;
+      const Column* c = cols[(size_t)cmp.column[k]];
+      if (c->data_type == PG_TYPE_STRING) str = c;
+      if (c->data_type == PG_TYPE_LONG && c->max_abs_int > kExact)
+        fail(PG_ERR_UNSUPPORTED, "expression: a comparison over the LONG column %s, whose values reach beyond 2^53", c->name.c_str());
+    }
+    if (cmp.literal < 0) continue;
+    pg_expr_step& st = prog.steps[cmp.step];
+    if (str) {   // Dictionary#indexOf, as the EQ predicate's evaluator: a value the dictionary lacks is -1, which no doc holds
+      const int32_t id = dict_insertion_index(*str, cmp.text.c_str());
+      st.lit = id >= 0 ? (double)id : -1.0;
+    } else if (cmp.literal_type == PG_EXPR_T_STRING) {
+      fail(PG_ERR_INVALID_ARGUMENT, "expression: the literal '%s' is not a decimal number", short_text(cmp.text).c_str());
+    } else if (cmp.literal_type == PG_EXPR_T_LONG && (cmp.ival > (int64_t)kExact || cmp.ival < -(int64_t)kExact)) {
+      fail(PG_ERR_UNSUPPORTED, "expression: a comparison with the LONG literal %lld, beyond 2^53", (long long)cmp.ival);
+    }
+  }
+  // the CASEs' result types: the numeric upcast INT -> LONG -> FLOAT -> DOUBLE over the branches, inner CASEs first
+  std::vector<int32_t> type(prog.cases.size(), PG_TYPE_INT);
+  for (size_t i = 0; i < prog.cases.size(); i++) {
+    const ExprCase& C = prog.cases[i];
+    if (null_handling && !C.has_else)
+      fail(PG_ERR_UNSUPPORTED, "enableNullHandling: a CASE without ELSE (the docs no WHEN selects are null there)");
+    auto type_of = [&](const ExprBranch& b) -> int32_t {
+      switch (b.kind) {
+        case ExprBranch::COLUMN: return cols[(size_t)b.ref]->data_type;
+        case ExprBranch::LITERAL: return b.ref;
+        case ExprBranch::CASE: return type[(size_t)b.ref];
+        default: return PG_TYPE_DOUBLE;
+      }
+    };
+    int32_t t = PG_TYPE_INT;
+    for (const ExprBranch& b : C.branches) {
+      const int32_t bt = type_of(b);
+      if (bt > PG_TYPE_DOUBLE) fail(PG_ERR_UNSUPPORTED, "expression over the STRING column %s", cols[(size_t)b.ref]->name.c_str());   // (case_string_column refuses it first)
+      t = std::max(t, bt);
+    }
+    type[i] = t;
+    if (t != PG_TYPE_FLOAT) continue;
+    // a FLOAT-typed CASE reads every branch as a float: an INT / LONG literal is narrowed here, a column or a CASE would be narrowed per doc
+    for (const ExprBranch& b : C.branches) {
+      const int32_t bt = type_of(b);
+      if (bt != PG_TYPE_INT && bt != PG_TYPE_LONG) continue;
+      if (b.kind == ExprBranch::COLUMN)
+        fail(PG_ERR_UNSUPPORTED, "expression: a FLOAT-typed CASE with the %s column %s as a branch (the reference narrows it to float per doc)",
+             bt == PG_TYPE_INT ? "INT" : "LONG", cols[(size_t)b.ref]->name.c_str());
+      if (b.kind == ExprBranch::CASE)
+        fail(PG_ERR_UNSUPPORTED, "expression: a FLOAT-typed CASE with an %s-typed CASE as a branch (the reference narrows it to float per doc)", bt == PG_TYPE_INT ? "INT" : "LONG");
+      pg_expr_step& st = prog.steps[b.step];
+      (b.slot == 0 ? st.lit : st.lit2) = (double)(float)b.ival;
+    }
+  }
+  return cols;
+}
+static void refuse_conditional(const ExprProgram& prog, const char* where, const std::string& text) {
+  if (prog.conditional) fail(PG_ERR_UNSUPPORTED, "a CASE, a comparison or a logical call %s (%s): inside SUM, MIN, MAX, AVG and MINMAXRANGE they run on the GPU path", where, short_text(text).c_str());
 }
 // One expression predicate, checked and resolved: the program, the operand columns, the raw DOUBLE predicate (the four transform functions'
 // getResultMetadata says DOUBLE, so the reference builds the raw DOUBLE evaluators of the predicate's type).  seg.mu held.
@@ -447,6 +540,7 @@ static ExprLeafSpec expr_leaf_spec(Segment& seg, const pg_filter_node& f, bool n
   std::string error;
   const int32_t st = expr_parse(f.column, prog, error);
   if (st != PG_OK) fail(st, "%s (in %s)", error.c_str(), short_text(text).c_str());
+  refuse_conditional(prog, "in a WHERE predicate", text);
   memset(&L.args, 0, sizeof(L.args));
   memset(&L.pred, 0, sizeof(L.pred));
   for (const std::string& name : prog.columns) {

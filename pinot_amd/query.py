@@ -293,6 +293,10 @@ class SqlError(ValueError):
     pass
 
 
+class _WhenError(SqlError):
+    """a construct the condition of a CASE does not take (IN, BETWEEN, LIKE, IS NULL ...): raised through the parser's own backtracking"""
+
+
 def _tokenize(sql: str) -> List[Tuple[str, str]]:
     pos = 0
     out = []
@@ -512,10 +516,12 @@ class _Parser:
             return f"'{t[1]}'"
         if t[0] != "id":
             raise SqlError(f"bad aggregation argument {t}")
+        if t[1].upper() == "CASE" and self.kw("WHEN"):
+            return self.case_expression()
         if self.peek() == ("op", "("):   # a function call: its name in lower case, without underscores (FunctionContext's canonical name)
             self.i += 1
             name = t[1].lower().replace("_", "")
-            argument = self.time_argument if name in self._TIME else self.expression
+            argument = self.time_argument if name in self._TIME or name in ("equals", "notequals") else self.else_argument if name == "case" else self.expression
             args = [argument()]
             while self.peek() == ("op", ","):
                 self.i += 1
@@ -523,6 +529,105 @@ class _Parser:
             self.expect_op(")")
             return f"{name}({','.join(args)})"
         return t[1]
+
+    # CASE WHEN c THEN x [WHEN ...] [ELSE y] END: case(c1,x1,...,cN,xN,else) as CalciteSqlParser compiles it (711-734):
+    # WHEN and THEN in pairs, the ELSE last, an omitted ELSE or ELSE NULL as the literal 'null'.  A condition is not a
+    # FilterContext here but a function call like any other: a > b stays greater_than(a,b) (PredicateComparisonRewriter touches WHERE and
+    # HAVING only), AND / OR are n-ary and flattened, NOT and parentheses nest.
+    _COMPARISON = {"=": "equals", "!=": "notequals", "<>": "notequals", ">": "greaterthan", ">=": "greaterthanorequal",
+                   "<": "lessthan", "<=": "lessthanorequal"}   # FunctionContext's canonical names: lower case, no underscores
+
+    def else_argument(self) -> str:
+        """an argument of the function form case(...): the last one may be the literal 'null', the omitted ELSE"""
+        if self.peek() == ("str", "null") and self.peek(1) == ("op", ")"):
+            self.i += 1
+            return "'null'"
+        return self.expression()
+
+    def case_expression(self) -> str:
+        args = []
+        while self.kw("WHEN"):
+            self.i += 1
+            args.append(self._condition_text(self.condition()))
+            self.expect_kw("THEN")
+            args.append(self.expression())
+        if self.kw("ELSE"):
+            self.i += 1
+            if self.kw("NULL"):
+                self.i += 1
+                args.append("'null'")
+            else:
+                args.append(self.expression())
+        else:
+            args.append("'null'")
+        self.expect_kw("END")
+        return f"case({','.join(args)})"
+
+    @staticmethod
+    def _condition_text(c) -> str:
+        op, items = c
+        return items[0] if op is None else f"{op}({','.join(items)})"
+
+    def _condition_list(self, word: str, op: str, operand):
+        parts = [operand()]
+        while self.kw(word):
+            self.i += 1
+            parts.append(operand())
+        if len(parts) == 1:
+            return parts[0]
+        flat = []
+        for p in parts:   # a AND (b AND c) is and(a,b,c)
+            flat.extend(p[1] if p[0] == op else [self._condition_text(p)])
+        return (op, flat)
+
+    def condition(self):
+        """(None, [text]) | ('and' | 'or', [texts]) of the condition that starts here"""
+        return self._condition_list("OR", "or", lambda: self._condition_list("AND", "and", self.condition_not))
+
+    def condition_not(self):
+        if self.kw("NOT"):
+            self.i += 1
+            return (None, [f"not({self._condition_text(self.condition_not())})"])
+        if self.peek() == ("op", "("):   # a group of conditions, or a parenthesised operand: try the group, fall back to the operand
+            mark, toks = self.i, list(self.toks)
+            try:
+                self.i += 1
+                c = self.condition()
+                self.expect_op(")")
+                t = self.peek()
+                if (t[0] == "op" and t[1] not in (")", ",")) or (t[0] == "num" and t[1].startswith("-")):
+                    raise SqlError("a parenthesised operand, not a group of conditions")
+                return c
+            except _WhenError:
+                raise
+            except SqlError:
+                self.i, self.toks = mark, toks
+        return self.comparison()
+
+    def condition_operand(self):
+        """(canonical text, is a non-numeric string literal)"""
+        t = self.peek()
+        if t[0] == "str" and not _is_number(t[1]):
+            self.i += 1
+            if "'" in t[1]:
+                raise SqlError(f"the literal {t[1]!r} holds a quote: the canonical text cannot carry it")
+            return f"'{t[1]}'", True
+        return self.expression(), False
+
+    def comparison(self):
+        left, left_text = self.condition_operand()
+        for word in ("IN", "BETWEEN", "LIKE", "IS"):
+            if self.kw(word) or (self.kw("NOT") and self.kw(word, 1)):
+                raise _WhenError(f"{'IS [NOT] NULL' if word == 'IS' else word} inside a WHEN: comparisons, AND, OR and NOT are its conditions")
+        op = self.take()
+        if op[0] != "op" or op[1] not in self._COMPARISON:
+            raise SqlError(f"expected a comparison inside a WHEN, got {op}")
+        right, right_text = self.condition_operand()
+        if left.startswith("'") and right.startswith("'"):
+            raise SqlError("a comparison of two literals")
+        if (left_text or right_text) and op[1] not in ("=", "!=", "<>"):
+            raise SqlError(f"the string literal {left if left_text else right} under {op[1]}: = and <> compare strings inside a WHEN")
+        return (None, [f"{self._COMPARISON[op[1]]}({left},{right})"])
 
     # The time-bucket transforms (DESIGN 4.9): GROUP BY / DISTINCT keys such as dateTrunc('day', ts).  Their arguments other than the value are
     # literals of any text (units, formats, time zones), printed single-quoted with their case kept; nowhere else is a non-numeric string literal
@@ -537,13 +642,15 @@ class _Parser:
             return f"'{t[1]}'"
         return self.expression()
 
-    _ARITHMETIC = frozenset(("add", "sub", "mult", "div", "plus", "minus", "times", "divide"))
+    _ARITHMETIC = frozenset(("add", "sub", "mult", "div", "plus", "minus", "times", "divide", "case"))
 
     def starts_expression(self) -> bool:
         """Does an expression start here, where a select item, a GROUP BY key or an ORDER BY expression is expected: one of the eight
         arithmetic function forms, a time-bucket transform, a parenthesis, or an operand followed by an infix operator?"""
         t, u = self.peek(), self.peek(1)
         if t == ("op", "("):
+            return True
+        if self.kw("CASE") and self.kw("WHEN", 1):
             return True
         if t[0] == "id" and u == ("op", "("):
             return t[1].lower().replace("_", "") in self._ARITHMETIC or t[1].lower().replace("_", "") in self._TIME
@@ -764,9 +871,16 @@ class _Parser:
                     text = t[1]
                 if t is not None and self.peek() == ("op", "("):
                     depth = 0
+                    in_case, last = False, ("op", "")
                     while True:
                         u = self.take()
-                        text += u[1]
+                        if u[0] == "eof":
+                            raise SqlError("unbalanced parentheses in ORDER BY")
+                        in_case = in_case or (u[0] == "id" and u[1].upper() == "CASE")
+                        if u[0] != "op" and last[0] != "op":   # CASE WHEN a ...: words stay apart
+                            text += " "
+                        text += "'%s'" % u[1].replace("'", "''") if u[0] == "str" and in_case else u[1]
+                        last = u
                         if u == ("op", "("):
                             depth += 1
                         if u == ("op", ")"):
