@@ -1,4 +1,4 @@
-// Device-side plan layout shared by the host planner (pg_plan.cpp) and the HIP kernels (pg_kernels.hip).
+// Device-side plan layout shared by the host planner (pg_plan.cpp) and the HIP kernels (pg_kernels*.hip).
 //
 // Execution model: a segment is cut into wave tiles of PG_WAVE_DOCS consecutive docIds.  One workgroup of
 // PG_BLOCK threads (16 wavefronts) is resident per CU; its wavefronts walk wave tiles independently (no barrier in the

@@ -1,7 +1,6 @@
-// pg_fast_i32range_d in a translation unit of its own (see PG_KERNEL in pg_kernels.hip): the device code is shared by inclusion, the
-// other kernels become unreferenced static functions here and are dropped.
-#define PG_KERNEL template <int PG_NOT_INSTANTIATED> static
-#include "pg_kernels.hip"
+// pg_fast_i32range_d in a translation unit of its own: next to the kernels of pg_kernels.hip it changed their register allocation at the
+// 128-VGPR limit (see the note there).
+#include "pg_kernel_agg.h"
 #include <type_traits>
 
 // Headline shape with the index program fused (PgQueryPlan::dense_fused): [AND of <= 4 OR-groups of dense postings] AND raw-INT range

@@ -32,7 +32,7 @@ typedef pg_d4 d4;
 typedef pg_d8 d8;
 
 // expr_load / expr_load_all / expr_eval: pg_expr_device.h (shared with the filter leaves of pg_kernels_exprpred.hip)
-DEVFN int64_t expr_order_key(double v) {   // order-preserving map double -> int64 (f64_order_key of pg_kernels.hip)
+DEVFN int64_t expr_order_key(double v) {   // order-preserving map double -> int64 (f64_order_key of pg_kernel_agg.h)
   const int64_t b = __double_as_longlong(v);
   return b ^ ((b >> 63) & 0x7FFFFFFFFFFFFFFFLL);
 }

@@ -19,8 +19,8 @@
 // wavefront still read neighbouring lines.  A translation unit of its own: the single-value kernels are compiled without any of this.
 #include <hip/hip_runtime.h>
 
-#define PG_KERNEL template <int PG_NOT_INSTANTIATED> static
-#include "pg_kernels.hip"
+#include "pg_kernel_agg.h"
+#include "pg_kernel_radix.h"
 
 // entry `idx` of a multi-value column's bit stream (64-bit bit offsets: 2^31 entries x 31 bits)
 DEVFN uint32_t mv_entry_at(const uint8_t* data, uint32_t idx, uint32_t bits) {

@@ -14,8 +14,7 @@
 // per accumulator at slot = dictId x R + replica.  16 wavefronts per workgroup, one workgroup per CU, <= 128 VGPRs.
 // Bytes per doc: entries x bits / 8 + the row starts (the int32 offsets of pg_segment.cpp: 4 B per doc, where the index's row-start bitmap
 // would be entries / 8) + 4 B of the value column.
-#define PG_KERNEL template <int PG_NOT_INSTANTIATED> static
-#include "pg_kernels.hip"
+#include "pg_kernel_agg.h"
 
 template <typename T> DEVFN const GAS T* mvg_sgpr_ptr(const void* ptr) {
   const uint64_t v = (uint64_t)ptr;

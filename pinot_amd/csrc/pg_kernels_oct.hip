@@ -34,8 +34,7 @@
 //                    doc and is kept in an LDS table of 32-bit counters by this kernel, flushed once per pass.
 //                    Survivors are appended to a tuple stream in HBM (key << payload bits | index | rank << log2m) in blocks of 1 024
 //                    entries claimed per wavefront with one global atomic; the stream is the input of pg_p2_scatter_stream.
-#define PG_KERNEL template <int PG_NOT_INSTANTIATED> static
-#include "pg_kernels.hip"
+#include "pg_kernel_agg.h"
 
 #include "pg_oct_layout.h"
 

@@ -1,5 +1,5 @@
 // Partition pipeline v2 — group-by over key spaces beyond one LDS table (PG_AGG_RADIX with PgQueryPlan::p2), a translation unit
-// of its own (256-thread scatter workgroups; the kernels of pg_kernels.hip become uninstantiated templates here).
+// of its own (256-thread scatter workgroups).
 //
 // Reference work: DictionaryBasedGroupKeyGenerator's map-based holders (core/query/aggregation/groupby/
 // DictionaryBasedGroupKeyGenerator.java:416-446,629-668,993-1084) + the aggregateGroupBySV loops of the aggregation functions
@@ -25,8 +25,8 @@
 #ifndef PG_WAVES_PER_BLOCK
 #define PG_WAVES_PER_BLOCK 4
 #endif
-#define PG_KERNEL template <int PG_NOT_INSTANTIATED> static
-#include "pg_kernels.hip"
+#include "pg_kernel_agg.h"
+#include "pg_kernel_radix.h"
 #include "pg_oct_layout.h"
 
 #define P2_THREADS (PG_P2_WAVES * 64)

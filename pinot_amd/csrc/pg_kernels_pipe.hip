@@ -23,8 +23,7 @@
 #ifndef PG_PIPE_GRAIN
 #define PG_PIPE_GRAIN 8
 #endif
-#define PG_KERNEL template <int PG_NOT_INSTANTIATED> static
-#include "pg_kernels.hip"
+#include "pg_kernel_agg.h"
 
 extern "C" const int pg_pipe_waves_per_block = PG_WAVES_PER_BLOCK;   // the host launches pg_fast_i32range_p with this many wavefronts
 

@@ -12,8 +12,7 @@
 #ifndef PG_SCAN_BUFFERS
 #define PG_SCAN_BUFFERS 2   // tiles in rotation per wavefront; 3 and 4 measured 2 % SLOWER over 10^9 docs (0.564 / 0.579 / 0.578 ms), the same over 10^8
 #endif
-#define PG_KERNEL template <int PG_NOT_INSTANTIATED> static
-#include "pg_kernels.hip"
+#include "pg_kernel_filter.h"
 
 extern "C" const int pg_scan_waves_per_block = PG_WAVES_PER_BLOCK;   // the host launches pg_fast_i32range_fp with this many wavefronts
 

@@ -31,8 +31,7 @@
 // wide: 24-bit images, 7.625 B/doc): 1.21-1.22 ms against 1.37-1.43 on the same box, and the loaders alone (-DPG_SPEC_NO_CONSUME) take that
 // time too: the kernel sits at its loaders' stream, the consumers are not the long path.  PG_NO_NARROW_IMAGE keeps the raw layout.
 #define PG_WAVES_PER_BLOCK 12
-#define PG_KERNEL template <int PG_NOT_INSTANTIATED> static
-#include "pg_kernels.hip"
+#include "pg_kernel_agg.h"
 
 #define SPEC_LOADERS 4
 #ifndef SPEC_TILES

@@ -48,8 +48,7 @@
 #define SD_EXEC_ROUNDS 0
 #endif
 #define PG_WAVES_PER_BLOCK SD_WAVES
-#define PG_KERNEL template <int PG_NOT_INSTANTIATED> static
-#include "pg_kernels.hip"
+#include "pg_kernel_filter.h"
 #include "pg_oct_layout.h"
 
 #define SD_PAD 16u                                      // a field's dword pair may reach one dword past the column's last byte

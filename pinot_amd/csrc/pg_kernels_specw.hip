@@ -20,8 +20,7 @@
 #define SW_MIN_WAVES_PER_SIMD 4   // 16 wavefronts per CU whatever the workgroup size (16 / SW_WAVES workgroups)
 #endif
 #define PG_WAVES_PER_BLOCK SW_WAVES
-#define PG_KERNEL template <int PG_NOT_INSTANTIATED> static
-#include "pg_kernels.hip"
+#include "pg_kernel_filter.h"
 #include "pg_oct_layout.h"
 
 #define SW_PAD 16u                                      // a field's dword pair may reach one dword past the column's last byte

@@ -1,8 +1,10 @@
 // Oct layout (shared by pg_kernels_oct.hip and the oct-layout scatter of pg_kernels_part.hip): lane L owns the 8 CONSECUTIVE docs
 // 8L .. 8L+7 of a 512-doc sub-tile, so the 8 values of a b-bit column are exactly b bytes at byte offset b x L — one byte permute
 // (v_perm_b32: alignment + endianness in one instruction, its selector a per-lane constant) per dword and compile-time field positions
-// after it (1.5-4 VALU per value; the quad layout's run-time-width windows cost 5-9).  Included after pg_kernels.hip.
+// after it (1.5-4 VALU per value; the quad layout's run-time-width windows cost 5-9).
 #pragma once
+
+#include "pg_kernel_common.h"
 
 typedef uint32_t u32x3 __attribute__((ext_vector_type(3)));
 typedef u32x3 u32x3_a4 __attribute__((aligned(4)));

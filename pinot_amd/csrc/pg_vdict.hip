@@ -105,7 +105,7 @@ __global__ void pg_vdict_ids_kernel(const uint64_t* __restrict__ keys, const uin
 }
 
 // One thread per output dword of the bit-packed forward index: a wave tile of 2 048 values is a big-endian bit stream of 64 x bits
-// dwords starting on a dword boundary (packed_wtile_base in pg_kernels.hip).
+// dwords starting on a dword boundary (packed_wtile_base in pg_kernel_filter.h).
 __global__ void pg_vdict_pack_kernel(const uint32_t* __restrict__ ids, int64_t n, int bits, uint32_t* __restrict__ out, int64_t n_dwords) {
   const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (w >= n_dwords) return;

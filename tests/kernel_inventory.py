@@ -191,7 +191,7 @@ ENTRIES = [
     E("pg_nogroup_da", "bench", "SELECT SUM(m_d), MIN(m_d), MAX(m_d), COUNT(*) FROM gpuBench", ALL),
     E("pg_nogroup_dg", "bench", "SELECT SUM(m_s), MIN(m_s), MAX(m_s), COUNT(*) FROM gpuBench", ALL),
     E("pg_nogroup_dl", "wide", "SELECT SUM(kq), MIN(kq), MAX(kq), COUNT(*) FROM wide", ALL),
-    # ---- wide group columns, 64-bit and DOUBLE sources: the general aggregator (pg_kernels.hip) and the wide pipeline (pg_kernels_pipe.hip) ----
+    # ---- wide group columns, 64-bit and DOUBLE sources: the general aggregator (aggregate_wtile of pg_kernel_agg.h, in the kernels of pg_kernels.hip) and the wide pipeline (pg_kernels_pipe.hip) ----
     E("pg_fast_none_w", "wide", "SELECT k, SUM(lm), SUM(r) FROM wide GROUP BY k LIMIT 5000", ALL),
     E("pg_fast_none_wd", "wide", "SELECT k, SUM(dm), SUM(lm) FROM wide GROUP BY k LIMIT 5000", ALL),
     E("pg_fast_multi_w", "wide", "SELECT k, SUM(lm) FROM wide WHERE r < 900 AND lm > 0 GROUP BY k LIMIT 5000", ALL),

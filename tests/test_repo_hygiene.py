@@ -51,3 +51,14 @@ def test_documents_cite_things_that_exist():
             if not m.group(1).endswith("_") and m.group(1) not in src:
                 bad.add((doc, m.group(1)))
     assert not bad, sorted(bad)
+
+
+def test_no_source_file_is_included_as_a_header():
+    """Kernel files share device code through headers (pg_kernel_*.h): nothing under pinot_amd/csrc/ includes a .hip file."""
+    bad = []
+    for f in glob.glob(os.path.join(ROOT, "pinot_amd", "csrc", "**", "*"), recursive=True):
+        if os.path.isfile(f) and not f.endswith((".o", ".so", ".log")):
+            for n, line in enumerate(open(f, errors="ignore"), 1):
+                if re.match(r"\s*#\s*include\s*[\"<][^\">]*\.hip[\">]", line):
+                    bad.append((os.path.relpath(f, ROOT), n))
+    assert not bad, bad
