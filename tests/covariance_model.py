@@ -19,7 +19,8 @@ from fractions import Fraction
 
 import numpy as np
 
-from tests.variance_model import MAX_DOC_PER_CALL, as_doubles, fx_exp_of, round_fraction, same_bits  # noqa: F401  (shared with the callers)
+from tests.variance_model import (MAX_DOC_PER_CALL, as_doubles, fx_exp_of, int_power_sums, integer_values, round_fraction, same_bits,  # noqa: F401
+                                   sum_int64)   # (shared with the callers)
 
 NEG_INF = float("-inf")
 FUNCTIONS = ("COVARPOP", "COVARSAMP")
@@ -43,6 +44,30 @@ def exact_sum(doubles) -> Fraction:
 def exact_tuple(xs, ys) -> tuple:
     assert len(xs) == len(ys)
     return (round_fraction(exact_sum(xs)), round_fraction(exact_sum(ys)), round_fraction(exact_sum(products(xs, ys))), len(xs))
+
+
+def exact_sum_of_array(d: np.ndarray) -> Fraction:
+    """exact_sum over a float64 array of finite values: the 53-bit mantissas summed as integers per binary exponent"""
+    d = np.asarray(d, dtype=np.float64)
+    if d.size == 0:
+        return Fraction(0)
+    m, e = np.frexp(d)
+    mant, e = np.ldexp(m, 53).astype(np.int64), e.astype(np.int64) - 53   # d = mant x 2^e, |mant| < 2^53: exact
+    lowest = int(e.min())
+    total = 0
+    for x in np.unique(e):
+        total += sum_int64(mant[e == x]) << (int(x) - lowest)
+    return Fraction(total) * Fraction(2) ** lowest
+
+
+def exact_tuple_of_ints(x_values, tx: str, y_values, ty: str) -> tuple:
+    """exact_tuple over two INT / LONG columns, through the integer path: the sums of x and y as integers (tests/variance_model.py), the
+    products fl(x * y) by one IEEE multiply each in numpy and their exact sum per exponent"""
+    assert len(x_values) == len(y_values)
+    xi, yi = integer_values(x_values, tx), integer_values(y_values, ty)
+    xd, yd = xi.astype(np.float64), yi.astype(np.float64)   # exact: they are (double) values already
+    sx, sy = int_power_sums(xi, 1)[0], int_power_sums(yi, 1)[0]
+    return (round_fraction(Fraction(sx)), round_fraction(Fraction(sy)), round_fraction(exact_sum_of_array(xd * yd)), len(xi))
 
 
 def reference_tuple(xs, ys, grouped: bool = False) -> tuple:

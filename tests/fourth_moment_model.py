@@ -19,7 +19,7 @@ from fractions import Fraction
 
 import numpy as np
 
-from tests.variance_model import as_doubles, fx_exp_of, round_fraction, same_bits, ulp  # noqa: F401  (shared with the variance model)
+from tests.variance_model import as_doubles, fx_exp_of, int_power_sums, integer_values, round_fraction, same_bits, ulp  # noqa: F401  (shared with the variance model)
 
 NAN = float("nan")
 FUNCTIONS = ("SKEWNESS", "KURTOSIS")
@@ -40,11 +40,23 @@ def power_sums(doubles):
     return (n,) + tuple(Fraction(sum(i ** k for i in ints), scale ** k) for k in (1, 2, 3, 4))
 
 
-def exact_moments(doubles):
-    """(n, m1, m2, m3, m4) as exact Fractions through the power sums (n >= 1)"""
-    n, s1, s2, s3, s4 = power_sums(doubles)
+def _moments_of_sums(n, s1, s2, s3, s4):
     return (n, s1 / n, s2 - s1 * s1 / n, s3 - 3 * s1 * s2 / n + 2 * s1 ** 3 / n ** 2,
             s4 - 4 * s1 * s3 / n + 6 * s1 * s1 * s2 / n ** 2 - 3 * s1 ** 4 / n ** 3)
+
+
+def exact_moments(doubles):
+    """(n, m1, m2, m3, m4) as exact Fractions through the power sums (n >= 1)"""
+    return _moments_of_sums(*power_sums(doubles))
+
+
+def exact_tuple_of_ints(values, data_type: str) -> tuple:
+    """exact_tuple(as_doubles(values, data_type)) for an INT / LONG column, through the integer power sums of tests/variance_model.py"""
+    ints = integer_values(values, data_type)
+    if len(ints) == 0:
+        return 0, NAN, NAN, NAN, NAN
+    n, m1, m2, m3, m4 = _moments_of_sums(len(ints), *(Fraction(s) for s in int_power_sums(ints, 4)))
+    return n, round_fraction(m1), round_fraction(m2), round_fraction(m3), round_fraction(m4)
 
 
 def direct_moments(doubles):

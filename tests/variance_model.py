@@ -52,6 +52,13 @@ def round_fraction(x: Fraction) -> float:
         return sign * math.inf
 
 
+def _moments_of_sums(n: int, sx: int, sq: int, scale: int):
+    """(n, sum x, sum x^2 - (sum x)^2 / n) from the integer power sums of the values times `scale`"""
+    if n == 0:
+        return 0, Fraction(0), Fraction(0)
+    return n, Fraction(sx, scale), Fraction(n * sq - sx * sx, n * scale * scale)
+
+
 def exact_moments(doubles):
     """(n, sum x, sum x^2 - (sum x)^2 / n) as exact Fractions (m2 = 0 for n = 0)"""
     n = len(doubles)
@@ -61,12 +68,64 @@ def exact_moments(doubles):
     parts = [v.as_integer_ratio() for v in doubles]
     scale = max(d for _, d in parts)   # a power of two
     ints = [m * (scale // d) for m, d in parts]
-    sx, sq = sum(ints), sum(i * i for i in ints)
-    return n, Fraction(sx, scale), Fraction(n * sq - sx * sx, n * scale * scale)
+    return _moments_of_sums(n, sum(ints), sum(i * i for i in ints), scale)
 
 
 def exact_tuple(doubles) -> tuple:
     n, sx, m2 = exact_moments(doubles)
+    return n, round_fraction(sx), round_fraction(m2)
+
+
+# ---- the integer path: INT / LONG columns of millions of docs -----------------------------------------------------------------------------------
+# The (double) of an INT or a LONG is an integer, so its power sums are integers: numpy computes them in int64 where a power stays below
+# 2^62 (chunked sums of the 32-bit halves, totalled as Python ints) and in object arrays of Python ints beyond.  The sums feed the same
+# construction as the Fraction path; tests/test_model_int_path.py pins the two to each other.
+_CHUNK = 1 << 20
+
+
+def integer_values(values, data_type: str) -> np.ndarray:
+    """getDoubleValuesSV of an INT / LONG column as exact integers: an int64 array, or an object array of Python ints where a (double)-rounded
+    LONG reaches 2^63"""
+    assert data_type in ("INT", "LONG"), data_type
+    a = np.asarray(values, dtype=np.int64)
+    if data_type == "INT":
+        return a
+    d = a.astype(np.float64)   # rounds to nearest-even, as (double) does
+    if d.size == 0 or np.abs(d).max() < 2.0**63:
+        return d.astype(np.int64)
+    return np.array([int(v) for v in d], dtype=object)
+
+
+def sum_int64(a: np.ndarray) -> int:
+    """the exact total of an int64 array as a Python int"""
+    total = 0
+    for c0 in range(0, a.size, _CHUNK):
+        c = a[c0:c0 + _CHUNK]
+        total += (int((c >> 32).sum()) << 32) + int((c & 0xFFFFFFFF).sum())   # |high halves| < 2^31 and low halves < 2^32, 2^20 of them
+    return total
+
+
+def int_power_sums(ints: np.ndarray, kmax: int) -> tuple:
+    """(S1, .., S_kmax) of integer_values() as Python ints"""
+    if len(ints) == 0:
+        return (0,) * kmax
+    bits = 64 if ints.dtype == object else int(np.abs(ints.astype(np.float64)).max()).bit_length()
+    out, p = [], None   # p: the k-th powers, an int64 array while they stay below 2^62, then an object array of Python ints
+    for k in range(1, kmax + 1):
+        if k * bits <= 62:
+            p = ints if k == 1 else p * ints
+            out.append(sum_int64(p))
+        else:
+            base = ints if ints.dtype == object else ints.astype(object)
+            p = base if k == 1 else (p if p.dtype == object else p.astype(object)) * base
+            out.append(int(p.sum()))
+    return tuple(out)
+
+
+def exact_tuple_of_ints(values, data_type: str) -> tuple:
+    """exact_tuple(as_doubles(values, data_type)) for an INT / LONG column, through the integer path"""
+    ints = integer_values(values, data_type)
+    n, sx, m2 = _moments_of_sums(len(ints), *int_power_sums(ints, 2), 1)
     return n, round_fraction(sx), round_fraction(m2)
 
 
